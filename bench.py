@@ -318,6 +318,28 @@ def strong_scaling_leg(args, torch, group, model_local, rank, local_rank, world,
     return out
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, out):
+    """The arrays a caller of the timed path receives (hsqp_download after `iterate(1, take_step=False)`), as float64 .npy files:
+    x, u (the resident trajectory), dx, du (the QP step) and the performance index before / after the step, one row
+    (merit, cost, dynamics_sse, equality_sse) per instance.  At B = 256, N = 100 that is 38 MB in all; a larger batch is cut to a fixed,
+    seeded sample of instances (the same for every array, listed in instances.npy) that fits DUMP_BYTES."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: out[k] for k in ("x", "u", "dx", "du")}
+    for k in ("perf_before", "perf_after"):
+        arrays[k] = np.array([[p["merit"], p["cost"], p["dynamics_sse"], p["equality_sse"]] for p in out[k]])
+    B = arrays["x"].shape[0]
+    per_instance = sum(a[0].size * 8 for a in arrays.values())
+    if B * per_instance > DUMP_BYTES:
+        keep = np.sort(np.random.Generator(np.random.PCG64(0)).choice(B, max(1, DUMP_BYTES // per_instance - 1), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["instances"] = keep
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def self_spawn(args):
     """`python bench.py --gpus N` outside torchrun: re-launch under torch.distributed.run with N ranks (one per GPU)."""
     import socket
@@ -350,7 +372,11 @@ def main():
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling / data-path leg")
     ap.add_argument("--sustained", type=int, default=-1, help="steps of the sustained leg behind the timed region (default: max(300, --steps); 0: none)")
     ap.add_argument("--force-strong", action="store_true", help="run the data-path leg on one GPU too (scatter / gather degenerate to copies): exercises hsqp_upload_device / hsqp_download_device")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's solution: x, u, dx, du, perf_before, perf_after) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     from wb_humanoid_mpc_amd.distributed import Group, aggregate_throughput, env_rank, shard_seed
     rank, local_rank, world = env_rank()
@@ -408,6 +434,8 @@ def main():
     elapsed = time.perf_counter() - t0
     kms /= args.steps
     clocks_after = gpu_clocks(local_rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver.download())   # outside the timed region: the solution of its last step
     # sustained rate: the same handle, the same resident problem, >= 300 more steps (the timed region above is the driver's --steps: 83 ms at the
     # default 20 — too short to show a box that throttles); never `value`
     sus_steps = max(300, args.steps) if args.sustained < 0 else args.sustained

@@ -1,25 +1,53 @@
 """TEST INFRASTRUCTURE: builds (on the machine it runs on: g++ -O3 -march=native -fopenmp) and drives oracle/cpu_baseline.cpp, the
 timed CPU baseline of bench.py.  Only tests/ and bench.py's cpu_baseline leg import this."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "cpu_baseline.cpp")
-LIB = os.path.join(_HERE, "_native", "libcpu_baseline.so")     # built per machine, never shipped (git- and gpurun-ignored)
+LIB = os.path.join(_HERE, "_native", "libcpu_baseline.so")     # built per machine (-march=native), never shipped (git-ignored)
 FLAGS = ["-O3", "-march=native", "-std=c++17", "-fPIC", "-fopenmp", "-Wno-unknown-pragmas", "-shared"]
 _dp = C.POINTER(C.c_double)
 
 
+def _writable(d):
+    try:
+        os.makedirs(d, exist_ok=True)
+    except OSError:
+        return False
+    return os.access(d, os.W_OK | os.X_OK)
+
+
+def _lib_path(deps):
+    """oracle/_native/ where the tree is writable; else (a read-only checkout) a private per-user directory under the system
+    temp directory, the file named by a hash of the sources, flags and CPU so that no other build is ever picked up."""
+    if _writable(os.path.dirname(LIB)):
+        return LIB
+    h = hashlib.sha256(" ".join(FLAGS + [cpu_model()]).encode())
+    for d in deps:
+        with open(d, "rb") as f:
+            h.update(f.read())
+    cache = os.path.join(tempfile.gettempdir(), f"hsqp_cpu_baseline_{os.getuid()}")
+    os.makedirs(cache, mode=0o700, exist_ok=True)
+    if os.stat(cache).st_uid != os.getuid() or not os.access(cache, os.W_OK | os.X_OK):
+        raise RuntimeError(f"{cache} is not a private writable directory: cannot build the CPU baseline")
+    return os.path.join(cache, f"libcpu_baseline_{h.hexdigest()[:16]}.so")
+
+
 def build(force=False):
     csrc = os.path.join(_HERE, "..", "wb_humanoid_mpc_amd", "csrc")
-    deps = [SRC] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
-    if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        subprocess.check_call(["g++", *FLAGS, SRC, "-o", LIB])
-    return LIB
+    deps = [SRC] + sorted(os.path.join(csrc, f) for f in os.listdir(csrc))
+    lib = _lib_path(deps)
+    if force or not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
+        tmp = f"{lib}.{os.getpid()}.tmp"
+        subprocess.check_call(["g++", *FLAGS, SRC, "-o", tmp])
+        os.replace(tmp, lib)     # concurrent builders never load a half-written file
+    return lib
 
 
 def cpu_model():

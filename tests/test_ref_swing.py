@@ -6,11 +6,12 @@ third-party headers).  tests/golden/ref_swing.npz holds its outputs for every ga
 (tests/golden/make_ref_swing_golden.py).  Checked against them:
   * the host mirror wb_humanoid_mpc_amd/reference.py (CubicSpline, SplineCpg, SwingTrajectoryPlanner, tile_gait, mode flags),
   * the device generator hsqp_params.h — kernel source compiled for the host here, the HIP kernel k_params through the C ABI on the GPU.
-Where the library itself is present (build container: always; GPU box: it travels with the snapshot) the mirror is also
-compared with it directly on random schedules."""
+On random schedules the mirror is compared with what the library returned for them (tests/golden/ref_swing_random.npz), and
+with the library itself where it is present."""
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -20,6 +21,7 @@ from wb_humanoid_mpc_amd.reference import (MODE_BY_NAME, CubicSpline, ModeSchedu
                                            mode_to_contact_flags, pack_reference, swing_config, tile_gait)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "golden"))
 G = np.load(os.path.join(HERE, "golden", "ref_swing.npz"))
 GAITS = [str(g) for g in G["gaits"]]
 _dp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
@@ -144,36 +146,36 @@ def test_device_kernel_against_reference_compiled_values(model):
         s.close()
 
 
-def _ref_or_skip():
+def _ref_or_none():
+    """The compiled reference where it is present (then checked against the fixture too), else None."""
     import ref_swing
-    if not ref_swing.available():
-        pytest.skip("oracle/_ref/libref_swing.so not present and /root/reference not mounted")
-    return ref_swing.RefSwing()
+    return ref_swing.RefSwing() if ref_swing.available() else None
 
 
 def test_mode_numbers_against_reference_compiled_code():
-    ref = _ref_or_skip()
-    for name, m in MODE_BY_NAME.items():
-        assert ref.stance_legs(m) == mode_to_contact_flags(m), name
+    R = np.load(os.path.join(HERE, "golden", "ref_swing_random.npz"))
+    assert sorted(MODE_BY_NAME.values()) == list(R["mode_numbers"])
+    ref = _ref_or_none()
+    for m, want in zip(R["mode_numbers"], R["stance_legs"]):
+        assert mode_to_contact_flags(m) == tuple(bool(w) for w in want), m
+        if ref is not None:
+            assert ref.stance_legs(m) == tuple(bool(w) for w in want), m
 
 
 def test_host_planner_against_the_reference_library_on_random_schedules(model, rng):
-    """Random mode sequences (all four modes, random durations) with random planner settings, compared with the compiled
-    reference directly; sequences the reference rejects (a swing without lift-off / touch-down) must be rejected by the mirror too."""
-    ref = _ref_or_skip()
+    """Random mode sequences (all four modes, random durations) with random planner settings, compared with what the compiled
+    reference returned for them (tests/golden/ref_swing_random.npz, tests/golden/make_ref_swing_random_golden.py; the library itself
+    too where it is present); sequences the reference rejects (a swing without lift-off / touch-down) must be rejected by the mirror too."""
+    import make_ref_swing_random_golden as mk
+    R = np.load(os.path.join(HERE, "golden", "ref_swing_random.npz"))
+    ref = _ref_or_none()
     accepted = rejected = 0
-    for trial in range(60):
-        n_ev = int(rng.integers(2, 14))
-        ev = np.cumsum(rng.uniform(0.05, 0.7, n_ev))
-        seq = rng.integers(0, 4, n_ev + 1)
-        if trial % 3:
-            seq[0] = seq[-1] = 3      # most schedules start and end in stance like the reference's own
-        cfg = dict(model.swing)
-        cfg.update(liftOffVelocity=rng.uniform(0, 0.3), touchDownVelocity=-rng.uniform(0, 0.3), swingHeight=rng.uniform(0.02, 0.2),
-                   touchDownHeightOffset=rng.uniform(-0.01, 0.01), swingTimeScale=rng.uniform(0.1, 0.6))
-        terrain = rng.uniform(-0.05, 0.05)
-        t = np.sort(rng.uniform(ev[0] - 0.2, ev[-1] + 0.2, 64))
-        ok, want, modes = ref.swing_planner(cfg, ev, seq, t, terrain)
+    for i, (cfg, ev, seq, t, terrain) in enumerate(mk.random_cases(model, rng)):
+        assert np.array_equal(t, R["t"][i]) and terrain == R["terrain"][i], f"schedule {i} is not the one the fixture was made from"
+        ok, want, modes = bool(R["ok"][i]), R["values"][i], R["modes"][i]
+        if ref is not None:
+            r_ok, r_want, r_modes = ref.swing_planner(cfg, ev, seq, t, terrain)
+            assert r_ok == ok and (not ok or (np.array_equal(r_want, want) and np.array_equal(r_modes, modes))), i
         try:
             planner = SwingTrajectoryPlanner(cfg, ModeSchedule(ev, seq), terrain)
         except RuntimeError:
@@ -182,9 +184,9 @@ def test_host_planner_against_the_reference_library_on_random_schedules(model, r
             continue
         assert ok
         accepted += 1
-        for i, tk in enumerate(t):
-            assert planner.schedule.mode_at(tk) == modes[i]
+        for k, tk in enumerate(t):
+            assert planner.schedule.mode_at(tk) == modes[k]
             for leg in range(2):
                 got = (*planner.z_refs(leg, tk), planner.impact_proximity(leg, tk))
-                np.testing.assert_allclose(got, want[i, leg], rtol=1e-12, atol=1e-11)
+                np.testing.assert_allclose(got, want[k, leg], rtol=1e-12, atol=1e-11)
     assert accepted >= 15 and rejected >= 5
