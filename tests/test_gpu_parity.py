@@ -876,7 +876,7 @@ def test_value_pass_on_quads_of_lanes_equals_the_phase_form(model):
 
 def _poisoned_and_clean(model, make, **solver_kw):
     """Two solves of the same problem: on a handle created with HSQP_POISON_LDS (every kernel launch preceded by one that fills the LDS of every
-    CU with NaN bit patterns: csrc/hsqp_capi.hip, k_poison_lds) and on a clean one (created second: the flag is process-wide and set at hsqp_create)."""
+    CU with NaN bit patterns: csrc/hsqp_capi.hip, k_poison_lds) and on a clean one (the flags are read at hsqp_create and belong to the handle)."""
     from wb_humanoid_mpc_amd.solver import HipSqpSolver
     outs = []
     for poison in (True, False):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # (GPU) A/B of the whole-body LQ approximation: limb-lane form (k_lq_limb + k_lq_rows + k_lq_chain, hsqp_lql.h) against the phase form (k_lq<true>,
-# HSQP_LQ_PHASE_FORM=1) and against every library under wb_humanoid_mpc_amd/variants/: parity subset first, then bench lines, then the
-# rocprofv3 kernel stats of the product library (the split between the two limb-form kernels).
+# HSQP_LQ_PHASE_FORM=1): parity subset first, then bench lines, then the rocprofv3 kernel stats of the product library (the split between the
+# two limb-form kernels).
 # Usage: gpurun -- 'TESTS="tests/test_gpu_parity.py -k lq_blocks" bash tools/gpu_lq_ab.sh'
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
@@ -15,13 +15,9 @@ for line in sys.stdin:
     elif "rror" in line: print(line[:300])
 '; }
 {
-libs=("" $(ls wb_humanoid_mpc_amd/variants/libhsqp_*.so 2>/dev/null | sed 's/.*libhsqp_//; s/\.so//'))
-for v in "${libs[@]}"; do
-  lib=$PWD/wb_humanoid_mpc_amd/libhsqp_hip.so; [ -n "$v" ] && lib=$PWD/wb_humanoid_mpc_amd/variants/libhsqp_$v.so
-  echo "== ${v:-product}"
-  [ -n "$TESTS" ] && HSQP_LIB=$lib timeout 900 python -m pytest $TESTS -m gpu -x -q 2>&1 | tail -5
-  for rep in 1 2; do HSQP_LIB=$lib timeout 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS} 2>&1 | line; done
-done
+echo "== product"
+[ -n "$TESTS" ] && timeout 900 python -m pytest $TESTS -m gpu -x -q 2>&1 | tail -5
+for rep in 1 2; do timeout 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS} 2>&1 | line; done
 echo "== product, phase form (HSQP_LQ_PHASE_FORM=1)"
 for rep in 1 2; do HSQP_LQ_PHASE_FORM=1 timeout 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS} 2>&1 | line; done
 for shape in "32 100" "64 100" "128 100"; do

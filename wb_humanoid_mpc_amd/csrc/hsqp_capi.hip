@@ -27,45 +27,24 @@ using namespace hsqp;
 
 namespace {
 
-// launch shapes of the LQ kernels (overridable for tuning builds: tools/build_variants.py)
-#ifndef HSQP_LQ_THREADS
-#define HSQP_LQ_THREADS 128   /* 40 KB workspace: 4 workgroups of 2 waves per CU, no register spills */
-#endif
-#ifndef HSQP_LQ_WPE
-#define HSQP_LQ_WPE 2
-#endif
-#ifndef HSQP_LQV_THREADS
-#define HSQP_LQV_THREADS 64   /* value-only pass: its phases rarely have more than one wave of work; one wave needs no barrier hardware (A/B: 0.95 vs 0.99 ms) */
-#endif
-#ifndef HSQP_LQV_WPE
-#define HSQP_LQV_WPE 2
-#endif
-constexpr int LQ_THREADS = HSQP_LQ_THREADS;
+// launch shapes of the LQ kernels
+constexpr int LQ_THREADS = 128, LQ_WPE = 2;    // 40 KB workspace: 4 workgroups of 2 waves per CU, no register spills
+constexpr int LQV_THREADS = 64, LQV_WPE = 2;   // value-only pass (19.2 KB workspace: 8 one-wave workgroups per CU): its phases rarely have more than one wave
+                                               // of work; one wave needs no barrier hardware (A/B: 0.95 vs 0.99 ms)
 
-#ifndef HSQP_VALUE_QUAD_MIN_NODES
-#define HSQP_VALUE_QUAD_MIN_NODES 2048   /* handles sized below this keep the phase form of the whole-body value pass (hsqp_create) */
-#endif
-#ifndef HSQP_LQ_LIMB_MIN_NODES
-#define HSQP_LQ_LIMB_MIN_NODES 2048    /* handles sized below this keep the phase form of the whole-body LQ kernel (hsqp_create) */
-#endif
-#ifndef HSQP_PROJ_THREADS
-#define HSQP_PROJ_THREADS 256
-#endif
-#ifndef HSQP_PROJ_WPE
-#define HSQP_PROJ_WPE 3
-#endif
-constexpr int PROJ_THREADS = HSQP_PROJ_THREADS;   // 49.5 KB workspace: three workgroups of four waves per CU
+constexpr size_t VALUE_QUAD_MIN_NODES = 2048;   // handles sized below this keep the phase form of the whole-body value pass (hsqp_create)
+constexpr size_t LQ_LIMB_MIN_NODES = 2048;      // handles sized below this keep the phase form of the whole-body LQ kernel (hsqp_create)
+constexpr int PROJ_THREADS = 256, PROJ_WPE = 3;   // 49.5 KB workspace: three workgroups of four waves per CU
 static_assert(PROJ_THREADS >= 256 && PROJ_THREADS % 64 == 0, "project_node hoists its staging loads assuming >= 256 threads; the Gram tiles are dealt to waves 0..3");
 // Every kernel hands its workgroup size to the device functions as the CONSTANT it is launched with (Ctx::nthreads), not as blockDim.x: the item loops
 // (WG_FOR) then have constant strides and trip counts, and the paths written for other workgroup shapes (the host build's) are not compiled into the
 // kernels — k_riccati alone shrank from 16.7 k to 9 k instructions and from 1.518 to 1.463 ms (256 instances; 1.378 -> 1.317 at 32).
 constexpr int RIC_THREADS = 512;
-constexpr int LQV_THREADS = HSQP_LQV_THREADS;   // value-only LQ pass (19.2 KB workspace: 8 one-wave workgroups per CU)
 static_assert(sizeof(LqWST<false>) <= 163840 / 8, "value-only workspace: eight workgroups per CU");
 
 extern __shared__ __attribute__((aligned(16))) unsigned char hsqp_smem[];
 
-// ---- test aid (HSQP_POISON_LDS in the environment at hsqp_create; process-wide): every kernel launch is preceded by one that fills the LDS of every CU
+// ---- test aid (HSQP_POISON_LDS in the environment at hsqp_create: hsqp_handle::poison_lds): every kernel launch of the handle is preceded by one that fills the LDS of every CU
 // with NaN bit patterns.  LDS keeps what the previous kernel left there, so a kernel that reads a word it never wrote (say a padding row that is
 // "multiplied by zero") works until the leftover happens to be a NaN — tests/test_gpu_parity.py runs the iteration with and without the poison
 // and asks for the same bits.
@@ -74,21 +53,16 @@ __global__ __launch_bounds__(256) void k_poison_lds() {
   volatile unsigned long long* p = reinterpret_cast<volatile unsigned long long*>(hsqp_smem);
   for (int i = threadIdx.x; i < POISON_LDS_BYTES / 8; i += 256) p[i] = 0x7ff8dead7ff8deadull;   // a NaN as a double and as two floats
 }
-bool g_poison_lds = false;
-bool g_poison_hbm = false;                 // HSQP_POISON_HBM (test aid, read at hsqp_create): every device buffer the library allocates starts as NaN bit patterns
-// (0xFF bytes) instead of whatever the allocator returns — usually zeros, which hide a read of something never written.  Not the LQ record: the limb-lane
-// kernels rely on its zero fill (hsqp_lql.h).
-inline void poison_hbm(void* p, size_t bytes) { if (g_poison_hbm && p) (void)hipMemset(p, 0xFF, bytes); }
-int g_poison_blocks = 512;                 // two per CU (set from the device's CU count at hsqp_create)
+// every kernel launch of the library: `h` is the handle in scope
 #define HSQP_LAUNCH(kernel, grid, block, lds, st, ...)                                                                  \
   do {                                                                                                                 \
-    if (g_poison_lds) hipLaunchKernelGGL(k_poison_lds, dim3(g_poison_blocks), dim3(256), POISON_LDS_BYTES, (st));      \
+    if (h->poison_lds) hipLaunchKernelGGL(k_poison_lds, dim3(h->poison_blocks), dim3(256), POISON_LDS_BYTES, (st));    \
     hipLaunchKernelGGL(kernel, (grid), (block), (lds), (st), __VA_ARGS__);                                             \
   } while (0)
 
 // ---- LQ approximation: one workgroup per (instance, node)
 template <bool DERIV>
-__global__ __launch_bounds__(DERIV ? LQ_THREADS : LQV_THREADS, DERIV ? HSQP_LQ_WPE : HSQP_LQV_WPE) void k_lq(const DevModel* __restrict__ dm, const double* __restrict__ x,
+__global__ __launch_bounds__(DERIV ? LQ_THREADS : LQV_THREADS, DERIV ? LQ_WPE : LQV_WPE) void k_lq(const DevModel* __restrict__ dm, const double* __restrict__ x,
                                                    const double* __restrict__ u, const double* __restrict__ par, const double* __restrict__ dts, int N,
                                                    double* __restrict__ rec, double* __restrict__ misc, long long* prof,
                                                    const LsState* __restrict__ ls) {
@@ -136,7 +110,7 @@ __global__ __launch_bounds__(64) void k_params_cent_torso(const DevModel* __rest
 }
 
 // ---- projection: one workgroup per (instance, node)
-__global__ __launch_bounds__(PROJ_THREADS, HSQP_PROJ_WPE) void k_project(const double* __restrict__ rec, const double* __restrict__ dts, double* __restrict__ qp, long long* prof, int cent, int joint_rows, int chain) {
+__global__ __launch_bounds__(PROJ_THREADS, PROJ_WPE) void k_project(const double* __restrict__ rec, const double* __restrict__ dts, double* __restrict__ qp, long long* prof, int cent, int joint_rows, int chain) {
   ProjWS& w = *reinterpret_cast<ProjWS*>(hsqp_smem);
   const Ctx ctx{(int)threadIdx.x, PROJ_THREADS, blockIdx.x == 0 ? prof : nullptr};
   PH_TICK(ctx, 126);  // re-arm the phase clock (bucket 126 is a sink)
@@ -357,7 +331,7 @@ __global__ __launch_bounds__(64) void k_step(const double* __restrict__ qp, cons
 //      under the arithmetic of the other.  One wave per node; the step's scratch aliases the stage workspace (dead until the value
 //      pass starts), the stepped (x, u, x_next) go straight into the value pass's input slots — results are bit-identical to
 //      k_step followed by k_lq<false>.
-__global__ __launch_bounds__(LQV_THREADS, HSQP_LQV_WPE) void k_step_value(const DevModel* __restrict__ dm, const double* __restrict__ qp, const double* __restrict__ ric,
+__global__ __launch_bounds__(LQV_THREADS, LQV_WPE) void k_step_value(const DevModel* __restrict__ dm, const double* __restrict__ qp, const double* __restrict__ ric,
                                                                           const double* __restrict__ dx, const double* __restrict__ x, const double* __restrict__ u,
                                                                           const double* __restrict__ par, const double* __restrict__ dts, int N, double alpha,
                                                                           double* ut, double* __restrict__ du, double* __restrict__ x_new,
@@ -460,19 +434,9 @@ __global__ __launch_bounds__(QV_THREADS * QV_WAVES) __attribute__((amdgpu_waves_
 
 // ---- whole-body LQ approximation on limb lanes (hsqp_lql.h), kernel 1 of 3: the rigid-body model and its Jacobian at the four RK4 stages.  A wave
 //      evaluates QL_NODES nodes, one lane per limb; writes REC_GS (transposed) and REC_AS of the node's record.
-#ifndef HSQP_LQ_SPLIT_DEFAULT
-#define HSQP_LQ_SPLIT_DEFAULT 2   /* node ranges of the limb-lane LQ kernels on streams of their own (hsqp_iterate_device) */
-#endif
-#ifndef HSQP_QL_WAVES
-#define HSQP_QL_WAVES 2          /* waves per workgroup: they share the body constants */
-#endif
-#ifndef HSQP_QL_WPE
-#define HSQP_QL_WPE 1            /* waves per SIMD the register budget is cut for (1: 512 registers per lane) */
-#endif
-#ifndef HSQP_QR_WPE
-#define HSQP_QR_WPE 1
-#endif
-constexpr int QL_WAVES = HSQP_QL_WAVES;
+constexpr int LQ_SPLIT_DEFAULT = 2;   // node ranges of the limb-lane LQ kernels on streams of their own (hsqp_iterate_device)
+constexpr int QL_WAVES = 2;           // waves per workgroup: they share the body constants
+constexpr int QL_WPE = 1, QR_WPE = 1;   // waves per SIMD the register budget of k_lq_limb / k_lq_rows is cut for (1: 512 registers per lane)
 struct QlWS {
   QvConst k;
   struct {
@@ -492,7 +456,7 @@ struct QlWS {
   auto quad_sum = [](double v) { return v; };  \
   auto quad_x1 = quad_sum, quad_x2 = quad_sum, quad_x3 = quad_sum; (void)quad_x1; (void)quad_x2; (void)quad_x3
 #endif
-__global__ __launch_bounds__(QL_THREADS * QL_WAVES) __attribute__((amdgpu_waves_per_eu(HSQP_QL_WPE, HSQP_QL_WPE))) void k_lq_limb(
+__global__ __launch_bounds__(QL_THREADS * QL_WAVES) __attribute__((amdgpu_waves_per_eu(QL_WPE, QL_WPE))) void k_lq_limb(
     const DevModel* __restrict__ dm, const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ dts, int N, int nodes,
     double* __restrict__ rec, long long* prof, int node_base) {   // the launch covers the nodes [node_base, nodes)
   __shared__ QlWS ws;
@@ -602,7 +566,7 @@ struct QrWS {
   } wv[QL_WAVES];
 };
 static_assert(sizeof(QrWS) * (4 / QL_WAVES) <= 163840, "four waves per CU");
-__global__ __launch_bounds__(QL_THREADS * QL_WAVES) __attribute__((amdgpu_waves_per_eu(HSQP_QR_WPE, HSQP_QR_WPE))) void k_lq_rows(
+__global__ __launch_bounds__(QL_THREADS * QL_WAVES) __attribute__((amdgpu_waves_per_eu(QR_WPE, QR_WPE))) void k_lq_rows(
     const DevModel* __restrict__ dm, const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ par, const double* __restrict__ dts,
     int N, int nodes, double* __restrict__ rec, long long* prof, int node_base, int defect) {
   __shared__ QrWS ws;
@@ -669,11 +633,8 @@ __global__ __launch_bounds__(QL_THREADS * QL_WAVES) __attribute__((amdgpu_waves_
 }
 
 // ---- ... kernel 3 of 3: the RK4 chain and the defect: one workgroup per (instance, node), a lane per column of [A|B] (lq_chain_node, hsqp_lql.h)
-#ifndef HSQP_LQC_WPE
-#define HSQP_LQC_WPE 3
-#endif
-constexpr int LQC_THREADS = 128;   // (the 64 defect items must be one wave: lq_chain_node sums their squares with a butterfly)
-__global__ __launch_bounds__(LQC_THREADS, HSQP_LQC_WPE) void k_lq_chain(const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ dts, int N,
+constexpr int LQC_THREADS = 128, LQC_WPE = 3;   // (the 64 defect items must be one wave: lq_chain_node sums their squares with a butterfly)
+__global__ __launch_bounds__(LQC_THREADS, LQC_WPE) void k_lq_chain(const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ dts, int N,
                                                          double* __restrict__ rec, int node_base, int columns) {
   __shared__ LqChainWS w;
   const int node = node_base + blockIdx.x, b = node / N, k = node % N;
@@ -940,6 +901,11 @@ struct hsqp_handle {
   bool backoff_persistent = false;            // hsqp_set_scan_backoff_persistent: uploads of the same (B, N) keep the back-off
   long long backoff_iterations = 0;           // iterations that ran the serial recursion because of the back-off (hsqp_scan_backoffs)
   bool seg_debug = false;                     // HSQP_SEG_DEBUG in the environment at hsqp_create
+  // test aids, from the environment at hsqp_create: HSQP_POISON_LDS (k_poison_lds in front of every launch, HSQP_LAUNCH) and HSQP_POISON_HBM (every device
+  // buffer the handle allocates starts as NaN bit patterns, 0xFF bytes, instead of whatever the allocator returns — usually zeros, which hide a read of
+  // something never written.  Not the LQ record: the limb-lane kernels rely on its zero fill, hsqp_lql.h)
+  bool poison_lds = false, poison_hbm = false;
+  int poison_blocks = 512;                    // workgroups of k_poison_lds: two per CU (set from the device's CU count at hsqp_create)
   bool chain_fused = false;                   // limb-lane form: the RK4 chain of the columns of [A|B] runs inside k_project (project_node, chain), the defect on the lanes of k_lq_rows (ql_defect_lane), k_lq_chain is not launched; HSQP_LQ_CHAIN_SEPARATE in the environment at hsqp_create keeps the chain in k_lq_chain (A/B runs)
   bool lq_limb = false;                       // whole-body LQ approximation on limb lanes (hsqp_lql.h: k_lq_limb + k_lq_rows + k_lq_chain) instead of the phase form k_lq<true> (HSQP_LQ_PHASE_FORM / HSQP_LQ_LIMB_FORM in the environment at hsqp_create force either)
   bool ric_fact = false;                      // whole-body serial sweep on the factors of [A~ | B~] (hsqp_riccati_fact.h: k_riccati_fact; HSQP_RICCATI_DENSE in the environment at hsqp_create: the dense stage k_riccati<58>, for A/B runs)
@@ -971,6 +937,8 @@ struct hsqp_handle {
 
 static std::string g_create_error;
 
+static void poison_hbm(const hsqp_handle* h, void* p, size_t bytes) { if (h->poison_hbm && p) (void)hipMemset(p, 0xFF, bytes); }
+
 #define HCHECK(call)                                                                                   \
   do {                                                                                                 \
     hipError_t e_ = (call);                                                                            \
@@ -986,7 +954,7 @@ static void* stage_area(hsqp_handle* h, size_t bytes) {
     if (h->d_stage) (void)hipFree(h->d_stage);
     h->d_stage = nullptr; h->stage_bytes = 0;
     if (hipMalloc(&h->d_stage, bytes) != hipSuccess) return nullptr;
-    poison_hbm(h->d_stage, bytes);
+    poison_hbm(h, h->d_stage, bytes);
     h->stage_bytes = bytes;
   }
   return h->d_stage;
@@ -1011,7 +979,7 @@ static int launch_scan(hsqp_handle* h, int B, int N, bool want_kkt, int refineme
     h->el_capacity = 0;
     for (auto& p : h->d_el) {
       if (hipMalloc(&p, need * 8) != hipSuccess) { p = nullptr; h->err = "hipMalloc failed (scan elements)"; return HSQP_ERR_OOM; }
-      poison_hbm(p, need * 8);
+      poison_hbm(h, p, need * 8);
     }
     h->el_capacity = need;
   }
@@ -1025,12 +993,12 @@ static int launch_scan(hsqp_handle* h, int B, int N, bool want_kkt, int refineme
     if (!*pv) {
       const size_t bytes = (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8;
       if (hipMalloc(pv, bytes) != hipSuccess) { *pv = nullptr; h->err = "hipMalloc failed (value functions of the scan, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-      poison_hbm(*pv, bytes);
+      poison_hbm(h, *pv, bytes);
     }
   if (!h->d_acl) {
     const size_t bytes = (size_t)h->st.max_batch * h->st.max_nodes * ACL_SIZE<n> * 8;
     if (hipMalloc(&h->d_acl, bytes) != hipSuccess) { h->d_acl = nullptr; h->err = "hipMalloc failed (closed loop of the scan path, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-    poison_hbm(h->d_acl, bytes);
+    poison_hbm(h, h->d_acl, bytes);
   }
   // the gains passes ping-pong between the two value-function buffers; the LAST pass writes d_vf2 (what the KKT check reads) and the closed loop
   double* vbuf[2] = {(refinements & 1) ? h->d_vf : h->d_vf2, (refinements & 1) ? h->d_vf2 : h->d_vf};
@@ -1069,7 +1037,7 @@ static int launch_segmented(hsqp_handle* h, int B, int N, int P, bool want_vf) {
     h->el_capacity = 0;
     for (auto& p : h->d_el) {
       if (hipMalloc(&p, need * 8) != hipSuccess) { p = nullptr; h->err = "hipMalloc failed (segment elements)"; return HSQP_ERR_OOM; }
-      poison_hbm(p, need * 8);
+      poison_hbm(h, p, need * 8);
     }
     h->el_capacity = need;
   }
@@ -1084,13 +1052,13 @@ static int launch_segmented(hsqp_handle* h, int B, int N, int P, bool want_vf) {
     if (h->d_vf0) (void)hipFree(h->d_vf0);
     h->d_vf0 = nullptr; h->vf0_capacity = 0;
     if (hipMalloc(&h->d_vf0, (size_t)B * P * VF_SIZE * 8) != hipSuccess) { h->d_vf0 = nullptr; h->err = "hipMalloc failed (segmented sweep: boundary value functions)"; return HSQP_ERR_OOM; }
-    poison_hbm(h->d_vf0, (size_t)B * P * VF_SIZE * 8);
+    poison_hbm(h, h->d_vf0, (size_t)B * P * VF_SIZE * 8);
     h->vf0_capacity = (size_t)B * P;
   }
   if (!h->d_vf2) {   // (the gate needs the value functions of the boundary stages' nodes; want_vf: of every node, for the KKT report)
     const size_t bytes = (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8;
     if (hipMalloc(&h->d_vf2, bytes) != hipSuccess) { h->d_vf2 = nullptr; h->err = "hipMalloc failed (value functions of the segmented sweep, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-    poison_hbm(h->d_vf2, bytes);
+    poison_hbm(h, h->d_vf2, bytes);
   }
   const int segs = B * P;
   HSQP_LAUNCH(k_seg_elem_ric<n>, dim3(segs), dim3(RIC_THREADS), sizeof(RicWS), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, (const double*)h->d_zero, h->d_ric2,
@@ -1194,6 +1162,8 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
   if (settings->device < 0 || settings->device >= ndev) { g_create_error = "device ordinal out of range"; return HSQP_ERR_BAD_ARG; }
   hsqp_handle* h = new hsqp_handle;
   h->seg_debug = getenv("HSQP_SEG_DEBUG") != nullptr;
+  h->poison_lds = getenv("HSQP_POISON_LDS") != nullptr;
+  h->poison_hbm = getenv("HSQP_POISON_HBM") != nullptr;
   h->ric_fact = model->formulation == HSQP_FORM_WB && getenv("HSQP_RICCATI_DENSE") == nullptr;
   h->md = *model;
   h->st = *settings;
@@ -1205,10 +1175,10 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
   // in ~40 us — so a handle sized for fewer nodes than fill the GPU once (config 3: one instance, 100 nodes) keeps the phase form.  Decided per HANDLE, not
   // per call: every solve of a handle runs the same arithmetic (an instance of a batch equals its solo solve bit for bit)
   h->value_quad = h->hdm.formulation == HSQP_FORM_WB && h->hdm.n_limbs > 0 && getenv("HSQP_VALUE_PHASE_FORM") == nullptr &&
-                  (getenv("HSQP_VALUE_QUAD_FORM") != nullptr || (size_t)settings->max_batch * settings->max_nodes >= HSQP_VALUE_QUAD_MIN_NODES);
+                  (getenv("HSQP_VALUE_QUAD_FORM") != nullptr || (size_t)settings->max_batch * settings->max_nodes >= VALUE_QUAD_MIN_NODES);
   // the LQ approximation on limb lanes (hsqp_lql.h) is a throughput form like the quad value pass; same rule, same per-handle decision
   h->lq_limb = h->hdm.formulation == HSQP_FORM_WB && h->hdm.ql_ok && getenv("HSQP_LQ_PHASE_FORM") == nullptr &&
-               (getenv("HSQP_LQ_LIMB_FORM") != nullptr || (size_t)settings->max_batch * settings->max_nodes >= HSQP_LQ_LIMB_MIN_NODES);
+               (getenv("HSQP_LQ_LIMB_FORM") != nullptr || (size_t)settings->max_batch * settings->max_nodes >= LQ_LIMB_MIN_NODES);
   h->chain_fused = h->lq_limb && getenv("HSQP_LQ_CHAIN_SEPARATE") == nullptr;
   auto fail = [&](int code, const std::string& msg) { g_create_error = msg; hsqp_destroy(h); return code; };
   if (hipSetDevice(h->device) != hipSuccess) return fail(HSQP_ERR_HIP, "hipSetDevice failed");
@@ -1217,7 +1187,7 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
     if (hipEventCreate(&ev) != hipSuccess) return fail(HSQP_ERR_HIP, "hipEventCreate failed");
   if (h->lq_limb) {
     const char* sp = getenv("HSQP_LQ_SPLIT");
-    h->lq_split = HSQP_LQ_SPLIT_DEFAULT;
+    h->lq_split = LQ_SPLIT_DEFAULT;
     if (sp) {
       char* end = nullptr;
       const long v = strtol(sp, &end, 10);
@@ -1226,7 +1196,7 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
       h->lq_split = (int)v;
     }
     // one round of the chip = the workgroups of the two one-wave-per-SIMD kernels it holds at once: asked of the runtime for the kernels as built
-    // (tuning builds change their waves per SIMD: HSQP_QL_WPE / HSQP_QR_WPE), not assumed from the CU count
+    // (QL_WPE / QR_WPE), not assumed from the CU count
     int cus = 0, per_cu_limb = 0, per_cu_rows = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0 &&
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_limb, (const void*)k_lq_limb, QL_THREADS * QL_WAVES, 0) == hipSuccess &&
@@ -1252,10 +1222,9 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
       {(void**)&h->d_kkt, B * 3 * 8 + ((B * sizeof(int) + 7) / 8) * 8}, {(void**)&h->d_dt, B * N * 8}, {(void**)&h->d_perf_before, B * sizeof(hsqp_perf)}, {(void**)&h->d_perf_after, B * sizeof(hsqp_perf)},
       {(void**)&h->d_status, B * sizeof(int)}, {(void**)&h->d_prof, 4 * 128 * sizeof(long long)},
       {(void**)&h->d_stepinfo, B * N * 4 * 8}, {(void**)&h->d_ls, B * sizeof(LsState)}, {(void**)&h->d_counts, 2 * sizeof(int)}};
-  g_poison_hbm = getenv("HSQP_POISON_HBM") != nullptr;
   for (const Alloc& a : allocs) {
     if (hipMalloc(a.p, a.bytes) != hipSuccess) return fail(HSQP_ERR_OOM, "hipMalloc failed (" + std::to_string(a.bytes) + " bytes)");
-    poison_hbm(*a.p, a.bytes);
+    poison_hbm(h, *a.p, a.bytes);
   }
   if (hipHostMalloc((void**)&h->h_gate, B * 3 * 8 + ((B * sizeof(int) + 7) / 8) * 8) != hipSuccess) { h->h_gate = nullptr; return fail(HSQP_ERR_OOM, "hipHostMalloc failed (gate block)"); }
   h->d_ginf = h->d_kkt + 2 * B;   // one block [kkt (2 per instance of max_batch) | |g|_inf | flags of the scan kernels]: one memset, one read-back for the scan's gate
@@ -1266,10 +1235,9 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
   if (hipMemset(h->d_rec, 0, B * N * (size_t)REC_SIZE * 8) != hipSuccess) return fail(HSQP_ERR_HIP, "memset failed");
   // the kernels use up to ~158 KB of dynamic LDS (gfx950: 160 KB per workgroup)
   hipError_t a1 = hipFuncSetAttribute((const void*)k_lq<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LqWS));
-  g_poison_lds = getenv("HSQP_POISON_LDS") != nullptr;
-  if (g_poison_lds) {
+  if (h->poison_lds) {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) g_poison_blocks = 2 * prop.multiProcessorCount;
+    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) h->poison_blocks = 2 * prop.multiProcessorCount;
     if (a1 == hipSuccess) a1 = hipFuncSetAttribute((const void*)k_poison_lds, hipFuncAttributeMaxDynamicSharedMemorySize, POISON_LDS_BYTES);
   }
   hipError_t a2 = hipFuncSetAttribute((const void*)k_lq<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LqWST<false>));
@@ -1521,7 +1489,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     if (want_kkt && !h->d_vf) {
       const size_t bytes = (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8;
       if (hipMalloc(&h->d_vf, bytes) != hipSuccess) { h->d_vf = nullptr; h->err = "hipMalloc failed (value function for the KKT check, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-      poison_hbm(h->d_vf, bytes);
+      poison_hbm(h, h->d_vf, bytes);
     }
     const int Bm = h->st.max_batch;
     const size_t gate_bytes = (size_t)Bm * 3 * 8 + (((size_t)Bm * sizeof(int) + 7) / 8) * 8;   // [kkt | |g|_inf | scan flags]

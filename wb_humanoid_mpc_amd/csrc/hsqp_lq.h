@@ -26,27 +26,23 @@ constexpr int REC_CDE = REC_GD + LDJ;             // [NE_MAX][LDJ] rows [C|D|e]
 constexpr int CDE_ROWS = 16;                      //              rows the equality block is allocated for (its transposed form keeps 16 per column)
 constexpr int REC_MISC = REC_CDE + CDE_ROWS * LDJ;  // [16] ne, cost (x dt), eq_sse (x dt), dyn_sse (x dt), contact flags (2), first equality row of each foot (2), [8] = NROWS, [9] = LAYOUT
 constexpr int REC_NROWS = REC_MISC + 8;           //      residual rows in use (compact layout, hsqp_node.h); the rows up to the end of their 24-row pass are zero
-constexpr int REC_LAYOUT = REC_MISC + 9;          //      0: REC_J [row][LDJ], REC_CDE [row][LDJ] (phase form, centroidal); 1: transposed, REC_J [column][NRS] with the row slots of
-                                                  //      hsqp_lql.h (ROWQ_*), REC_CDE [column][CDE_ROWS] — written column by column by the limb lanes
+constexpr int REC_LAYOUT = REC_MISC + 9;          //      0: REC_J [row][LDJ], REC_CDE [row][LDJ] (phase form, centroidal); 1: transposed, REC_J [column][NRS] with the row slots
+                                                  //      ROWQ_* below, REC_CDE [column][CDE_ROWS] — written column by column by the limb lanes (hsqp_lql.h)
 constexpr int REC_FLOW = REC_MISC + 16;           // [64] xdot at (x,u)
 constexpr int REC_GS = REC_FLOW + 64;             // [4][6][LDJ] stage Jacobians d a_b/dz (scratch of the LQ kernel; limb-lane form: transposed, [4][LDJ][6])
 constexpr int REC_AS = REC_GS + 4 * 6 * LDJ;      // [4][6]      base accelerations of the RK4 stages (limb-lane form: from the model kernel to the chain kernel)
 constexpr int REC_SIZE = REC_AS + 24;
 static_assert(REC_J % 2 == 0 && REC_CDE % 2 == 0 && REC_GS % 2 == 0 && REC_SIZE % 2 == 0, "16-byte aligned pieces");
+// the residual row slots of the transposed layout (REC_LAYOUT = 1):
+constexpr int ROWQ_FOOT = 0;    // + 16 f: the 15 task-space rows of foot f (ori, vlin, vang, alin, aang) and one zero row
+constexpr int ROWQ_FM = 32;     // + 8 f : friction cone (4) and contact moment (4) rows of foot f — zero while the foot is in the air
+constexpr int ROWQ_COLL = 48;   // the 16 foot-collision rows, in use (REC_NROWS = 64) only while one of them is active
+static_assert(ROWQ_COLL + 16 == NRS && ROWQ_FM + 16 == ROWQ_COLL, "row slots");
 
-// Model constants: read from global memory through the vector L1 (every workgroup of a CU reads the same 9 KB), or,
-// with -DHSQP_DM_LDS=1, from a per-workgroup LDS copy (costs 9 KB of LDS = one workgroup of occupancy per CU).
-#ifndef HSQP_DM_LDS
-#define HSQP_DM_LDS 0
-#endif
-struct NoDevModelCopy {};
+// Model constants are read from global memory through the vector L1 (every workgroup of a CU reads the same 9 KB).
 template <bool D>
 struct LqWST {
-#if HSQP_DM_LDS
-  DevModel dml;
-#else
-  NoDevModelCopy dml;
-#endif
+  double lead_pad;     // unused: keeps st at offset 8 — without it every LDS offset of k_lq and k_step_value moves by 8 bytes, and their code with it
   StageWST<D> st;
   double blk[D ? 3 : 1][2][6][6];   // RK4 chain: the blocks G_s[:, v_b] and G_s[:, q_b] of stages 2..4 (everything else of the chain lives in registers)
   NodeWST<D> nw;
@@ -174,20 +170,8 @@ HSQP_HD void lq_chain_column(const double (*blk)[2][6][6], const double* gs, int
 // PRELOADED: w.nw.x, w.nw.u and w.xnext already hold the node's (x, u, x_next) — the fused step + value kernel writes the stepped
 // values there — and x / u / xnext are not read.
 template <bool DERIV, bool PRELOADED = false>
-HSQP_HD void lq_node(const Ctx& ctx, const DevModel& dm_global, LqWST<DERIV>& w, const double* x, const double* u, const double* xnext,
+HSQP_HD void lq_node(const Ctx& ctx, const DevModel& dm, LqWST<DERIV>& w, const double* x, const double* u, const double* xnext,
                      const double* par, double dt, double* rec, double* misc) {
-#if HSQP_DM_LDS
-  {
-    constexpr int nw = (int)(sizeof(DevModel) / sizeof(double));
-    static_assert(sizeof(DevModel) % sizeof(double) == 0, "DevModel must be a whole number of doubles");
-    const double* src = reinterpret_cast<const double*>(&dm_global);
-    double* dst = reinterpret_cast<double*>(&w.dml);
-    WG_FOR(ctx, i, nw) dst[i] = src[i];
-  }
-  const DevModel& dm = w.dml;
-#else
-  const DevModel& dm = dm_global;
-#endif
   stage_topology(ctx, dm, w.st, /*sync*/ false);   // one phase with the node's inputs: the two global round trips overlap
   WG_FOR(ctx, i, NX + NU + NP + NX) {
     if (i < NX) { if (!PRELOADED) w.nw.x[i] = x[i]; }
@@ -272,9 +256,7 @@ HSQP_HD void lq_node(const Ctx& ctx, const DevModel& dm_global, LqWST<DERIV>& w,
   // selection structure), so one item per column runs the whole chain in registers and writes its column of P6, V6: one phase
   // (round 2: LDS copies of all four G_s, a direct-part phase and a matrix-core job per stage — eight barriers, 22 k cycles).
   WG_SYNC(ctx);
-#ifndef HSQP_NO_CHAIN
   WG_FOR(ctx, col, LDJ) lq_chain_column(w.blk, rec + REC_GS, col, dt, rec);
-#endif
   PH_TICK(ctx, 8);
   }
 }

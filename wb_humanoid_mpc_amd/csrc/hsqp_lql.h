@@ -418,21 +418,11 @@ HSQP_HD int ql_foot_step(const DevModel& dm, int L) { return dm.limb_foot_step[L
 // node (as hsqp_lqv.h does for the value pass), and the residual / equality ROWS of every column formed by the lane that owns the column, at the
 // moment its stage-1 Jacobian column exists — the joint's motion axis, the body state and the composite are in registers then.  The record's
 // rows are stored TRANSPOSED (REC_LAYOUT = 1): REC_J [column][NRS], REC_CDE [column][CDE_ROWS], so that a lane writes contiguous, 16-byte
-// aligned pieces; the row slots are fixed:
-constexpr int ROWQ_FOOT = 0;    // + 16 f: the 15 task-space rows of foot f (ori, vlin, vang, alin, aang) and one zero row
-constexpr int ROWQ_FM = 32;     // + 8 f : friction cone (4) and contact moment (4) rows of foot f — zero while the foot is in the air
-constexpr int ROWQ_COLL = 48;   // the 16 foot-collision rows, in use (REC_NROWS = 64) only while one of them is active
-static_assert(ROWQ_COLL + 16 == NRS && ROWQ_FM + 16 == ROWQ_COLL, "row slots");
+// aligned pieces; the row slots are fixed (ROWQ_*, hsqp_lq.h).
 // Entries that are zero for every state (a column that can never move a row: an arm joint and the friction rows, ...) are never written: the
 // record is zero-filled when it is allocated (hsqp_create) and only this kernel writes these regions.
 
-#ifndef HSQP_QL_MERGED_STORES
-#define HSQP_QL_MERGED_STORES 1   /* ql_put_foot: full and half blocks stored by the same wave instructions (0: one branch each; A/B builds) */
-#endif
 HSQP_HD void ql_st2(double* p, double a, double b) {
-#if defined(HSQP_EXP_FEWSTORES)   /* timing experiment only (wrong results): one store in eight reaches memory */
-  if ((reinterpret_cast<unsigned long long>(p) >> 4) & 7ull) return;
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
   *reinterpret_cast<double2*>(p) = make_double2(a, b);
 #else
@@ -727,24 +717,11 @@ HSQP_HD void ql_put_foot(const DevModel& dm, const QlRows& rw, int f, bool full,
     double* jt = rec + REC_J + col * NRS + ROWQ_FOOT + 16 * f;
     const double sc = rw.imp[f];
     const double* w = dm.foot_sqrt_w + 3;
-#if HSQP_QL_MERGED_STORES
     // ONE store instruction per row pair for the lanes that write the whole block and those that write its acceleration half (rows 8 .. 15; their out[11] is zero):
     // the two groups used to run their stores one after the other, twelve wave instructions per foot and column instead of eight
 #pragma unroll
     for (int k = 0; k < 16; k += 2)
       if (!((zpairs >> (k / 2)) & 1u) || k >= 8) { if (full || k >= 8) ql_st2(jt + k, sc * w[k] * out[3 + k], k < 14 ? sc * w[k + 1] * out[4 + k] : 0.0); }
-#else
-    if (full) {
-#pragma unroll
-      for (int k = 0; k < 14; k += 2) if (!((zpairs >> (k / 2)) & 1u)) ql_st2(jt + k, sc * w[k] * out[3 + k], sc * w[k + 1] * out[4 + k]);
-      ql_st2(jt + 14, sc * w[14] * out[17], 0.0);
-    } else {
-      ql_st2(jt + 8, 0.0, sc * w[9] * out[12]);
-      ql_st2(jt + 10, sc * w[10] * out[13], sc * w[11] * out[14]);
-      ql_st2(jt + 12, sc * w[12] * out[15], sc * w[13] * out[16]);
-      ql_st2(jt + 14, sc * w[14] * out[17], 0.0);
-    }
-#endif
   }
   const int cf = f == 0 ? rw.c0 : rw.c1;
   if (cf) {
@@ -1021,13 +998,8 @@ HSQP_HD int ql_rows_column(const QlLimb& lb, int t, int kind) {
   return kind == 0 ? 3 + i + 2 : (kind == 1 ? NV + 3 + i + 2 : NX + 12 + j);
 }
 HSQP_HD void ql_rows_fetch(const double* gs, int col, double* g) {
-#if defined(HSQP_EXP_NOFETCH)   /* timing experiment only (wrong results): no stage-Jacobian column fetch, hence no wait behind the row stores */
-#pragma unroll
-  for (int k = 0; k < 6; ++k) g[k] = 1e-3 * (col + k);
-#else
 #pragma unroll
   for (int k = 0; k < 6; ++k) g[k] = gs[col * GT_LD + k];
-#endif
 }
 // one step of the rows pass: the rows of the three columns of joint i = path[t], then up to the parent.  pend: the stage Jacobian columns of
 // (t, kinds 0 .. 2) on entry, of step t - 1 on exit.

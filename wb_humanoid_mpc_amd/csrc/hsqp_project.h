@@ -11,9 +11,6 @@
 #include <cstddef>
 #include <vector>
 #include "hsqp_linalg.h"
-#ifndef HSQP_PEXP
-#define HSQP_PEXP 0   /* timing experiments of tuning builds (WRONG results): bit 0 no Px / Pu / Pe and b~ stores, 1 no Gram store, 2 no second pass, 3 no QR, 4 no dense-row jobs, 5 no weight rows, 6 no first pass */
-#endif
 #include "hsqp_lq.h"
 
 namespace hsqp {
@@ -34,14 +31,9 @@ constexpr int QP_NUT = QP_PE + NU;             // [1]  nu - ne, or -1 if D was r
 constexpr int QP_SIZE = ((QP_NUT + 1 + 7) / 8) * 8;
 
 constexpr int NTW = NX + NUT;                  // 81: projected stage variable [dx; ut]
-#ifndef HSQP_LDTM
-#define HSQP_LDTM 82    /* (88 until the end of round 6: row groups of a tile read 48 banks apart overlap in 16 banks; 82: in 4.  k_project 1.410 -> 1.397 ms) */
-#endif
-#ifndef HSQP_LDP
-#define HSQP_LDP 98     /* leading dimension of PV in LDS (the record's is LDJ = 96: sixteen lanes LDJ apart are ONE bank) */
-#endif
-constexpr int LDP = HSQP_LDP;
-constexpr int LDTM = HSQP_LDTM;                // leading dimension of Tm = [Px | Pu | Pe | pad] and of the residual rows (>= NTW + 1; tuning builds: -DHSQP_LDTM)
+constexpr int LDP = 98;                        // leading dimension of PV in LDS (the record's is LDJ = 96: sixteen lanes LDJ apart are ONE bank)
+constexpr int LDTM = 82;                       // leading dimension of Tm = [Px | Pu | Pe | pad] and of the residual rows (>= NTW + 1).  (88 until the end of
+                                               // round 6: row groups of a tile read 48 banks apart overlap in 16 banks; 82: in 4.  k_project 1.410 -> 1.397 ms)
 // The 64 residual row slots are projected in passes of NRP rows (24 + 24 + 16) through one small LDS block; the projected
 // Gauss-Newton Hessian J~^T J~ is accumulated ACROSS the passes in registers (the matrix-core accumulators of the 15 tiles on /
 // above the diagonal of its leading 80 x 80 block, dealt to the four waves; the last projected input and the gradient column
@@ -68,17 +60,11 @@ struct ProjWS {
       double Jt[NRP][LDTM];      // the projected residual rows of the current pass (column 81 = rho')
       double JuT[NU + 1][NRP];   // transposed input block of the residual rows of the current (next) pass (row NU: their rho); overlaps Wm
     } ps;
-#if defined(HSQP_PEXP_ALIAS)   /* timing experiment only (WRONG results): T over the first union — 28.5 KB, four to five workgroups per CU (profiles/r06_project_experiments.txt (3)) */
-    double Tm[NU + 1][LDTM];
-    double CDe[NE_MAX][LDJ];
-  };
-#else
   };
   union {
     double Tm[NU + 1][LDTM];     // [Px (58) | Pu (23) | Pe | 0 ...]; row NU = e_NTW: with rho as row NU of JuT the product J_u [Pu | Pe] also adds rho to its last column
     double CDe[NE_MAX][LDJ];     // the equality rows, until W = R1^-T [C|e] is formed (Tm is written after that)
   };
-#endif
   int ne, nut, ok;
   int jt;                        // the record's residual / equality rows are stored transposed (REC_LAYOUT)
   int nrows;                     // residual rows of the record in use (REC_NROWS); the third pass is skipped when they fit two
@@ -95,18 +81,9 @@ struct ProjWS {
 static_assert(LDP >= LDJ && sizeof(double) * 2 * 6 * LDP <= offsetof(ProjWS, qr.Q1T), "PV may only overlap what is dead while Tm is formed");
 static_assert(sizeof(ProjWS) <= 163840 / 3 - 256, "three workgroups per CU");
 // fused RK4 chain (project_node, chain = true): the chain's threads — waves 2, 3 minus their last 32 lanes; wave 0 runs the factorisation meanwhile.  The 216 entries of the
-// 6 x 6 blocks have wave-uniform addresses and come through the scalar cache; the A/B form (HSQP_PROJ_CHAIN_BLK_LDS) stages them in rows of Tm that lie behind the equality
-// rows (CDe) and are first written when Q2^T goes into Tm, two phases after the chain
-#ifndef HSQP_PROJ_CHAIN_BLK_LDS
-#define HSQP_PROJ_CHAIN_BLK_LDS 0   /* 1: the chain's 6 x 6 blocks staged in LDS (rows of Tm) instead of read through the scalar cache (A/B builds) */
-#endif
-#ifndef HSQP_PROJ_CHAIN_T0
-#define HSQP_PROJ_CHAIN_T0 128   /* first thread of the fused chain (tuning builds: 64 = waves 1, 2) */
-#endif
-constexpr int PROJ_CHAIN_T0 = HSQP_PROJ_CHAIN_T0, PROJ_CHAIN_ROW = 24;
+// 6 x 6 blocks have wave-uniform addresses and come through the scalar cache (staged in LDS they were 0.02 ms slower: profiles/r06_project_experiments.txt (5))
+constexpr int PROJ_CHAIN_T0 = 128;             // first thread of the fused chain (64 / 96 / 160 were no faster: profiles/r06_project_experiments.txt (5))
 static_assert(PROJ_CHAIN_T0 >= 64 && PROJ_CHAIN_T0 + LDJ <= 256, "the chain's threads: not wave 0 (the factorisation), inside the workgroup");
-static_assert(PROJ_CHAIN_ROW * LDTM >= NE_MAX * LDJ && PROJ_CHAIN_ROW * LDTM + 3 * 72 <= NU * LDTM, "the chain's blocks must not touch the equality rows or row NU of Tm");
-HSQP_HD double* proj_chain_blk(ProjWS& w) { return &w.Tm[PROJ_CHAIN_ROW][0]; }
 
 // Event interval (hsqp_problem::dt_nodes[b][k] == 0): the stage of the QP is the identity jump map
 // dx+ = dx + (x_k - x_{k+1}) with no cost and the inputs pinned (R~ = I, everything else zero -> ut = 0, du = 0).  b~ is the defect
@@ -295,13 +272,6 @@ HSQP_HD void project_node(const Ctx& ctx, ProjWS& w, const double* rec, double d
     // structure of the equality rows (closed forms, one item per input / row): a swing foot f contributes the unit rows
     // off[f] .. off[f]+5 on the inputs 6f .. 6f+5
     WG_FOR(ctx, i, LDTM) w.Tm[NU][i] = i == NTW ? 1.0 : 0.0;   // (beyond the equality rows that share the block until Tm is formed)
-#if defined(__HIP_DEVICE_COMPILE__)
-    // (A/B form only) the 6 x 6 blocks G_s[:, v_b], G_s[:, q_b] of stages 2 .. 4 that every column's chain multiplies with: in rows of Tm nobody touches before the W phase is over
-    if (chain && HSQP_PROJ_CHAIN_BLK_LDS) WG_FOR(ctx, i, 3 * 72) {
-      const int sg = i / 72, which = (i / 36) % 2, r = (i / 6) % 6, k = i % 6;
-      proj_chain_blk(w)[i] = rec[REC_GS + lq_chain_blk_offset(sg, which, r, k)];
-    }
-#endif
     WG_FOR(ctx, i, NU + NE_MAX + 1) {
       const int ne_ = (int)m_ne;
       const int sw0 = m_c0 == 0.0 ? 1 : 0, sw1 = m_c1 == 0.0 ? 1 : 0;
@@ -365,8 +335,8 @@ HSQP_HD void project_node(const Ctx& ctx, ProjWS& w, const double* rec, double d
   // (which the host build runs), summation order aside.
   double chP[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, chV[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // chain: column tid - PROJ_CHAIN_T0 of P6, V6 (threads PROJ_CHAIN_T0 .. + LDJ - 1), held until store_pv
   if (chain && ctx.tid >= PROJ_CHAIN_T0 && ctx.tid < PROJ_CHAIN_T0 + LDJ)
-    lq_chain_column_pv<true, !HSQP_PROJ_CHAIN_BLK_LDS>(reinterpret_cast<const double (*)[2][6][6]>(proj_chain_blk(w)), rec + REC_GS, ctx.tid - PROJ_CHAIN_T0, dt, chP, chV);
-  if (ctx.tid < 64 && !(HSQP_PEXP & 8)) {
+    lq_chain_column_pv<true, true>(nullptr, rec + REC_GS, ctx.tid - PROJ_CHAIN_T0, dt, chP, chV);
+  if (ctx.tid < 64) {
     const int lane = ctx.tid, g = lane >> 4, c = lane & 15;
     constexpr int NT9 = (NU + 1) / 4;
     static_assert(NT9 * 4 == NU + 1 && LDR == 16, "four row groups of nine rows, one column per lane of a DPP row");
@@ -652,12 +622,11 @@ HSQP_HD void project_node(const Ctx& ctx, ProjWS& w, const double* rec, double d
     ja.sx1 = LDP; jb.sx1 = LDP;
     ja.rsplit = 6; ja.rjump = r1 - 6; jb.rsplit = 6; jb.rjump = r1 - 6;
     const XtyJob jobs[2] = {ja, jb};
-    if (!(HSQP_PEXP & 16)) wg_xty_jobs<true, XTY_C_GLOBAL | XTY_ROW_JUMP>(ctx, jobs, 2);
+    wg_xty_jobs<true, XTY_C_GLOBAL | XTY_ROW_JUMP>(ctx, jobs, 2);
   }
   constexpr int NCG = 3;   // row groups per column
   constexpr int NCI = NCG * (NTW + 1), NBI = 256 - NCI;   // column items; the items left of one 256-thread round share the twelve b~ rows
   static_assert(NBI >= 1 && NBI <= 12, "one round of the 256-thread workgroup (a second round would be wave 0's alone)");
-  if (!(HSQP_PEXP & 1))
   WG_FOR(ctx, it, 256) {
     if (it >= NCI) {   // b~ of the dense rows
       for (int i = it - NCI; i < 12; i += NBI) {
@@ -708,7 +677,7 @@ HSQP_HD void project_node(const Ctx& ctx, ProjWS& w, const double* rec, double d
   //      accumulators while the input block of the next pass is fetched
   GramAcc g;
   gram_init(ctx, g);
-  // In the limb-lane layout the row slots are fixed (hsqp_lql.h: ROWQ_FOOT + 16 f: ori, vlin, vang, alin, aang, one zero row; ROWQ_FM + 8 f: friction cone and
+  // In the limb-lane layout the row slots are fixed (hsqp_lq.h: ROWQ_FOOT + 16 f: ori, vlin, vang, alin, aang, one zero row; ROWQ_FM + 8 f: friction cone and
   // contact moment of foot f; ROWQ_COLL: collision), and most of the INPUT block of J is zero for every state: only the six acceleration rows of a foot
   // depend on all inputs, a foot's friction / moment rows on its own wrench (inputs 6 f .. 6 f + 5), nothing else on any input.  So the rows of a pass
   // beyond its first 16-row tile need no product with [Px | Pu | Pe] at all (pass 0: rows 16 .. 23 = orientation / velocities of foot 1; pass 2: the
@@ -744,22 +713,23 @@ HSQP_HD void project_node(const Ctx& ctx, ProjWS& w, const double* rec, double d
       wg_xty_jobs<true, XTY_ADD_GLOBAL | XTY_ADD_T>(ctx, jobs, 2);
     }
   };
-  if (!(HSQP_PEXP & 64)) project_rows(0, NRP, 16, 0, 0);
+  static_assert(ROWQ_FOOT == 0 && ROWQ_FM == 2 * 16 && ROWQ_COLL == 2 * NRP && NRP == 24, "the heads (16) and tails (inputs 6 .. 11) of the passes below follow the row slots");
+  project_rows(0, NRP, 16, 0, 0);
   WG_SYNC(ctx);
   PH_TICK(ctx, 6);
   load_ju(NRP, NRP);
-  if (!(HSQP_PEXP & 64)) gram_rows<false, NRP>(ctx, g, &w.ps.Jt[0][0], LDTM, nullptr, nullptr);
+  gram_rows<false, NRP>(ctx, g, &w.ps.Jt[0][0], LDTM, nullptr, nullptr);
   store_ju(NRP, NRP);
   WG_SYNC(ctx);
   PH_TICK(ctx, 14);
-  if (!(HSQP_PEXP & 4)) project_rows(NRP, NRP, 16, 6, 6);
+  project_rows(NRP, NRP, 16, 6, 6);
   WG_SYNC(ctx);
   PH_TICK(ctx, 11);
   // the third pass only if rows beyond the first two passes are in use (the whole-body LQ kernel writes its rows compactly: 46 in
   // double support, 38 in single support; the collision rows, which would make it 54 / 62, are absent unless one of them is active)
   const bool pass3 = w.nrows > 2 * NRP;
   if (pass3) load_ju(2 * NRP, NRS - 2 * NRP);
-  if (!(HSQP_PEXP & 4)) gram_rows<false, NRP>(ctx, g, &w.ps.Jt[0][0], LDTM, nullptr, nullptr);
+  gram_rows<false, NRP>(ctx, g, &w.ps.Jt[0][0], LDTM, nullptr, nullptr);
   if (pass3) {
     store_ju(2 * NRP, NRS - 2 * NRP);
     WG_SYNC(ctx);
@@ -770,9 +740,9 @@ HSQP_HD void project_node(const Ctx& ctx, ProjWS& w, const double* rec, double d
     gram_rows<false, NRS - 2 * NRP>(ctx, g, &w.ps.Jt[0][0], LDTM, nullptr, nullptr);
   }
   // the input-weight rows sqrt(d_u) [Px | Pu | Pe] and the diagonal part of the gradient, straight from Tm
-  if (!(HSQP_PEXP & 32)) gram_rows<true, NU>(ctx, g, &w.Tm[0][0], LDTM, &w.d[NX], &w.gd[NX]);
+  gram_rows<true, NU>(ctx, g, &w.Tm[0][0], LDTM, &w.d[NX], &w.gd[NX]);
   PH_TICK(ctx, 12);
-  if (!(HSQP_PEXP & 2)) gram_store(ctx, g, w, nut, qp, joint_rows);
+  gram_store(ctx, g, w, nut, qp, joint_rows);
   WG_SYNC(ctx);
   PH_TICK(ctx, 10);
 }

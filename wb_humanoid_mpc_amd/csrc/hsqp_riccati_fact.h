@@ -16,7 +16,7 @@
 //   Ph1  S B~ = (F^T S)^T Vu  (8 tiles x 9 steps: waves 0 .. 3 run both column tiles of their row tile in one call, the A operand formed once; the
 //        combinations F^T S are KEPT: FS),  sb = s + S b~  (vector items: all that waves 4 .. 7 do in the phase)
 //   Ph2  G = P~ + SB^T E_J + (F^T SB)^T Vx  (8 tiles),  [Lam | g] = [R~ | r~] + Vu^T (F^T [SB | sb])  (4 tiles, second tile of waves 4 .. 7's call);
-//        P~, R~, r~ from LDS: no global load in the phase.  Waves 0 .. 3, one tile short of the others, form the first row tile of S A~ (HSQP_SA_EARLY)
+//        P~, R~, r~ from LDS: no global load in the phase.  Waves 0 .. 3, one tile short of the others, form the first row tile of S A~
 //   Ph3  waves 0, 1: blocked elimination of [Lam | I | G | g] (hsqp_elim.h, unchanged); wave 0's hook issues every asynchronous copy of the next
 //        stage (Vx, P~, R~) and both fetch Q~ of their S tiles into registers  ||  waves 2, 3, 6, 7: the other three row tiles of S A~, then W' — whose
 //        last column tile carries sb as column NX of S A~ and leaves A~^T sb there  ||  waves 4, 5: the next stage's Vu, b~, r~ through address
@@ -31,24 +31,10 @@
 #pragma once
 #include <cstddef>
 #include "hsqp_riccati.h"
-#ifndef HSQP_LAP_WAVE
-#define HSQP_LAP_WAVE 4   /* -DHSQP_PHASE_PROFILE builds: the wave whose Ph4 is split into laps (slots 20 .. 25) */
-#endif
-#ifndef HSQP_EXP
-#ifndef HSQP_FACT_PF
-#define HSQP_FACT_PF RIC_PF   /* operand prefetch depth of this stage's tile loops (tuning builds) */
-#endif
-#ifndef HSQP_PH1_NT2
-#define HSQP_PH1_NT2 1    /* Ph1: the two column tiles of a row tile of S B~ in one call on waves 0 .. 3 (0: one tile per wave; A/B builds) */
-#endif
-#ifndef HSQP_SA_EARLY
-#define HSQP_SA_EARLY 1   /* the first row tile of SA on waves 0 .. 3 in Ph2 (0: all of SA in Ph3; A/B builds) */
-#endif
-#define HSQP_EXP 0   /* timing experiments of tuning builds (WRONG results): bit 0 memory waves without trailing copies / Q~, 1 no Vx copy, 2 memory waves idle, 3 no W' tiles, 4 no hook; (correct results:) 5 no s_setprio */
-#endif
 
 namespace hsqp {
-constexpr int FACT_PF = HSQP_FACT_PF;
+constexpr int FACT_PF = RIC_PF;               // operand prefetch depth of this stage's tile loops
+constexpr int LAP_WAVE = 4;                   // -DHSQP_PHASE_PROFILE builds: the wave whose Ph4 is split into laps (slots 20 .. 25)
 
 constexpr int NF = 12 + NJ;                   // rank of the factored part
 constexpr int NFS = (NF + 3) / 4;             // contraction steps of four (index 35 is padding)
@@ -326,7 +312,7 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
   for (int k = N - 1; k >= 0; --k) {
     // (the thread index is made opaque once per stage: see riccati_backward)
     Ctx ctx = ctx_outer;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(HSQP_FACT_NO_OPAQUE)
+#if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(ctx.tid));
 #endif
     const double* q = qp + (size_t)k * QP_SIZE;
@@ -340,7 +326,7 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
     PH_MARK(ctx);
 #if defined(__HIP_DEVICE_COMPILE__)
     const int wv = wave_index(ctx.tid), lane = ctx.tid & 63, li = lane & 15, kk = lane >> 4;
-    // ---- Ph1: SB = (F^T S)^T Vu — one tile per wave; the waves of the first column tile also keep the combinations they fetch (FS);
+    // ---- Ph1: SB = (F^T S)^T Vu — a row tile per wave of waves 0 .. 3, which also keep the combinations they fetch (FS);
     //      the helper half first: sb = s + S b~ (four partial sums per row, closed by DPP quad permutes), k of the previous stage -> record
     {
       // (ONE wave per SIMD carries the vector items, all 64 lanes: a SIMD runs the vector instructions of its two waves one after the other, so what a
@@ -360,48 +346,28 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
           if (p == 0) { w.sb[r] = sacc; w.SB[r][NUT] = sacc; w.SA[r][NX] = sacc; }
         } else if (it < 4 * NX + NUT && k < N - 1) ric[(size_t)(k + 1) * RIC_SIZE + RIC_KV + it - 4 * NX] = w.PG[it - 4 * NX][FG_GV];
       }
-      if (HSQP_PH1_NT2) {
-        // waves 0 .. 3: BOTH column tiles of row tile wv in one call — the A operand (a combination of rows of S: two or three LDS reads and two
-        // multiply-adds per element) is formed once for the two tiles instead of once per tile on two waves of the same SIMD
-        if (wv < 4) {
-          const int r0 = wv << 4, xr = r0 + li < NX ? r0 + li : NX - 1;
-          hsqp_d4 acc[2] = {hsqp_d4{0.0, 0.0, 0.0, 0.0}, hsqp_d4{0.0, 0.0, 0.0, 0.0}};
-          auto xf = [&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            double v = fact_combo(sc, kk, &w.S[0][0], NX, xr, dt, hq);
-            if (4 * s + 3 >= NF) v = 4 * s + kk < NF ? v : 0.0;
-            if (r0 + li < NX && 4 * s + kk < NF) w.FS[4 * s + kk][xr] = v;
-            return v;
-          };
-          auto yf = [&](auto sc, int t) { constexpr int s = decltype(sc)::value; const int kc = 4 * s + kk < NF ? 4 * s + kk : NF - 1; return w.VB[kc][16 * t + li < LDB ? 16 * t + li : LDB - 1]; };
-          fact_mfma_sx<2, FACT_PF, NFS>(acc, xf, yf);
+      // waves 0 .. 3: BOTH column tiles of row tile wv in one call — the A operand (a combination of rows of S: two or three LDS reads and two
+      // multiply-adds per element) is formed once for the two tiles instead of once per tile on two waves of the same SIMD
+      if (wv < 4) {
+        const int r0 = wv << 4, xr = r0 + li < NX ? r0 + li : NX - 1;
+        hsqp_d4 acc[2] = {hsqp_d4{0.0, 0.0, 0.0, 0.0}, hsqp_d4{0.0, 0.0, 0.0, 0.0}};
+        auto xf = [&](auto sc) {
+          constexpr int s = decltype(sc)::value;
+          double v = fact_combo(sc, kk, &w.S[0][0], NX, xr, dt, hq);
+          if (4 * s + 3 >= NF) v = 4 * s + kk < NF ? v : 0.0;
+          if (r0 + li < NX && 4 * s + kk < NF) w.FS[4 * s + kk][xr] = v;
+          return v;
+        };
+        auto yf = [&](auto sc, int t) { constexpr int s = decltype(sc)::value; const int kc = 4 * s + kk < NF ? 4 * s + kk : NF - 1; return w.VB[kc][16 * t + li < LDB ? 16 * t + li : LDB - 1]; };
+        fact_mfma_sx<2, FACT_PF, NFS>(acc, xf, yf);
 #pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const int col = 16 * t + li;
-            if (col < NUT) {
+        for (int t = 0; t < 2; ++t) {
+          const int col = 16 * t + li;
+          if (col < NUT) {
 #pragma unroll
-              for (int r = 0; r < 4; ++r) { const int row = r0 + kk + 4 * r; if (row < NX) w.SB[row][col] = acc[t][r]; }
-            }
+            for (int r = 0; r < 4; ++r) { const int row = r0 + kk + 4 * r; if (row < NX) w.SB[row][col] = acc[t][r]; }
           }
         }
-      } else {
-      const int rt = wv & 3, ct = wv >> 2, r0 = rt << 4, c0 = ct << 4;
-      const int xr = r0 + li < NX ? r0 + li : NX - 1, yc = c0 + li < LDB ? c0 + li : LDB - 1;
-      hsqp_d4 acc[1] = {hsqp_d4{0.0, 0.0, 0.0, 0.0}};
-      auto xf = [&](auto sc, int) {
-        constexpr int s = decltype(sc)::value;
-        double v = fact_combo(sc, kk, &w.S[0][0], NX, xr, dt, hq);
-        if (4 * s + 3 >= NF) v = 4 * s + kk < NF ? v : 0.0;
-        if (ct == 0 && r0 + li < NX && 4 * s + kk < NF) w.FS[4 * s + kk][xr] = v;
-        return v;
-      };
-      auto yf = [&](auto sc, int) { constexpr int s = decltype(sc)::value; const int kc = 4 * s + kk < NF ? 4 * s + kk : NF - 1; return w.VB[kc][yc]; };
-      fact_mfma<1, FACT_PF, NFS>(acc, xf, yf);
-      const int col = c0 + li;
-      if (col < NUT) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const int row = r0 + kk + 4 * r; if (row < NX) w.SB[row][col] = acc[0][r]; }
-      }
       }
     }
 #else
@@ -508,7 +474,7 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
       }
       // waves 0 .. 3 have one tile in this phase, waves 4 .. 7 two: the first row tile of SA's column tile wv (S, FS, Vx: all there since Ph1) moves
       // from Ph3 — whose tile waves are 2 k cycles behind the elimination — into the difference
-      else if (HSQP_SA_EARLY) sa_tiles(std::integral_constant<int, 1>{}, 0, wv);
+      else sa_tiles(std::integral_constant<int, 1>{}, 0, wv);
     }
 #else
     WG_FOR(ctx, it, NFS * 4) w.fsb[it] = it < NF ? fact_combo(it >> 2, it & 3, w.sb, 1, 0, dt, hq) : 0.0;
@@ -550,21 +516,19 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
     };
     {
       if (wv < 2) {
-        if (!(HSQP_EXP & 32)) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         const DevWave dw{lane};
         const ElimIO io{&w.Ef[0][0], LDF, &w.PG[0][0], &w.PG[0][FG_GV], LDG, &w.Ef[0][EF_MI], LDF, nullptr, 0, &w.Zs[0][0], LDZ, w.zv, &w.ok};
         double* v_dst = &VAn[0][0];
         // wave 0 (the faster of the two) issues every asynchronous copy of the next stage: Vx, P~, R~
         auto prefetch = [&]() {
-          if (HSQP_EXP & 16) return;
           fetch_qpre();
-          if (wv == 0 && !(HSQP_EXP & 2)) { fact_next_vx_to_lds(qn, v_dst, lane); fact_next_cost_to_lds(qn, &w.Pn[0][0], &w.Rn[0][0], lane); }
+          if (wv == 0) { fact_next_vx_to_lds(qn, v_dst, lane); fact_next_cost_to_lds(qn, &w.Pn[0][0], &w.Rn[0][0], lane); }
         };
         if (wv == 0) eliminate_blocked<NXE, 0>(dw, io, prefetch);
         else eliminate_blocked<NXE, 1>(dw, io, prefetch);
         __builtin_amdgcn_s_setprio(0);
       } else if ((wv & 3) < 2) {
-        if (HSQP_EXP & 4) {} else {
         // waves 4, 5 share their SIMDs with the eliminating waves: memory only.  The next stage's Vu, b~, r~ through the
         // address tables: every load in flight before the first store, no index arithmetic in here
         double pb[FM_NPB];
@@ -575,58 +539,54 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
 #pragma unroll
           for (int t = 0; t < FM_NPB; ++t) if (FM_DST(t) >= 0) lbase[FM_DST(t)] = pb[t];
         }
-        }
       } else {
         // waves 2, 6 (SIMD 2) own column tiles 0, 3, waves 3, 7 (SIMD 3) column tiles 1, 2: 45 + 72 and 54 + 63 matrix instructions.  No global
         // access at all in here.
         const int ct = wv == 2 ? 0 : (wv == 6 ? 3 : (wv == 3 ? 1 : 2)), c0 = ct << 4;
         const int col = c0 + li, yc = col < NX ? col : NX - 1, ycp = fact_partner(yc);
         hsqp_d4 acc[4];
-        if (HSQP_SA_EARLY) sa_tiles(std::integral_constant<int, 3>{}, 1, ct);   // (row tile 0 of every column tile: formed in Ph2)
-        else sa_tiles(std::integral_constant<int, 4>{}, 0, ct);
+        sa_tiles(std::integral_constant<int, 3>{}, 1, ct);   // (row tile 0 of every column tile: formed in Ph2)
         WV_SYNC();
         // W' tiles (rt <= ct, ct) from the wave's own column of SA; the accumulators wait in registers until the column is consumed
-        if (!(HSQP_EXP & 8)) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) acc[t] = hsqp_d4{0.0, 0.0, 0.0, 0.0};
-          // Column NX of the last column tile is not a column of S A~: it carries sb (as if sb were column NX of SA).  The same tiles then leave
-          // A~^T sb = E_J^T sb + Vx^T (F^T sb) in that column — the vector part of the new s, which rounds 3 - 6 summed by 232 items in Ph4
-          const bool sbl = col == NX;                                   // (lane 10 of every row group of wave 6)
-          const double* ym = &w.SA[0][0];
-          constexpr int yld = LDA;
-          const int ycs = col < NX ? col : NX;
-          auto yf = [&](auto sc, int) { return fact_combo(sc, kk, ym, yld, ycs, dt, hq); };
-          auto xf = [&](auto sc, int t) {
-            constexpr int s = decltype(sc)::value;
-            const int kc = 4 * s + kk < NF ? 4 * s + kk : NF - 1, r = 16 * t + li;
-            const double v = VA[kc][r < NX ? r : NX - 1];
-            return 4 * s + kk < NF ? v : 0.0;
-          };
-          if (ct == 0) { hsqp_d4 a1[1] = {acc[0]}; fact_mfma<1, FACT_PF, NFS>(a1, xf, yf); acc[0] = a1[0]; }
-          else if (ct == 1) { hsqp_d4 a2[2] = {acc[0], acc[1]}; fact_mfma<2, FACT_PF, NFS>(a2, xf, yf); acc[0] = a2[0]; acc[1] = a2[1]; }
-          else if (ct == 2) { hsqp_d4 a3[3] = {acc[0], acc[1], acc[2]}; fact_mfma<3, FACT_PF, NFS>(a3, xf, yf); acc[0] = a3[0]; acc[1] = a3[1]; acc[2] = a3[2]; }
-          else fact_mfma<4, FACT_PF, NFS>(acc, xf, yf);
-          // (E_J^T SA)[row][col]: row `row` of E_J^T picks row `row` (and row - 29) of SA — unconditional reads of the own column, then the stores
+        for (int t = 0; t < 4; ++t) acc[t] = hsqp_d4{0.0, 0.0, 0.0, 0.0};
+        // Column NX of the last column tile is not a column of S A~: it carries sb (as if sb were column NX of SA).  The same tiles then leave
+        // A~^T sb = E_J^T sb + Vx^T (F^T sb) in that column — the vector part of the new s, which rounds 3 - 6 summed by 232 items in Ph4
+        const bool sbl = col == NX;                                   // (lane 10 of every row group of wave 6)
+        const double* ym = &w.SA[0][0];
+        constexpr int yld = LDA;
+        const int ycs = col < NX ? col : NX;
+        auto yf = [&](auto sc, int) { return fact_combo(sc, kk, ym, yld, ycs, dt, hq); };
+        auto xf = [&](auto sc, int t) {
+          constexpr int s = decltype(sc)::value;
+          const int kc = 4 * s + kk < NF ? 4 * s + kk : NF - 1, r = 16 * t + li;
+          const double v = VA[kc][r < NX ? r : NX - 1];
+          return 4 * s + kk < NF ? v : 0.0;
+        };
+        if (ct == 0) { hsqp_d4 a1[1] = {acc[0]}; fact_mfma<1, FACT_PF, NFS>(a1, xf, yf); acc[0] = a1[0]; }
+        else if (ct == 1) { hsqp_d4 a2[2] = {acc[0], acc[1]}; fact_mfma<2, FACT_PF, NFS>(a2, xf, yf); acc[0] = a2[0]; acc[1] = a2[1]; }
+        else if (ct == 2) { hsqp_d4 a3[3] = {acc[0], acc[1], acc[2]}; fact_mfma<3, FACT_PF, NFS>(a3, xf, yf); acc[0] = a3[0]; acc[1] = a3[1]; acc[2] = a3[2]; }
+        else fact_mfma<4, FACT_PF, NFS>(acc, xf, yf);
+        // (E_J^T SA)[row][col]: row `row` of E_J^T picks row `row` (and row - 29) of SA — unconditional reads of the own column, then the stores
 #pragma unroll
-          for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { const int row = 16 * t + kk + 4 * r, rc = row < NX ? row : NX - 1; acc[t][r] += fact_ej_mix(ym[rc * yld + ycs], ym[fact_partner(rc) * yld + ycs], rc, dt); }
-          WV_SYNC();   // every read of the column is done before it is overwritten
+          for (int r = 0; r < 4; ++r) { const int row = 16 * t + kk + 4 * r, rc = row < NX ? row : NX - 1; acc[t][r] += fact_ej_mix(ym[rc * yld + ycs], ym[fact_partner(rc) * yld + ycs], rc, dt); }
+        WV_SYNC();   // every read of the column is done before it is overwritten
 #pragma unroll
-          for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int row = 16 * t + kk + 4 * r;
-              if (t <= ct && col < NX && row < NX) w.SA[row][col] = acc[t][r];
-            }
-          // (A~^T sb)[rows] of the sb lanes: picked up by the S tiles of the last column in Ph4.  ONE branch of the wave around all of them (a lane
-          // condition per store was 16 branches on every tile wave: 2.2 k cycles of wave 2's epilogue)
-          if (ct == 3 && sbl) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) { const int row = 16 * t + kk + 4 * r; if (row < NX) w.SA[row][NX] = acc[t][r]; }
+          for (int r = 0; r < 4; ++r) {
+            const int row = 16 * t + kk + 4 * r;
+            if (t <= ct && col < NX && row < NX) w.SA[row][col] = acc[t][r];
           }
+        // (A~^T sb)[rows] of the sb lanes: picked up by the S tiles of the last column in Ph4.  ONE branch of the wave around all of them (a lane
+        // condition per store was 16 branches on every tile wave: 2.2 k cycles of wave 2's epilogue)
+        if (ct == 3 && sbl) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { const int row = 16 * t + kk + 4 * r; if (row < NX) w.SA[row][NX] = acc[t][r]; }
         }
         // waves 2, 3 form one S tile each in Ph4: its Q~ is fetched here, behind the wave's last LDS read of the phase (they finish 2 - 3 k cycles
         // before the elimination: the round trip runs under their wait at the barrier)
@@ -721,7 +681,7 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
       const XtyJob jk = xty_also_to(xty_job(NUT, NXE + 1, NUT, &w.Ef[0][EF_MI], LDF, &w.Zs[0][0], LDZ, &w.PG[0][0], LDG, nullptr, 0, -1.0), rk + RIC_K, NX, NXE);
 #if defined(__HIP_DEVICE_COMPILE__)
       constexpr int NSZ = (NUT + 3) / 4;
-      PH_LAP0(ctx, HSQP_LAP_WAVE);
+      PH_LAP0(ctx, LAP_WAVE);
       if (wv < 4) {
         // S tiles: six 23-deep steps, W' from LDS and Q~ from the registers loaded in Ph3
         auto run = [&](auto ntc) {
@@ -743,13 +703,13 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
           for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) wp[t][r] = lsa[FS_W(t) + (16 * fact_sym_tr(sfirst + t) + kk) * (LDA - NX) + 4 * LDA * r];   // (SA's rows are LDA apart, S's NX)
-          PH_LAP(ctx, HSQP_LAP_WAVE, 21);
+          PH_LAP(ctx, LAP_WAVE, 21);
           fact_mfma<NT, FACT_PF, NSZ>(acc, xf, yf);
           // (the z lane's addresses are formed HERE: left to the compiler they are formed in front of the stage loop, one register per element — a spill)
           int fm[NT];
 #pragma unroll
           for (int t = 0; t < NT; ++t) { fm[t] = FS_M(t); asm volatile("" : "+v"(fm[t])); }
-          PH_LAP(ctx, HSQP_LAP_WAVE, 22);
+          PH_LAP(ctx, LAP_WAVE, 22);
 #pragma unroll
           for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -771,10 +731,10 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
         };
         if (scount == 3) run(std::integral_constant<int, 3>{});
         else run(std::integral_constant<int, 2>{});
-        PH_LAP(ctx, HSQP_LAP_WAVE, 23);
+        PH_LAP(ctx, LAP_WAVE, 23);
       } else {
         // waves 4 .. 7: [K | k] = -L^-T [Z | z], two of the eight tiles each, one call (the vector items of the new s are gone: it leaves through the S tiles)
-        PH_LAP(ctx, HSQP_LAP_WAVE, 20);
+        PH_LAP(ctx, LAP_WAVE, 20);
         {
           const double* lz = &w.Zs[0][0];
           const double* le = &w.Ef[0][0];
@@ -796,7 +756,7 @@ HSQP_HD void riccati_backward_fact(const Ctx& ctx, RicFWS& w, const double* Qf, 
               if ((FK_MASK(t) >> (4 + r)) & 1) ((hsqp_gptr)rk)[FK_RK(t) + 4 * NX * r] = v;
             }
         }
-        PH_LAP(ctx, HSQP_LAP_WAVE, 23);
+        PH_LAP(ctx, LAP_WAVE, 23);
       }
 #else
       WG_FOR(ctx, it, 4 * NX) s_item(it);
