@@ -203,10 +203,30 @@ typedef struct hsqp_reference {
   hsqp_swing_config swing;
   double terrain_height;
   int32_t arm_swing;                    /* 0 disables the arm-swing reference                                     */
-  int32_t reserved;
+  int32_t warm_start;                   /* HSQP_WARM_*: where the linearisation trajectory comes from (below)      */
   const double* node_times;             /* optional [B][N+1]: time stamp of every node (non-uniform grids / event nodes: a post-event
                                            node carries t_event + epsilon, as ocs2's getIntervalStart does); NULL: t0 + k dt  */
 } hsqp_reference;
+/* hsqp_reference::warm_start — the receding-horizon warm start of HipSqpSolverAdaptor::runImpl (upstream ocs2 SqpSolver::runImpl),
+ * built on the device instead of being uploaded.  Every hsqp_upload_reference records the RAW time stamps of the new grid in the handle
+ * (uniform grid: t0 + k dt; event grid: node_times[k], except that a post-event node takes the stamp of the node before it, so the pre- and
+ * the post-event node of an event share one stamp, as in ocs2's PrimalSolution).
+ *   HSQP_WARM_CALLER  hsqp_problem::x_traj / u_traj are uploaded (the behaviour of ABI 6 and before).
+ *   HSQP_WARM_SHIFT   built from the solution resident in the handle (what hsqp_download would return) and its stamps: a new node whose
+ *                     stamp is not past the last old stamp T takes the clamped linear interpolation (std::upper_bound) of the old states
+ *                     and of the old STAMPED inputs (input j = u[min(j, N_old - 1)]; a pre-event node carries the input of the node before
+ *                     it: upstream toPrimalSolution); a node past T the state of the node before it (x_init for node 0) and the
+ *                     weight-compensating input of its contact flags (WeightCompInitializer: total mass * 9.81 on the stance feet'
+ *                     force z entries 2 / 8, divided by their number).  Bit for bit the adaptor's host arithmetic.  Needs: an iteration has
+ *                     run on a problem of the same batch uploaded through hsqp_upload_reference (hsqp_upload / hsqp_upload_device /
+ *                     hsqp_solve forget the stamps), non-decreasing node_times, and no numeric failure in that solution (else
+ *                     HSQP_ERR_NUMERIC with the message of hsqp_download).  n_nodes may differ from the previous problem's.  A rejected
+ *                     call leaves the resident solution as it was.
+ *   HSQP_WARM_COLD    the WeightCompInitializer cold start: x_k = x_init, u_k the weight-compensating input of node k's contact flags.
+ * With SHIFT or COLD, hsqp_problem::x_traj and u_traj must be NULL (x_init is still required). */
+#define HSQP_WARM_CALLER 0
+#define HSQP_WARM_SHIFT 1
+#define HSQP_WARM_COLD 2
 
 typedef struct hsqp_perf {      /* ocs2::PerformanceIndex subset, per instance                           */
   double merit, cost, dynamics_sse, equality_sse;
@@ -348,6 +368,10 @@ int hsqp_download_device(hsqp_handle* h, hsqp_solution* solution);
                                                     chain of the columns of [A|B] runs inside k_project, the defect on the lanes of k_lq_rows, and k_lq_chain is not launched
                                                     (HSQP_LQ_CHAIN_SEPARATE in the environment at hsqp_create: chain and defect in k_lq_chain, P6 / V6 through the LQ record).
                                                     Available at any time */
+/* Available as soon as a problem is resident (hsqp_upload_reference for STAMPS): */
+#define HSQP_BLK_X 13           /* [B][N+1][58]     the linearisation trajectory the next iteration starts from  */
+#define HSQP_BLK_U 14           /* [B][N][35]                                                              */
+#define HSQP_BLK_STAMPS 15      /* [B][N+1]         raw time stamps of the grid (hsqp_reference::warm_start)  */
 long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes);
 
 /* Elapsed device time (ms) of the kernels of the last hsqp_iterate_device call,
@@ -383,9 +407,9 @@ long long hsqp_scan_backoffs(const hsqp_handle* h);
 int hsqp_set_scan_backoff_persistent(hsqp_handle* h, int on);
 const char* hsqp_version(void);
 /* Binary interface revision: bumped whenever a public struct or an entry point's meaning changes (5: hsqp_linesearch_settings::cost_tol,
- * hsqp_set_scan_backoff_persistent; 6: hsqp_comm_*, HSQP_BLK_FORMS[2]).  A caller compares hsqp_abi_version() with the HSQP_ABI_VERSION it was compiled against before it
+ * hsqp_set_scan_backoff_persistent; 6: hsqp_comm_*, HSQP_BLK_FORMS[2]; 7: hsqp_reference::warm_start, HSQP_BLK_X / U / STAMPS).  A caller compares hsqp_abi_version() with the HSQP_ABI_VERSION it was compiled against before it
  * passes structs (host/HipSqpSolver.h and the Python binding do). */
-#define HSQP_ABI_VERSION 6
+#define HSQP_ABI_VERSION 7
 int hsqp_abi_version(void);
 int hsqp_device_count(void);
 

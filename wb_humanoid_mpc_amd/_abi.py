@@ -13,12 +13,14 @@ P_XDES, P_ARMSWING, P_CONTACT, P_SWING, P_IMPACT = 0, 58, 59, 61, 67
 FORM_WB, FORM_CENTROIDAL = 0, 1
 CNX, PC_TORSO = 35, 35
 
-ABI_VERSION = 6   # HSQP_ABI_VERSION of include/hsqp.h (tests/test_abi.py compares them)
+ABI_VERSION = 7   # HSQP_ABI_VERSION of include/hsqp.h (tests/test_abi.py compares them)
 
 OK, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_OOM, ERR_NUMERIC, ERR_HIP, ERR_NOT_CONVERGED = 0, -1, -2, -3, -4, -5, -6
 
 BLK_AB, BLK_BVEC, BLK_H, BLK_G, BLK_CDE, BLK_NE, BLK_COST, BLK_DX, BLK_DU, BLK_FLOW = range(1, 11)
 BLK_PARAMS, BLK_FORMS = 11, 12
+BLK_X, BLK_U, BLK_STAMPS = 13, 14, 15
+WARM_CALLER, WARM_SHIFT, WARM_COLD = 0, 1, 2   # hsqp_reference::warm_start
 COMM_ID_BYTES = 128   # HSQP_COMM_ID_BYTES
 
 
@@ -93,7 +95,7 @@ class Reference(C.Structure):
     _fields_ = [("batch", C.c_int32), ("n_nodes", C.c_int32), ("t0", C.c_double), ("dt", C.c_double), ("max_events", C.c_int32),
                 ("n_events", C.POINTER(C.c_int32)), ("event_times", C.POINTER(C.c_double)), ("mode_sequence", C.POINTER(C.c_int32)),
                 ("n_knots", C.c_int32), ("target_times", C.POINTER(C.c_double)), ("target_states", C.POINTER(C.c_double)),
-                ("swing", SwingConfig), ("terrain_height", C.c_double), ("arm_swing", C.c_int32), ("reserved", C.c_int32),
+                ("swing", SwingConfig), ("terrain_height", C.c_double), ("arm_swing", C.c_int32), ("warm_start", C.c_int32),
                 ("node_times", C.POINTER(C.c_double))]
 
 

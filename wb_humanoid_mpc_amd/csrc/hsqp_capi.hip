@@ -16,6 +16,7 @@
 #include "hsqp_riccati_fact.h"
 #include "hsqp_params.h"
 #include "hsqp_policy.h"
+#include "hsqp_warm.h"
 #include "hsqp_cent.h"
 #include "hsqp_cent_lq.h"
 #include "hsqp_scan.h"
@@ -778,6 +779,21 @@ __global__ __launch_bounds__(64) void k_params(const DevModel* __restrict__ dm, 
   if (!ok) atomicExch(bad, 1);
 }
 
+// ---- receding-horizon warm start (hsqp_warm.h) behind k_params: one wave per node of the new grid, WARM_WAVES nodes per workgroup
+// (blockIdx.x), one instance per blockIdx.y; the instance's previous stamps are staged in LDS once per workgroup (SHIFT)
+constexpr int WARM_WAVES = 4;
+__global__ __launch_bounds__(64 * WARM_WAVES) void k_warm_start(WarmArgs w) {
+  double* tp = reinterpret_cast<double*>(hsqp_smem);
+  const int b = blockIdx.y, k = blockIdx.x * WARM_WAVES + wave_index(threadIdx.x);
+  if (w.mode == HSQP_WARM_SHIFT) {
+    const double* src = w.stamps_prev + (size_t)b * (w.N_prev + 1);
+    for (int i = threadIdx.x; i <= w.N_prev; i += blockDim.x) tp[i] = src[i];
+    __syncthreads();
+  }
+  if (k > w.N) return;
+  warm_node(Ctx{(int)(threadIdx.x & 63), 64, nullptr}, w, tp, b, k);
+}
+
 // ---- policy evaluation / joint torques in three small kernels.
 //  k_policy_inputs: one workgroup per pair — xt != null: interpolate the trajectories of instance blockIdx.x at s[blockIdx.x]
 //                   (uniform grid, or dts != null: the instance's interval lengths); otherwise take the pair from xin / uin.
@@ -928,6 +944,12 @@ struct hsqp_handle {
   int B = 0, N = 0;
   double dt = 0.0;
   bool have_problem = false, have_solution = false;
+  // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
+  // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
+  // with non-decreasing stamps
+  double* d_stamps[2] = {nullptr, nullptr};
+  int stamps_cur = 0;
+  bool have_stamps = false;
   double kernel_ms[5] = {0, 0, 0, 0, 0};
   int last_iterations = 0;
   struct IterLog { std::vector<hsqp_perf> perf; std::vector<double> alpha; std::vector<int> type; };
@@ -1080,7 +1102,7 @@ static int launch_segmented(hsqp_handle* h, int B, int N, int P, bool want_vf) {
 
 extern "C" {
 
-const char* hsqp_version(void) { return "hsqp-hip 0.3 (gfx950, f64, abi 6)"; }
+const char* hsqp_version(void) { return "hsqp-hip 0.3 (gfx950, f64, abi 7)"; }
 int hsqp_abi_version(void) { return HSQP_ABI_VERSION; }
 int hsqp_set_scan_backoff_persistent(hsqp_handle* h, int on) {
   if (!h) return HSQP_ERR_BAD_ARG;
@@ -1103,7 +1125,7 @@ void hsqp_destroy(hsqp_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   void* bufs[] = {h->d_dm, h->d_xinit, h->d_x, h->d_u, h->d_par, h->d_rec, h->d_qp, h->d_ric, h->d_dx, h->d_du, h->d_ut, h->d_fj, h->d_xnew,
-                  h->d_unew, h->d_misc, h->d_kkt, h->d_dt, h->d_perf_before, h->d_perf_after, h->d_status, h->d_prof, h->d_stepinfo, h->d_ls, h->d_counts, h->d_vf, h->d_stage,
+                  h->d_unew, h->d_misc, h->d_kkt, h->d_dt, h->d_perf_before, h->d_perf_after, h->d_status, h->d_prof, h->d_stepinfo, h->d_ls, h->d_counts, h->d_vf, h->d_stage, h->d_stamps[0], h->d_stamps[1],
                   h->d_el[0], h->d_el[1], h->d_vf2, h->d_acl, h->d_ric2, h->d_linv, h->d_vf0, h->d_zero};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
@@ -1221,7 +1243,8 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
       {(void**)&h->d_xnew, B * (N + 1) * NX * 8}, {(void**)&h->d_unew, B * N * NU * 8}, {(void**)&h->d_misc, B * N * 8 * 8},
       {(void**)&h->d_kkt, B * 3 * 8 + ((B * sizeof(int) + 7) / 8) * 8}, {(void**)&h->d_dt, B * N * 8}, {(void**)&h->d_perf_before, B * sizeof(hsqp_perf)}, {(void**)&h->d_perf_after, B * sizeof(hsqp_perf)},
       {(void**)&h->d_status, B * sizeof(int)}, {(void**)&h->d_prof, 4 * 128 * sizeof(long long)},
-      {(void**)&h->d_stepinfo, B * N * 4 * 8}, {(void**)&h->d_ls, B * sizeof(LsState)}, {(void**)&h->d_counts, 2 * sizeof(int)}};
+      {(void**)&h->d_stepinfo, B * N * 4 * 8}, {(void**)&h->d_ls, B * sizeof(LsState)}, {(void**)&h->d_counts, 2 * sizeof(int)},
+      {(void**)&h->d_stamps[0], B * (N + 1) * 8}, {(void**)&h->d_stamps[1], B * (N + 1) * 8}};
   for (const Alloc& a : allocs) {
     if (hipMalloc(a.p, a.bytes) != hipSuccess) return fail(HSQP_ERR_OOM, "hipMalloc failed (" + std::to_string(a.bytes) + " bytes)");
     poison_hbm(h, *a.p, a.bytes);
@@ -1269,7 +1292,8 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
 // centroidal formulation: the padding states of every state row must be zero (include/hsqp.h)
 static bool padding_is_zero(hsqp_handle* h, const hsqp_problem* p) {
   if (h->hdm.formulation != HSQP_FORM_CENTROIDAL) return true;
-  for (size_t r = 0; r < (size_t)p->batch * (p->n_nodes + 2); ++r) {
+  const size_t rows = (size_t)p->batch * (p->x_traj ? p->n_nodes + 2 : 1);   // (no x_traj: the warm start is built on the device)
+  for (size_t r = 0; r < rows; ++r) {
     const double* row = r < (size_t)p->batch ? p->x_init + r * NX : p->x_traj + (r - p->batch) * NX;
     for (int i = HSQP_CNX; i < NX; ++i)
       if (row[i] != 0.0) { h->err = "centroidal formulation: entries 35..57 of every state row must be zero"; return false; }
@@ -1324,7 +1348,7 @@ static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   const size_t B = p->batch, N = p->n_nodes;
   const hipMemcpyKind kind = device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   // the grid is validated BEFORE any trajectory copy is queued; a rejected problem leaves no half-uploaded state behind
-  h->have_problem = false; h->have_solution = false;
+  h->have_problem = false; h->have_solution = false; h->have_stamps = false;
   { const int rc = set_grid(h, p, device_src); if (rc != HSQP_OK) return rc; }
   HCHECK(hipMemcpyAsync(h->d_xinit, p->x_init, B * NX * 8, kind, h->stream));
   HCHECK(hipMemcpyAsync(h->d_x, p->x_traj, B * (N + 1) * NX * 8, kind, h->stream));
@@ -1341,10 +1365,30 @@ static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
 int hsqp_upload(hsqp_handle* h, const hsqp_problem* p) { return upload_impl(h, p, false); }
 int hsqp_upload_device(hsqp_handle* h, const hsqp_problem* p) { return upload_impl(h, p, true); }
 
+// the numeric status of the resident solution (d_status, read back by the caller): HSQP_ERR_NUMERIC and its message if an instance failed
+static int check_status(hsqp_handle* h, const std::vector<int>& status) {
+  for (size_t b = 0; b < status.size(); ++b)
+    if (status[b]) {
+      h->err = "instance " + std::to_string(b) + ": " + ((status[b] & 1) ? "rank-deficient equality Jacobian D " : "") +
+               ((status[b] & 2) ? "reduced Hessian not positive definite" : "");
+      return HSQP_ERR_NUMERIC;
+    }
+  return HSQP_OK;
+}
+
 int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r) {
   if (!h) return HSQP_ERR_BAD_ARG;
-  if (!p || !r || !p->x_init || !p->x_traj || !p->u_traj || !r->n_events || !r->event_times || !r->mode_sequence || !r->target_times || !r->target_states) {
+  if (!p || !r || !p->x_init || !r->n_events || !r->event_times || !r->mode_sequence || !r->target_times || !r->target_states) {
     h->err = "null problem / reference pointer";
+    return HSQP_ERR_BAD_ARG;
+  }
+  const int warm = r->warm_start;
+  if (warm != HSQP_WARM_CALLER && warm != HSQP_WARM_SHIFT && warm != HSQP_WARM_COLD) {
+    h->err = "hsqp_reference::warm_start must be HSQP_WARM_CALLER, HSQP_WARM_SHIFT or HSQP_WARM_COLD";
+    return HSQP_ERR_BAD_ARG;
+  }
+  if ((warm == HSQP_WARM_CALLER) != (p->x_traj && p->u_traj) || (warm != HSQP_WARM_CALLER && (p->x_traj || p->u_traj))) {
+    h->err = warm == HSQP_WARM_CALLER ? "null problem / reference pointer" : "warm_start SHIFT / COLD: hsqp_problem::x_traj and u_traj must be NULL";
     return HSQP_ERR_BAD_ARG;
   }
   if (p->batch < 1 || p->batch > h->st.max_batch || p->n_nodes < 1 || p->n_nodes > h->st.max_nodes || (!p->dt_nodes && !(p->dt > 0.0))) {
@@ -1362,7 +1406,22 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   for (int b = 0; b < r->batch; ++b)
     if (r->n_events[b] < 1 || r->n_events[b] > r->max_events) { h->err = "n_events outside [1, max_events]"; return HSQP_ERR_BAD_ARG; }
   if (!padding_is_zero(h, p)) return HSQP_ERR_BAD_ARG;
+  bool sorted = true;   // raw stamps of the new grid non-decreasing (always on a uniform grid): what the interpolation of a later SHIFT needs
+  for (size_t i = 1; r->node_times && sorted && i < (size_t)p->batch * (p->n_nodes + 1); ++i)
+    sorted = i % (p->n_nodes + 1) == 0 || r->node_times[i] >= r->node_times[i - 1];
   HCHECK(hipSetDevice(h->device));
+  const int N_prev = h->N;
+  if (warm == HSQP_WARM_SHIFT) {   // preconditions, checked before anything is copied: a rejected call leaves the resident solution as it was
+    if (!h->have_solution || !h->have_stamps) {
+      h->err = "warm_start SHIFT: no resident solution of a problem uploaded through hsqp_upload_reference";
+      return HSQP_ERR_BAD_ARG;
+    }
+    if (h->B != p->batch) { h->err = "warm_start SHIFT: the batch differs from the resident solution's"; return HSQP_ERR_BAD_ARG; }
+    if (!sorted) { h->err = "warm_start SHIFT: node_times must not decrease"; return HSQP_ERR_BAD_ARG; }
+    std::vector<int> status(h->B);
+    HCHECK(hipMemcpy(status.data(), h->d_status, status.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (check_status(h, status) != HSQP_OK) return HSQP_ERR_NUMERIC;
+  }
   const size_t B = p->batch, N = p->n_nodes, E = r->max_events, K = r->n_knots;
   // staging area for the compact reference (a few KB per instance)
   const size_t o_ne = 0, o_seq = o_ne + align256(B * 4), o_bad = o_seq + align256(B * (E + 1) * 4), o_ev = o_bad + 256,
@@ -1378,7 +1437,7 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   double* d_ts = reinterpret_cast<double*>(base + o_ts);
   double* d_nt = r->node_times ? reinterpret_cast<double*>(base + o_nt) : nullptr;
   auto release = []() {};
-  h->have_problem = false; h->have_solution = false;   // a failure below leaves no half-uploaded problem behind
+  h->have_problem = false; h->have_solution = false; h->have_stamps = false;   // a failure below leaves no half-uploaded problem behind
   int rc = set_grid(h, p, false);
   if (rc != HSQP_OK) return rc;
   auto step = [&](hipError_t e, const char* what) { if (rc == HSQP_OK && e != hipSuccess) { h->err = std::string(what) + ": " + hipGetErrorString(e); rc = HSQP_ERR_HIP; } };
@@ -1390,8 +1449,10 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   step(hipMemcpyAsync(d_ts, r->target_states, B * K * NX * 8, hipMemcpyHostToDevice, h->stream), "upload target_states");
   step(hipMemsetAsync(d_bad, 0, 4, h->stream), "memset");
   step(hipMemcpyAsync(h->d_xinit, p->x_init, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x_init");
-  step(hipMemcpyAsync(h->d_x, p->x_traj, B * (N + 1) * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
-  step(hipMemcpyAsync(h->d_u, p->u_traj, B * N * NU * 8, hipMemcpyHostToDevice, h->stream), "upload u");
+  if (warm == HSQP_WARM_CALLER) {
+    step(hipMemcpyAsync(h->d_x, p->x_traj, B * (N + 1) * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
+    step(hipMemcpyAsync(h->d_u, p->u_traj, B * N * NU * 8, hipMemcpyHostToDevice, h->stream), "upload u");
+  }
   if (rc == HSQP_OK) {
     const int total = (int)(B * (N + 1));
     HSQP_LAUNCH(k_params, dim3((total + 63) / 64), dim3(64), 0, h->stream, h->d_dm, r->swing, r->terrain_height, r->arm_swing, (int)E, d_ne, d_ev, d_seq,
@@ -1399,6 +1460,17 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
     if (h->hdm.formulation == HSQP_FORM_CENTROIDAL)   // torso task-space reference of every row
       HSQP_LAUNCH(k_params_cent_torso, dim3(total), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_par);
     step(hipGetLastError(), "k_params");
+  }
+  if (rc == HSQP_OK) {   // the grid's raw stamps (every mode) and the device-built warm start (SHIFT / COLD), after k_params wrote the contact flags
+    WarmArgs w{};
+    w.mode = warm; w.B = (int)B; w.N = (int)N; w.N_prev = warm == HSQP_WARM_SHIFT ? N_prev : 0; w.cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
+    w.t0 = r->t0; w.dt = r->dt; w.total_mass = h->hdm.total_mass;
+    w.node_times = d_nt; w.dts = h->d_dt; w.par = h->d_par; w.x_init = h->d_xinit;
+    w.x_prev = h->d_xnew; w.u_prev = h->d_unew; w.stamps_prev = h->d_stamps[h->stamps_cur];
+    w.x = h->d_x; w.u = h->d_u; w.stamps = h->d_stamps[1 - h->stamps_cur];
+    const size_t lds = warm == HSQP_WARM_SHIFT ? (size_t)(N_prev + 1) * 8 : 0;
+    HSQP_LAUNCH(k_warm_start, dim3((unsigned)((N + 1 + WARM_WAVES - 1) / WARM_WAVES), (unsigned)B), dim3(64 * WARM_WAVES), lds, h->stream, w);
+    step(hipGetLastError(), "k_warm_start");
   }
   int bad = 0;
   step(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream), "download status");
@@ -1409,6 +1481,7 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   const bool same_shape = h->B == p->batch && h->N == p->n_nodes;
   h->B = p->batch; h->N = p->n_nodes; h->dt = p->dt;
   h->have_problem = true; h->have_solution = false;
+  h->stamps_cur = 1 - h->stamps_cur; h->have_stamps = sorted;
   if (!(h->backoff_persistent && same_shape)) { h->seg_backoff = 0; h->seg_backoff_len = 0; }
   return HSQP_OK;
 }
@@ -1787,13 +1860,7 @@ static int download_impl(hsqp_handle* h, hsqp_solution* s, bool device_dst) {
   s->timings.linesearch = 1e-3 * h->kernel_ms[3];
   s->timings.compute_controller = 0.0;
   s->timings.total = 1e-3 * h->kernel_ms[4];
-  for (size_t b = 0; b < B; ++b)
-    if (status[b]) {
-      h->err = "instance " + std::to_string(b) + ": " + ((status[b] & 1) ? "rank-deficient equality Jacobian D " : "") +
-               ((status[b] & 2) ? "reduced Hessian not positive definite" : "");
-      return HSQP_ERR_NUMERIC;
-    }
-  return HSQP_OK;
+  return check_status(h, status);
 }
 
 int hsqp_download(hsqp_handle* h, hsqp_solution* s) { return download_impl(h, s, false); }
@@ -1896,6 +1963,17 @@ long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes) 
     if (hipSetDevice(h->device) != hipSuccess) return HSQP_ERR_HIP;
     const long long size = (long long)h->B * (h->N + 1) * NP * 8;
     if (dst && bytes > 0 && hipMemcpy(dst, h->d_par, (size_t)(bytes < size ? bytes : size), hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP;
+    return size;
+  }
+  if (what == HSQP_BLK_X || what == HSQP_BLK_U || what == HSQP_BLK_STAMPS) {   // the resident linearisation trajectory and grid stamps
+    if (!h->have_problem || (what == HSQP_BLK_STAMPS && !h->have_stamps)) {
+      h->err = what == HSQP_BLK_STAMPS ? "no stamps: the resident problem was not uploaded through hsqp_upload_reference" : "no problem uploaded";
+      return HSQP_ERR_BAD_ARG;
+    }
+    if (hipSetDevice(h->device) != hipSuccess) return HSQP_ERR_HIP;
+    const double* src = what == HSQP_BLK_X ? h->d_x : what == HSQP_BLK_U ? h->d_u : h->d_stamps[h->stamps_cur];
+    const long long size = (long long)h->B * (what == HSQP_BLK_X ? (h->N + 1) * NX : what == HSQP_BLK_U ? h->N * NU : h->N + 1) * 8;
+    if (dst && bytes > 0 && hipMemcpy(dst, src, (size_t)(bytes < size ? bytes : size), hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP;
     return size;
   }
   if (!h->have_solution) { h->err = "no iteration has run"; return HSQP_ERR_BAD_ARG; }

@@ -47,8 +47,8 @@ class HipSqpSolver {
   HipSqpSolver(const HipSqpSolver&) = delete;
   HipSqpSolver& operator=(const HipSqpSolver&) = delete;
 
-  /** SolverBase::reset: forget the previous solution (the next run is a cold start supplied by the caller). */
-  void reset() { solution_ = PrimalSolution(); perf_.clear(); }
+  /** SolverBase::reset: forget the previous solution (the next run is a cold start supplied by the caller; runRecedingHorizon: built on the device). */
+  void reset() { solution_ = PrimalSolution(); perf_.clear(); shiftable_ = false; }
 
   /**
    * SolverBase::run for `batch` instances on a uniform grid of `nodes` intervals: one SQP iteration
@@ -68,6 +68,7 @@ class HipSqpSolver {
     s.alpha = stepSize_.data(); s.step_type = stepType_.data();
     s.x = solution_.stateTrajectory.data(); s.u = solution_.inputTrajectory.data();
     s.perf_before = perfBefore_.data(); s.perf_after = perf_.data(); s.kkt = reportKkt_ ? kkt_.data() : nullptr;
+    shiftable_ = false;   // (hsqp_solve forgets the grid's stamps)
     const int rc = hsqp_solve(h_, &p, &s);
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_solve failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     bench_.linearQuadraticApproximationTime = s.timings.lq_approximation;
@@ -85,29 +86,28 @@ class HipSqpSolver {
                         bool takeStepWithLinesearch = false, const double* dtNodes = nullptr /* non-uniform grid with event nodes: [batch][nodes] interval
                         lengths (0 = event), together with ref.node_times */,
                         int maxIterations = 1 /* sqp::Settings::sqpIteration: all of them in ONE device call, ended early by ocs2's step-size test */) {
-    const int batch = ref.batch;
-    hsqp_problem p{batch, nodes, dt, xInit, xTraj, uTraj, nullptr, dtNodes};
-    int rc = hsqp_upload_reference(h_, &p, &ref);
-    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_upload_reference failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
-    rc = hsqp_iterate_device(h_, maxIterations < 1 ? 1 : maxIterations,
-                             HSQP_ITER_TAKE_STEP | (reportKkt_ ? HSQP_ITER_KKT : 0) | (takeStepWithLinesearch ? HSQP_ITER_LINESEARCH : 0) | HSQP_ITER_UNTIL_CONVERGED);
-    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_iterate_device failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
-    iterations_ = hsqp_last_iterations(h_);
-    solution_.batch = batch; solution_.nodes = nodes;
-    solution_.stateTrajectory.assign((size_t)batch * (nodes + 1) * HSQP_NX, 0.0);
-    solution_.inputTrajectory.assign((size_t)batch * nodes * HSQP_NU, 0.0);
-    perf_.assign(batch, hsqp_perf{}); perfBefore_.assign(batch, hsqp_perf{});
-    kkt_.assign((size_t)batch * 2, 0.0); stepSize_.assign(batch, 0.0); stepType_.assign(batch, HSQP_STEP_FULL);
-    hsqp_solution s{};
-    s.x = solution_.stateTrajectory.data(); s.u = solution_.inputTrajectory.data();
-    s.perf_before = perfBefore_.data(); s.perf_after = perf_.data(); s.kkt = reportKkt_ ? kkt_.data() : nullptr;
-    s.alpha = stepSize_.data(); s.step_type = stepType_.data();
-    rc = hsqp_download(h_, &s);
-    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_download failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
-    bench_.linearQuadraticApproximationTime = s.timings.lq_approximation;
-    bench_.solveQpTime = s.timings.solve_qp;
-    bench_.linesearchTime = s.timings.linesearch;
-    bench_.computeControllerTime = s.timings.compute_controller;
+    hsqp_reference r = ref;
+    r.warm_start = HSQP_WARM_CALLER;
+    uploadAndIterate(nodes, dt, xInit, xTraj, uTraj, r, takeStepWithLinesearch, dtNodes, maxIterations);
+    download();
+  }
+
+  /**
+   * One cycle of a receding-horizon loop (MPC_BASE::run) with the warm start built on the device (hsqp_reference::warm_start): the solution
+   * of the previous cycle, resident in the handle, interpolated onto the new grid, the uncovered tail from the WeightCompInitializer — the
+   * host warm start of HipSqpSolverAdaptor::runImpl without the trajectories crossing PCIe.  A cold start (x_k = xInit, weight-compensating
+   * inputs) on the first call and after reset() or run(); `ref.warm_start` is ignored.  withDownload = false leaves the solution on the
+   * device: getPrimalSolution() then holds no trajectories, evaluatePolicy() still works.
+   */
+  void runRecedingHorizon(int nodes, double dt, const double* xInit, const hsqp_reference& ref, bool takeStepWithLinesearch = false,
+                          const double* dtNodes = nullptr, int maxIterations = 1, bool withDownload = true) {
+    hsqp_reference r = ref;
+    r.warm_start = shiftable_ ? HSQP_WARM_SHIFT : HSQP_WARM_COLD;
+    uploadAndIterate(nodes, dt, xInit, nullptr, nullptr, r, takeStepWithLinesearch, dtNodes, maxIterations);
+    if (withDownload) { download(); return; }
+    solution_.stateTrajectory.clear(); solution_.inputTrajectory.clear();
+    double ms[5];   // the benchmark buckets as hsqp_download reports them
+    if (hsqp_last_kernel_ms(h_, ms) == HSQP_OK) bench_ = Benchmarks{1e-3 * (ms[0] + ms[1]), 1e-3 * ms[2], 1e-3 * ms[3], 0.0};
   }
 
   /** MPC_MRT_Interface::evaluatePolicy + computeJointTorques for the solution of the last run: per instance, at `secondsAfterStart`. */
@@ -146,6 +146,39 @@ class HipSqpSolver {
   hsqp_handle* handle() { return h_; }
 
  private:
+  void uploadAndIterate(int nodes, double dt, const double* xInit, const double* xTraj, const double* uTraj, const hsqp_reference& ref,
+                        bool takeStepWithLinesearch, const double* dtNodes, int maxIterations) {
+    const int batch = ref.batch;
+    hsqp_problem p{batch, nodes, dt, xInit, xTraj, uTraj, nullptr, dtNodes};
+    shiftable_ = false;
+    int rc = hsqp_upload_reference(h_, &p, &ref);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_upload_reference failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    rc = hsqp_iterate_device(h_, maxIterations < 1 ? 1 : maxIterations,
+                             HSQP_ITER_TAKE_STEP | (reportKkt_ ? HSQP_ITER_KKT : 0) | (takeStepWithLinesearch ? HSQP_ITER_LINESEARCH : 0) | HSQP_ITER_UNTIL_CONVERGED);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_iterate_device failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    shiftable_ = true;
+    iterations_ = hsqp_last_iterations(h_);
+    solution_.batch = batch; solution_.nodes = nodes;
+  }
+
+  void download() {
+    const int batch = solution_.batch, nodes = solution_.nodes;
+    solution_.stateTrajectory.assign((size_t)batch * (nodes + 1) * HSQP_NX, 0.0);
+    solution_.inputTrajectory.assign((size_t)batch * nodes * HSQP_NU, 0.0);
+    perf_.assign(batch, hsqp_perf{}); perfBefore_.assign(batch, hsqp_perf{});
+    kkt_.assign((size_t)batch * 2, 0.0); stepSize_.assign(batch, 0.0); stepType_.assign(batch, HSQP_STEP_FULL);
+    hsqp_solution s{};
+    s.x = solution_.stateTrajectory.data(); s.u = solution_.inputTrajectory.data();
+    s.perf_before = perfBefore_.data(); s.perf_after = perf_.data(); s.kkt = reportKkt_ ? kkt_.data() : nullptr;
+    s.alpha = stepSize_.data(); s.step_type = stepType_.data();
+    const int rc = hsqp_download(h_, &s);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_download failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    bench_.linearQuadraticApproximationTime = s.timings.lq_approximation;
+    bench_.solveQpTime = s.timings.solve_qp;
+    bench_.linesearchTime = s.timings.linesearch;
+    bench_.computeControllerTime = s.timings.compute_controller;
+  }
+
   hsqp_handle* h_ = nullptr;
   PrimalSolution solution_;
   std::vector<hsqp_perf> perf_, perfBefore_;
@@ -154,6 +187,7 @@ class HipSqpSolver {
   Benchmarks bench_;
   int iterations_ = 0;
   bool reportKkt_ = false;
+  bool shiftable_ = false;   // the handle holds the solution of a runWithReference / runRecedingHorizon: the next runRecedingHorizon shifts it
 };
 
 }  // namespace hsqp_host

@@ -43,6 +43,11 @@ struct HipSqpAdaptorConfig {
   bool armSwingReference = true;
   bool eventNodes = true;         // false: uniform grid, mode switches snap to the nodes (the bench's configuration)
   int device = 0;
+  // true: step 2 (the warm start) runs on the device from the solution resident in the handle (hsqp_reference::warm_start: SHIFT, COLD on the
+  // first call and after reset()) instead of on the host — same numbers, bit for bit, provided the configured Initializer is the reference's
+  // WeightCompInitializer (the device builds that one: state kept, weight-compensating input of the node's contact flags).  The trajectories
+  // are still downloaded (getPrimalSolution).  The runImpl overload with an external PrimalSolution takes the host path for that call.
+  bool deviceWarmStart = false;
 };
 
 struct HipSqpBenchmarks {         // SqpSolver::getBenchmarks() of the fork (SqpBenchmarksPublisher.cpp:44-57), accumulated seconds
@@ -167,9 +172,11 @@ class HipSqpSolverAdaptor final : public SolverBase {
     primal_.inputTrajectory_ = primalSolution.inputTrajectory_;
     primal_.postEventIndices_ = primalSolution.postEventIndices_;
     primal_.modeSchedule_ = primalSolution.modeSchedule_;
-    runImpl(initTime, initState, finalTime);
+    solve(initTime, initState, finalTime, /*deviceWarmStart*/ false);
   }
-  void runImpl(scalar_t initTime, const vector_t& initState, scalar_t finalTime) override {
+  void runImpl(scalar_t initTime, const vector_t& initState, scalar_t finalTime) override { solve(initTime, initState, finalTime, cfg_.deviceWarmStart); }
+
+  void solve(scalar_t initTime, const vector_t& initState, scalar_t finalTime, bool deviceWarmStart) {
     const int nx = cfg_.stateDim;
     if ((int)initState.size() != nx) throw std::runtime_error("[HipSqpSolverAdaptor] initial state has the wrong dimension");
     const ReferenceManagerInterface& ref = getReferenceManager();
@@ -190,13 +197,13 @@ class HipSqpSolverAdaptor final : public SolverBase {
     std::vector<double> dts(N), nodeTimes(N + 1);
     for (int k = 0; k < N; ++k) dts[k] = times[k + 1] - times[k];
     for (int k = 0; k <= N; ++k) nodeTimes[k] = times[k] + (post[k] ? kEventEps : 0.0);
-    // 2. warm start
+    // 2. warm start (deviceWarmStart: built on the device at the upload, from the solution the handle holds — the one primal_ was made from)
     std::vector<double> x((size_t)(N + 1) * HSQP_NX, 0.0), u((size_t)N * HSQP_NU, 0.0), x0(HSQP_NX, 0.0);
     std::copy_n(initState.data(), nx, x0.data());
     const bool have = !primal_.timeTrajectory_.empty();
     const scalar_t covered = have ? primal_.timeTrajectory_.back() : initTime;
     vector_t xk(nx), uk(HSQP_NU), xn(nx);
-    for (int k = 0; k <= N; ++k) {
+    for (int k = 0; !deviceWarmStart && k <= N; ++k) {
       double* xr = &x[(size_t)k * HSQP_NX];
       if (have && times[k] <= covered) {
         interpolate(primal_.timeTrajectory_, primal_.stateTrajectory_, times[k], xr, nx);
@@ -227,8 +234,14 @@ class HipSqpSolverAdaptor final : public SolverBase {
     //    HBM between the iterations; the loop ends early by SqpSolver::checkConvergence's step-size test, evaluated per iteration from a
     //    small read-back of the line-search state)
     log_.clear();
-    impl_.runWithReference(N, settings_.dt, x0.data(), x.data(), u.data(), r, /*line search*/ true, cfg_.eventNodes ? dts.data() : nullptr,
-                           (int)std::max<size_t>(settings_.sqpIteration, 1));
+    if (deviceWarmStart) {
+      if (!have) impl_.reset();   // COLD (first call, reset()); SHIFT otherwise
+      impl_.runRecedingHorizon(N, settings_.dt, x0.data(), r, /*line search*/ true, cfg_.eventNodes ? dts.data() : nullptr,
+                               (int)std::max<size_t>(settings_.sqpIteration, 1), /*withDownload*/ true);
+    } else {
+      impl_.runWithReference(N, settings_.dt, x0.data(), x.data(), u.data(), r, /*line search*/ true, cfg_.eventNodes ? dts.data() : nullptr,
+                             (int)std::max<size_t>(settings_.sqpIteration, 1));
+    }
     {
       const hsqp_host::PrimalSolution& s = impl_.getPrimalSolution();
       x = s.stateTrajectory; u = s.inputTrajectory;

@@ -327,6 +327,69 @@ def event_grid(t0, tf, dt, event_times):
     return np.diff(times), times + EVENT_EPS * post
 
 
+def raw_stamps(dts, node_times):
+    """PrimalSolution time stamps of a grid from its interval lengths and sampling times (event_grid): a post-event node takes the stamp of
+    the node before it, so pre- and post-event node share one (what hsqp_upload_reference records, HSQP_BLK_STAMPS)."""
+    st = np.array(node_times, dtype=np.float64)
+    dts = np.broadcast_to(dts, st.shape[:-1] + (st.shape[-1] - 1,))
+    for k in range(1, st.shape[-1]):
+        st[..., k] = np.where(dts[..., k - 1] == 0.0, st[..., k - 1], st[..., k])
+    return st
+
+
+def stamped_inputs(times, u):
+    """The inputs of a PrimalSolution (HipSqpSolverAdaptor step 5, upstream toPrimalSolution): [..][N+1][35] from [..][N][35] and the raw
+    stamps [N+1]; a pre-event node (zero-length interval k, 0 < k < N) repeats the input before it, the last input is repeated."""
+    u = np.array(u, dtype=np.float64)
+    N = u.shape[-2]
+    for k in range(1, N):
+        if times[k + 1] == times[k]:
+            u[..., k, :] = u[..., k - 1, :]
+    return np.concatenate([u, u[..., N - 1:N, :]], axis=-2)
+
+
+def _interp_at(t, v, tau):
+    """ocs2 LinearInterpolation (clamped, std::upper_bound on the stamps t) of rows v[B][len(t)][n] at the times tau, unfused like the host."""
+    i = np.clip(np.searchsorted(t, tau, side="right"), 1, len(t) - 1)
+    h = t[i] - t[i - 1]
+    a = np.where(h > 0.0, (tau - t[i - 1]) / np.where(h > 0.0, h, 1.0), 1.0)
+    blend = (1.0 - a)[None, :, None] * v[:, i - 1] + a[None, :, None] * v[:, i]
+    return np.where((tau <= t[0])[None, :, None], v[:, :1], np.where((tau >= t[-1])[None, :, None], v[:, -1:], blend))
+
+
+def host_warm_start(total_mass, x_init, times, contact, prev=None, nx=_abi.NX):
+    """The adaptor's host warm start (HipSqpSolverAdaptor::runImpl steps 2 and 5; upstream SqpSolver::runImpl with the reference's
+    WeightCompInitializer), batched: the previous solution interpolated onto the new grid's raw stamps, the nodes past its last stamp
+    from the initializer (state of the node before / x_init, weight-compensating input of the node's contact flags).
+    x_init [B][58]; times: raw stamps [N+1] (shared) or [B][N+1]; contact: flags [B][N(+1)][2]; prev: None (cold start) or
+    dict(times=[Np+1] or [B][Np+1], x=[B][Np+1][58], u=[B][Np][35]) — the solution as hsqp_download returns it.  The arithmetic of the
+    adaptor, element by element (what hsqp_reference::warm_start reproduces on the device).  Returns (x [B][N+1][58], u [B][N][35])."""
+    x_init = np.asarray(x_init, dtype=np.float64)
+    B = x_init.shape[0]
+    times = np.asarray(times, dtype=np.float64)
+    pt = None if prev is None else np.asarray(prev["times"], dtype=np.float64)
+    if times.ndim == 2 or (pt is not None and pt.ndim == 2):
+        outs = [host_warm_start(total_mass, x_init[b:b + 1], times[b] if times.ndim == 2 else times, contact[b:b + 1],
+                                None if prev is None else dict(times=pt[b] if pt.ndim == 2 else pt, x=prev["x"][b:b + 1], u=prev["u"][b:b + 1]), nx)
+                for b in range(B)]
+        return np.concatenate([o[0] for o in outs]), np.concatenate([o[1] for o in outs])
+    N = len(times) - 1
+    x, u = np.zeros((B, N + 1, _abi.NX)), np.zeros((B, N, _abi.NU))
+    kc = 0 if pt is None else int(np.count_nonzero(times <= pt[-1]))   # the stamps do not decrease: the covered nodes are a prefix
+    if kc:
+        x[:, :kc, :nx] = _interp_at(pt, np.asarray(prev["x"], dtype=np.float64)[:, :, :nx], times[:kc])
+        ku = min(kc, N)
+        u[:, :ku] = _interp_at(pt, stamped_inputs(pt, prev["u"]), times[:ku])
+    x[:, kc:, :nx] = (x[:, kc - 1, :nx] if kc else x_init[:, :nx])[:, None, :]
+    c = np.asarray(contact)[:, kc:N] > 0.5
+    ns = c[..., 0].astype(np.int64) + c[..., 1].astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fz = total_mass * 9.81 / ns
+    u[:, kc:, 2] = np.where(c[..., 0], fz, 0.0)
+    u[:, kc:, 8] = np.where(c[..., 1], fz, 0.0)
+    return x, u
+
+
 def build_node_params_at(model, schedule, targets, node_times, arm_swing=True):
     """build_node_params on explicit node times (non-uniform grid / event nodes)."""
     planner = SwingTrajectoryPlanner(model.swing, schedule)

@@ -218,23 +218,49 @@ class HipSqpSolver:
         if x_traj.ndim == 2:
             x_traj, u_traj, x_init = x_traj[None], u_traj[None], x_init[None]
         B, N = u_traj.shape[0], u_traj.shape[1]
+        self._upload_reference(B, N, x_init, x_traj, u_traj, dt, t0, n_events, event_times, mode_sequence, target_times, target_states,
+                               swing, terrain_height, arm_swing, node_times, _abi.WARM_CALLER)
+
+    def upload_reference_warm(self, x_init, n_nodes, dt, t0, n_events, event_times, mode_sequence, target_times, target_states,
+                              swing, terrain_height=0.0, arm_swing=True, mode="shift", node_times=None):
+        """hsqp_upload_reference with the warm start built on the device (hsqp_reference::warm_start): mode="shift" interpolates the
+        solution resident in the handle onto the new grid and fills the uncovered tail with the weight-compensating input; mode="cold"
+        is that initializer alone (x_k = x_init).  Arguments as upload_reference, without x_traj / u_traj; x_init is [B][58]."""
+        x_init = _c(x_init)
+        if x_init.ndim == 1:
+            x_init = x_init[None]
+        warm = {"shift": _abi.WARM_SHIFT, "cold": _abi.WARM_COLD}[mode]
+        self._upload_reference(x_init.shape[0], int(n_nodes), x_init, None, None, dt, t0, n_events, event_times, mode_sequence, target_times,
+                               target_states, swing, terrain_height, arm_swing, node_times, warm)
+
+    def _upload_reference(self, B, N, x_init, x_traj, u_traj, dt, t0, n_events, event_times, mode_sequence, target_times, target_states,
+                          swing, terrain_height, arm_swing, node_times, warm):
         n_events = np.ascontiguousarray(n_events, dtype=np.int32)
         mode_sequence = np.ascontiguousarray(mode_sequence, dtype=np.int32)
         event_times, target_times, target_states = _c(event_times), _c(target_times), _c(target_states)
-        if event_times.shape[0] != B or mode_sequence.shape != (B, event_times.shape[1] + 1) or target_states.shape != (B, target_times.shape[1], _abi.NX):
+        if event_times.shape[0] != B or mode_sequence.shape != (B, event_times.shape[1] + 1) or target_states.shape != (B, target_times.shape[1], _abi.NX) \
+                or x_init.shape != (B, _abi.NX):
             raise ValueError("inconsistent reference array shapes")
         ip = C.POINTER(C.c_int32)
         dt, grid = self._grid(dt, B, N)
         nt = None if node_times is None else np.ascontiguousarray(np.broadcast_to(np.asarray(node_times, dtype=np.float64), (B, N + 1)))
-        p = _abi.Problem(batch=B, n_nodes=N, dt=dt, x_init=x_init.ctypes.data_as(_dp), x_traj=x_traj.ctypes.data_as(_dp),
-                         u_traj=u_traj.ctypes.data_as(_dp), node_params=None, dt_nodes=None if grid is None else grid.ctypes.data_as(_dp))
+        p = _abi.Problem(batch=B, n_nodes=N, dt=dt, x_init=x_init.ctypes.data_as(_dp), x_traj=None if x_traj is None else x_traj.ctypes.data_as(_dp),
+                         u_traj=None if u_traj is None else u_traj.ctypes.data_as(_dp), node_params=None, dt_nodes=None if grid is None else grid.ctypes.data_as(_dp))
         r = _abi.Reference(batch=B, n_nodes=N, t0=t0, dt=dt, node_times=None if nt is None else nt.ctypes.data_as(_dp), max_events=event_times.shape[1], n_events=n_events.ctypes.data_as(ip),
                            event_times=event_times.ctypes.data_as(_dp), mode_sequence=mode_sequence.ctypes.data_as(ip),
                            n_knots=target_times.shape[1], target_times=target_times.ctypes.data_as(_dp),
                            target_states=target_states.ctypes.data_as(_dp), swing=swing, terrain_height=terrain_height,
-                           arm_swing=1 if arm_swing else 0, reserved=0)
+                           arm_swing=1 if arm_swing else 0, warm_start=warm)
         self._check(self.lib.hsqp_upload_reference(self.h, C.byref(p), C.byref(r)))
         self._shape = (B, N)
+
+    def device_trajectory(self):
+        """The linearisation trajectory resident on the device (HSQP_BLK_X / HSQP_BLK_U): (x[B][N+1][58], u[B][N][35])."""
+        return self.debug_read(_abi.BLK_X), self.debug_read(_abi.BLK_U)
+
+    def stamps(self):
+        """The raw time stamps of the resident grid (HSQP_BLK_STAMPS, [B][N+1]): pre- and post-event node share one."""
+        return self.debug_read(_abi.BLK_STAMPS)
 
     def device_params(self):
         """The per-node parameter table resident on the device ([B][N+1][72])."""
@@ -366,7 +392,7 @@ class HipSqpSolver:
         shapes = {_abi.BLK_AB: (B, N, _abi.NX, _abi.NZ), _abi.BLK_BVEC: (B, N, _abi.NX), _abi.BLK_H: (B, N, _abi.NZ, _abi.NZ),
                   _abi.BLK_G: (B, N, _abi.NZ), _abi.BLK_CDE: (B, N, _abi.NE_MAX, _abi.NZ + 1), _abi.BLK_NE: (B, N),
                   _abi.BLK_COST: (B, N + 1), _abi.BLK_DX: (B, N + 1, _abi.NX), _abi.BLK_DU: (B, N, _abi.NU),
-                  _abi.BLK_FLOW: (B, N, _abi.NX)}
+                  _abi.BLK_FLOW: (B, N, _abi.NX), _abi.BLK_X: (B, N + 1, _abi.NX), _abi.BLK_U: (B, N, _abi.NU), _abi.BLK_STAMPS: (B, N + 1)}
         a = np.zeros(shapes[what], dtype=np.int32 if what == _abi.BLK_NE else np.float64)
         n = self.lib.hsqp_debug_read(self.h, what, a.ctypes.data_as(C.c_void_p), a.nbytes)
         if n < 0:
