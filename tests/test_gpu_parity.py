@@ -928,3 +928,48 @@ def test_no_kernel_reads_lds_it_did_not_write(model, form):
         for key in ("dx", "du", "x", "u", "kkt"):
             assert np.isfinite(a[key]).all(), (form, key)
             assert np.array_equal(a[key], b[key]), (form, key)
+
+
+def test_raw_qp_block_is_refused_when_k_project_skipped_the_joint_rows(model):
+    """Debug block 102 hands out the raw QP record of the last iteration.  Without a KKT report the whole-body serial sweep on the factors has
+    k_project skip the joint rows of A~ / B~ and the lower triangle of Q~ (csrc/hsqp_project.h, QP_A): they keep what was there before, so the
+    block is refused.  After an iteration that wrote them it is returned, and its A~ is the one of the dense stage's handle (which always
+    writes them)."""
+    import ctypes as C
+    from wb_humanoid_mpc_amd.solver import HipSqpSolver
+    B, N = 2, 20
+    problem = make_problem(model, n_nodes=N, batch=B, gait="walk", perturb=True, seed=3)
+
+    def raw_qp(s):
+        size = s.lib.hsqp_debug_read(s.h, 102, None, 0)
+        assert size > 0 and size % (B * N * 8) == 0, size
+        qp = np.full(size // 8, np.nan)
+        assert s.lib.hsqp_debug_read(s.h, 102, qp.ctypes.data_as(C.c_void_p), qp.nbytes) == size
+        return qp.reshape(B * N, -1)
+
+    s = HipSqpSolver(model, max_nodes=N, max_batch=B, riccati="serial")
+    try:
+        assert s.kernel_forms()["ric_fact"]
+        s.upload(*problem)
+        s.iterate(kkt=False)
+        assert s.lib.hsqp_debug_read(s.h, 102, None, 0) == _abi.ERR_BAD_ARG
+        assert "joint rows" in s.lib.hsqp_last_error(s.h).decode()
+        s.iterate(kkt=True)
+        fact = raw_qp(s)
+    finally:
+        s.close()
+    os.environ["HSQP_RICCATI_DENSE"] = "1"
+    try:
+        s = HipSqpSolver(model, max_nodes=N, max_batch=B, riccati="serial")
+    finally:
+        os.environ.pop("HSQP_RICCATI_DENSE", None)
+    try:
+        assert not s.kernel_forms()["ric_fact"]
+        s.upload(*problem)
+        s.iterate(kkt=False)
+        dense = raw_qp(s)
+    finally:
+        s.close()
+    A = slice(0, _abi.NX * _abi.NX)
+    assert np.isfinite(fact[:, A]).all()
+    assert np.array_equal(fact[:, A], dense[:, A])

@@ -883,6 +883,17 @@ __global__ __launch_bounds__(64) void k_perf_trio(const DevModel* __restrict__ d
 }  // namespace
 
 // =================================================================================================
+// a device buffer of the handle: dev_ensure allocates it (grow-only), its destructor frees it.  Reads as the T* it holds.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  operator T*() const { return p; }
+};
+
 struct hsqp_handle {
   hsqp_model_desc md;
   hsqp_settings st;
@@ -895,25 +906,26 @@ struct hsqp_handle {
   int lq_split = 1;                            // node ranges of the limb-lane LQ kernels, each on its own stream (HSQP_LQ_SPLIT in the environment at hsqp_create)
   hipStream_t aux[LQ_SPLIT_MAX - 1] = {};
   hipEvent_t ev_fork = nullptr, ev_join[LQ_SPLIT_MAX - 1] = {};
-  DevModel* d_dm = nullptr;
-  double *d_xinit = nullptr, *d_x = nullptr, *d_u = nullptr, *d_par = nullptr;
-  double *d_rec = nullptr, *d_qp = nullptr, *d_ric = nullptr;
-  double *d_dx = nullptr, *d_du = nullptr, *d_ut = nullptr, *d_xnew = nullptr, *d_unew = nullptr;
-  double* d_fj = nullptr;         // [B][N][NJ] rows 12 .. 34 of Px dx + Pu ut as the factored roll-out forms them (k_step then reads the wrench rows of Px / Pu only)
-  double *d_misc = nullptr, *d_kkt = nullptr, *d_ginf = nullptr;
-  double* d_dt = nullptr;         // [B][N] length of every interval (uniform grids: filled with dt)
+  DevBuf<DevModel> d_dm;
+  DevBuf<double> d_xinit, d_x, d_u, d_par;
+  DevBuf<double> d_rec, d_qp, d_ric;
+  DevBuf<double> d_dx, d_du, d_ut, d_xnew, d_unew;
+  DevBuf<double> d_fj;            // [B][N][NJ] rows 12 .. 34 of Px dx + Pu ut as the factored roll-out forms them (k_step then reads the wrench rows of Px / Pu only)
+  DevBuf<double> d_misc, d_kkt;
+  double* d_ginf = nullptr;       // (inside d_kkt)
+  DevBuf<double> d_dt;            // [B][N] length of every interval (uniform grids: filled with dt)
   std::vector<double> h_dt;       // host copy (debug reads), empty for device-resident uploads
   bool uniform_grid = true, has_events = false;
-  double* d_vf = nullptr;         // [B][N+1][VF_SIZE] value function of the last Riccati sweep (allocated when a KKT check is first asked for)
-  double* d_vf2 = nullptr;        // scan path: value functions of the refinement pass (the KKT check then reads these)
+  DevBuf<double> d_vf;            // [B][N+1][VF_SIZE] value function of the last Riccati sweep (allocated when a KKT check is first asked for)
+  DevBuf<double> d_vf2;           // scan path: value functions of the refinement pass (the KKT check then reads these)
   double* h_gate = nullptr;       // pinned host copy of the gate block [kkt | |g|_inf | scan flags]
   long long scan_fallbacks = 0;   // iterations whose scan result failed the KKT gate and were redone with the serial recursion
-  double* d_acl = nullptr;        // scan path: closed loop [B][N][ACL_SIZE] of every stage for the roll-out (allocated when the scan is first used)
+  DevBuf<double> d_acl;           // scan path: closed loop [B][N][ACL_SIZE] of every stage for the roll-out (allocated when the scan is first used)
   // segmented sweep (allocated when first used): gains of the J = 0 recursions, (L^-1)^T of every stage, (J, s) at the segment starts, zeros
-  double *d_ric2 = nullptr, *d_linv = nullptr, *d_vf0 = nullptr, *d_zero = nullptr;
-  size_t vf0_capacity = 0;
-  int seg_backoff = 0, seg_backoff_len = 0;   // after a rejected gated sweep (scan or two-level) the next seg_backoff iterations go straight to the serial recursion (doubling, <= 64);
-                                              // state of the AUTOMATIC sweep choice only (a sweep forced by a flag is always attempted), reset by every upload
+  DevBuf<double> d_ric2, d_linv, d_vf0, d_zero;
+  bool qp_joint_rows = false;                 // the last k_project wrote the joint rows of A~ / B~ and all of Q~ (joint_rows, hsqp_iterate_device): debug block 102
+  int seg_backoff = 0, seg_backoff_len = 0;   // after a rejected gated sweep the next seg_backoff iterations go straight to the serial recursion (doubling, <= 64);
+                                              // state of the AUTOMATIC sweep choice only (choose_sweep), reset by every upload
   bool backoff_persistent = false;            // hsqp_set_scan_backoff_persistent: uploads of the same (B, N) keep the back-off
   long long backoff_iterations = 0;           // iterations that ran the serial recursion because of the back-off (hsqp_scan_backoffs)
   bool seg_debug = false;                     // HSQP_SEG_DEBUG in the environment at hsqp_create
@@ -926,28 +938,26 @@ struct hsqp_handle {
   bool lq_limb = false;                       // whole-body LQ approximation on limb lanes (hsqp_lql.h: k_lq_limb + k_lq_rows + k_lq_chain) instead of the phase form k_lq<true> (HSQP_LQ_PHASE_FORM / HSQP_LQ_LIMB_FORM in the environment at hsqp_create force either)
   bool ric_fact = false;                      // whole-body serial sweep on the factors of [A~ | B~] (hsqp_riccati_fact.h: k_riccati_fact; HSQP_RICCATI_DENSE in the environment at hsqp_create: the dense stage k_riccati<58>, for A/B runs)
   bool value_quad = false;                    // whole-body value pass on quads of lanes (hsqp_lqv.h): the tree has at most four limbs (HSQP_VALUE_PHASE_FORM in the environment at hsqp_create: the phase form, for A/B runs)
-  hsqp_perf *d_perf_before = nullptr, *d_perf_after = nullptr;
-  int* d_status = nullptr;
+  DevBuf<hsqp_perf> d_perf_before, d_perf_after;
+  DevBuf<int> d_status;
   int* d_scanst = nullptr;   // flags of the scan kernels (bad pivot, rank-deficient D, failed Lam) of the current attempt: part of the gate, behind d_ginf
-  double* d_stepinfo = nullptr;   // [B][N][4] per-node {armijo, |dx|^2, |du|^2}
-  LsState* d_ls = nullptr;
-  int* d_counts = nullptr;
+  DevBuf<double> d_stepinfo;      // [B][N][4] per-node {armijo, |dx|^2, |du|^2}
+  DevBuf<LsState> d_ls;
+  DevBuf<int> d_counts;
   hsqp_linesearch_settings ls_settings;
   std::vector<LsState> h_ls;                  // host copies for HSQP_ITER_UNTIL_CONVERGED (reused across iterations and calls)
   std::vector<hsqp_perf> h_perf_before;
-  double* d_el[2] = {nullptr, nullptr};   // scan elements (allocated when the parallel-in-time sweep is first used)
-  size_t el_capacity = 0;                 // in doubles per buffer
-  void* d_stage = nullptr;        // grow-only staging area for the small per-call inputs (reference, policy queries)
-  size_t stage_bytes = 0;
+  DevBuf<double> d_el[2];         // scan elements (allocated when the parallel-in-time sweep is first used)
+  DevBuf<char> d_stage;           // staging area for the small per-call inputs (reference, policy queries; 256-byte aligned carving by the callers)
   bool ls_ran = false;
-  long long* d_prof = nullptr;   // [4][128] phase-profile ticks (k_lq<true>, k_project, k_riccati, k_lq<false>)
+  DevBuf<long long> d_prof;       // [4][128] phase-profile ticks (k_lq<true>, k_project, k_riccati, k_lq<false>)
   int B = 0, N = 0;
   double dt = 0.0;
   bool have_problem = false, have_solution = false;
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
   // with non-decreasing stamps
-  double* d_stamps[2] = {nullptr, nullptr};
+  DevBuf<double> d_stamps[2];
   int stamps_cur = 0;
   bool have_stamps = false;
   double kernel_ms[5] = {0, 0, 0, 0, 0};
@@ -959,7 +969,24 @@ struct hsqp_handle {
 
 static std::string g_create_error;
 
-static void poison_hbm(const hsqp_handle* h, void* p, size_t bytes) { if (h->poison_hbm && p) (void)hipMemset(p, 0xFF, bytes); }
+// makes sure `buf` holds at least `bytes` (grow-only: a larger request replaces the buffer, the contents are not kept).  A new buffer starts as
+// 0xFF bytes under HSQP_POISON_HBM.  On failure the buffer is empty and h->err names it.
+template <class T>
+static int dev_ensure(hsqp_handle* h, DevBuf<T>& buf, size_t bytes, const char* what) {
+  if (buf.p && bytes <= buf.bytes) return HSQP_OK;
+  if (buf.p) (void)hipFree(buf.p);
+  buf.p = nullptr; buf.bytes = 0;
+  if (hipMalloc(&buf.p, bytes) != hipSuccess) { buf.p = nullptr; h->err = std::string("hipMalloc failed (") + what + ", " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
+  if (h->poison_hbm) (void)hipMemset(buf.p, 0xFF, bytes);
+  buf.bytes = bytes;
+  return HSQP_OK;
+}
+#define DEV_ENSURE(buf, bytes, what) do { const int rc_ = dev_ensure(h, (buf), (bytes), (what)); if (rc_ != HSQP_OK) return rc_; } while (0)
+
+// the gate block [kkt (2 per instance) | |g|_inf | flags of the scan kernels] of a handle for max_batch instances: d_kkt, h_gate
+static size_t gate_block_bytes(size_t max_batch) { return max_batch * 3 * 8 + ((max_batch * sizeof(int) + 7) / 8) * 8; }
+// [max_batch][max_nodes + 1][VF_SIZE]: d_vf, d_vf2
+static size_t vf_bytes(const hsqp_handle* h) { return (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8; }
 
 #define HCHECK(call)                                                                                   \
   do {                                                                                                 \
@@ -970,17 +997,6 @@ static void poison_hbm(const hsqp_handle* h, void* p, size_t bytes) { if (h->poi
     }                                                                                                  \
   } while (0)
 
-// grow-only device staging area of the handle (256-byte aligned carving by the callers)
-static void* stage_area(hsqp_handle* h, size_t bytes) {
-  if (bytes > h->stage_bytes) {
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    h->d_stage = nullptr; h->stage_bytes = 0;
-    if (hipMalloc(&h->d_stage, bytes) != hipSuccess) return nullptr;
-    poison_hbm(h, h->d_stage, bytes);
-    h->stage_bytes = bytes;
-  }
-  return h->d_stage;
-}
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // (the KKT gate of the parallel-in-time sweep: scan_gate_accepts, hsqp_scan.h)
@@ -995,33 +1011,16 @@ template <int n>
 static int launch_scan(hsqp_handle* h, int B, int N, bool want_kkt, int refinements) {
   constexpr int SZ = ScanEl<n>::SIZE;
   const int nodes = B * N;
-  const size_t need = (size_t)B * (N + 1) * SZ;
-  if (need > h->el_capacity) {
-    for (auto& p : h->d_el) { if (p) (void)hipFree(p); p = nullptr; }
-    h->el_capacity = 0;
-    for (auto& p : h->d_el) {
-      if (hipMalloc(&p, need * 8) != hipSuccess) { p = nullptr; h->err = "hipMalloc failed (scan elements)"; return HSQP_ERR_OOM; }
-      poison_hbm(h, p, need * 8);
-    }
-    h->el_capacity = need;
-  }
+  for (auto& el : h->d_el) DEV_ENSURE(el, (size_t)B * (N + 1) * SZ * 8, "scan elements");
   HSQP_LAUNCH(k_scan_init<n>, dim3(B * (N + 1)), dim3(SCAN_INIT_THREADS), sizeof(ScanInitWS<n>), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, N, h->d_el[0], h->d_scanst);
   int cur = 0;
   for (int d = 1; d < N + 1; d *= 2) {
     HSQP_LAUNCH(k_scan_combine<n>, dim3(B * (N + 1)), dim3(SCAN_COMB_THREADS), sizeof(ScanCombWS<n>), h->stream, h->d_el[cur], h->d_el[1 - cur], N, d, h->d_scanst, h->d_prof + 256);
     cur = 1 - cur;
   }
-  for (double** pv : {&h->d_vf, &h->d_vf2})
-    if (!*pv) {
-      const size_t bytes = (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8;
-      if (hipMalloc(pv, bytes) != hipSuccess) { *pv = nullptr; h->err = "hipMalloc failed (value functions of the scan, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-      poison_hbm(h, *pv, bytes);
-    }
-  if (!h->d_acl) {
-    const size_t bytes = (size_t)h->st.max_batch * h->st.max_nodes * ACL_SIZE<n> * 8;
-    if (hipMalloc(&h->d_acl, bytes) != hipSuccess) { h->d_acl = nullptr; h->err = "hipMalloc failed (closed loop of the scan path, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-    poison_hbm(h, h->d_acl, bytes);
-  }
+  DEV_ENSURE(h->d_vf, vf_bytes(h), "value functions");
+  DEV_ENSURE(h->d_vf2, vf_bytes(h), "value functions of the gated sweep");
+  DEV_ENSURE(h->d_acl, (size_t)h->st.max_batch * h->st.max_nodes * ACL_SIZE<n> * 8, "closed loop of the scan path");
   // the gains passes ping-pong between the two value-function buffers; the LAST pass writes d_vf2 (what the KKT check reads) and the closed loop
   double* vbuf[2] = {(refinements & 1) ? h->d_vf : h->d_vf2, (refinements & 1) ? h->d_vf2 : h->d_vf};
   for (int pass = 0; pass <= refinements; ++pass) {
@@ -1053,35 +1052,17 @@ static int segment_count(const hsqp_handle* h, int B, int N) {
 template <int n>
 static int launch_segmented(hsqp_handle* h, int B, int N, int P, bool want_vf) {
   constexpr int SZ = ScanEl<n>::SIZE;
-  const size_t need = (size_t)B * (P + 1) * SZ;
-  if (need > h->el_capacity) {
-    for (auto& p : h->d_el) { if (p) (void)hipFree(p); p = nullptr; }
-    h->el_capacity = 0;
-    for (auto& p : h->d_el) {
-      if (hipMalloc(&p, need * 8) != hipSuccess) { p = nullptr; h->err = "hipMalloc failed (segment elements)"; return HSQP_ERR_OOM; }
-      poison_hbm(h, p, need * 8);
-    }
-    h->el_capacity = need;
-  }
+  for (auto& el : h->d_el) DEV_ENSURE(el, (size_t)B * (P + 1) * SZ * 8, "segment elements");
   const size_t BN = (size_t)h->st.max_batch * h->st.max_nodes;
-  if (!h->d_ric2 && hipMalloc(&h->d_ric2, BN * RIC_SIZE * 8) != hipSuccess) { h->d_ric2 = nullptr; h->err = "hipMalloc failed (segmented sweep: gains)"; return HSQP_ERR_OOM; }
-  if (!h->d_linv && hipMalloc(&h->d_linv, BN * LDB * LDB * 8) != hipSuccess) { h->d_linv = nullptr; h->err = "hipMalloc failed (segmented sweep: factors)"; return HSQP_ERR_OOM; }
+  DEV_ENSURE(h->d_ric2, BN * RIC_SIZE * 8, "segmented sweep: gains");
+  DEV_ENSURE(h->d_linv, BN * LDB * LDB * 8, "segmented sweep: factors");
   if (!h->d_zero) {
-    if (hipMalloc(&h->d_zero, (NX * NX + NX) * 8) != hipSuccess) { h->d_zero = nullptr; h->err = "hipMalloc failed"; return HSQP_ERR_OOM; }
+    DEV_ENSURE(h->d_zero, (NX * NX + NX) * 8, "segmented sweep: zeros");
     if (hipMemsetAsync(h->d_zero, 0, (NX * NX + NX) * 8, h->stream) != hipSuccess) { h->err = "memset failed"; return HSQP_ERR_HIP; }
   }
-  if ((size_t)B * P > h->vf0_capacity) {
-    if (h->d_vf0) (void)hipFree(h->d_vf0);
-    h->d_vf0 = nullptr; h->vf0_capacity = 0;
-    if (hipMalloc(&h->d_vf0, (size_t)B * P * VF_SIZE * 8) != hipSuccess) { h->d_vf0 = nullptr; h->err = "hipMalloc failed (segmented sweep: boundary value functions)"; return HSQP_ERR_OOM; }
-    poison_hbm(h, h->d_vf0, (size_t)B * P * VF_SIZE * 8);
-    h->vf0_capacity = (size_t)B * P;
-  }
-  if (!h->d_vf2) {   // (the gate needs the value functions of the boundary stages' nodes; want_vf: of every node, for the KKT report)
-    const size_t bytes = (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8;
-    if (hipMalloc(&h->d_vf2, bytes) != hipSuccess) { h->d_vf2 = nullptr; h->err = "hipMalloc failed (value functions of the segmented sweep, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-    poison_hbm(h, h->d_vf2, bytes);
-  }
+  DEV_ENSURE(h->d_vf0, (size_t)B * P * VF_SIZE * 8, "segmented sweep: boundary value functions");
+  // (the gate needs the value functions of the boundary stages' nodes; want_vf: of every node, for the KKT report)
+  DEV_ENSURE(h->d_vf2, vf_bytes(h), "value functions of the gated sweep");
   const int segs = B * P;
   HSQP_LAUNCH(k_seg_elem_ric<n>, dim3(segs), dim3(RIC_THREADS), sizeof(RicWS), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, (const double*)h->d_zero, h->d_ric2,
                      h->d_linv, h->d_vf0, N, P, h->d_scanst);
@@ -1124,11 +1105,6 @@ const char* hsqp_last_error(const hsqp_handle* h) { return h ? h->err.c_str() : 
 void hsqp_destroy(hsqp_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  void* bufs[] = {h->d_dm, h->d_xinit, h->d_x, h->d_u, h->d_par, h->d_rec, h->d_qp, h->d_ric, h->d_dx, h->d_du, h->d_ut, h->d_fj, h->d_xnew,
-                  h->d_unew, h->d_misc, h->d_kkt, h->d_dt, h->d_perf_before, h->d_perf_after, h->d_status, h->d_prof, h->d_stepinfo, h->d_ls, h->d_counts, h->d_vf, h->d_stage, h->d_stamps[0], h->d_stamps[1],
-                  h->d_el[0], h->d_el[1], h->d_vf2, h->d_acl, h->d_ric2, h->d_linv, h->d_vf0, h->d_zero};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
   if (h->h_gate) (void)hipHostFree(h->h_gate);
   for (auto& e : h->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1138,7 +1114,7 @@ void hsqp_destroy(hsqp_handle* h) {
   for (auto& st : h->aux)
     if (st) (void)hipStreamDestroy(st);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // (the device buffers free themselves: DevBuf)
 }
 
 void hsqp_linesearch_defaults(hsqp_linesearch_settings* s) {
@@ -1233,57 +1209,48 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
         return fail(HSQP_ERR_HIP, "hipStreamCreate failed");
   }
   const size_t B = settings->max_batch, N = settings->max_nodes;
-  struct Alloc { void** p; size_t bytes; };
-  const Alloc allocs[] = {
-      {(void**)&h->d_dm, sizeof(DevModel)},
-      {(void**)&h->d_xinit, B * NX * 8}, {(void**)&h->d_x, B * (N + 1) * NX * 8}, {(void**)&h->d_u, B * N * NU * 8},
-      {(void**)&h->d_par, B * (N + 1) * NP * 8}, {(void**)&h->d_rec, B * N * (size_t)REC_SIZE * 8},
-      {(void**)&h->d_qp, B * N * (size_t)QP_SIZE * 8}, {(void**)&h->d_ric, B * N * (size_t)RIC_SIZE * 8},
-      {(void**)&h->d_dx, B * (N + 1) * NX * 8}, {(void**)&h->d_du, B * N * NU * 8}, {(void**)&h->d_ut, B * N * NUT * 8}, {(void**)&h->d_fj, B * N * NJ * 8},
-      {(void**)&h->d_xnew, B * (N + 1) * NX * 8}, {(void**)&h->d_unew, B * N * NU * 8}, {(void**)&h->d_misc, B * N * 8 * 8},
-      {(void**)&h->d_kkt, B * 3 * 8 + ((B * sizeof(int) + 7) / 8) * 8}, {(void**)&h->d_dt, B * N * 8}, {(void**)&h->d_perf_before, B * sizeof(hsqp_perf)}, {(void**)&h->d_perf_after, B * sizeof(hsqp_perf)},
-      {(void**)&h->d_status, B * sizeof(int)}, {(void**)&h->d_prof, 4 * 128 * sizeof(long long)},
-      {(void**)&h->d_stepinfo, B * N * 4 * 8}, {(void**)&h->d_ls, B * sizeof(LsState)}, {(void**)&h->d_counts, 2 * sizeof(int)},
-      {(void**)&h->d_stamps[0], B * (N + 1) * 8}, {(void**)&h->d_stamps[1], B * (N + 1) * 8}};
-  for (const Alloc& a : allocs) {
-    if (hipMalloc(a.p, a.bytes) != hipSuccess) return fail(HSQP_ERR_OOM, "hipMalloc failed (" + std::to_string(a.bytes) + " bytes)");
-    poison_hbm(h, *a.p, a.bytes);
-  }
-  if (hipHostMalloc((void**)&h->h_gate, B * 3 * 8 + ((B * sizeof(int) + 7) / 8) * 8) != hipSuccess) { h->h_gate = nullptr; return fail(HSQP_ERR_OOM, "hipHostMalloc failed (gate block)"); }
+  int rc = HSQP_OK;
+  auto alloc = [&](auto& buf, size_t bytes, const char* what) { if (rc == HSQP_OK) rc = dev_ensure(h, buf, bytes, what); };
+  alloc(h->d_dm, sizeof(DevModel), "model"); alloc(h->d_xinit, B * NX * 8, "x_init"); alloc(h->d_x, B * (N + 1) * NX * 8, "x"); alloc(h->d_u, B * N * NU * 8, "u");
+  alloc(h->d_par, B * (N + 1) * NP * 8, "node parameters"); alloc(h->d_rec, B * N * (size_t)REC_SIZE * 8, "LQ record");
+  alloc(h->d_qp, B * N * (size_t)QP_SIZE * 8, "QP record"); alloc(h->d_ric, B * N * (size_t)RIC_SIZE * 8, "gains"); alloc(h->d_dx, B * (N + 1) * NX * 8, "dx");
+  alloc(h->d_du, B * N * NU * 8, "du"); alloc(h->d_ut, B * N * NUT * 8, "ut"); alloc(h->d_fj, B * N * NJ * 8, "joint rows of the roll-out");
+  alloc(h->d_xnew, B * (N + 1) * NX * 8, "x_new"); alloc(h->d_unew, B * N * NU * 8, "u_new"); alloc(h->d_misc, B * N * 8 * 8, "value-pass terms");
+  alloc(h->d_kkt, gate_block_bytes(B), "gate block"); alloc(h->d_dt, B * N * 8, "interval lengths"); alloc(h->d_perf_before, B * sizeof(hsqp_perf), "perf_before");
+  alloc(h->d_perf_after, B * sizeof(hsqp_perf), "perf_after"); alloc(h->d_status, B * sizeof(int), "status"); alloc(h->d_prof, 4 * 128 * sizeof(long long), "phase profile");
+  alloc(h->d_stepinfo, B * N * 4 * 8, "step terms"); alloc(h->d_ls, B * sizeof(LsState), "line-search state"); alloc(h->d_counts, 2 * sizeof(int), "line-search counters");
+  alloc(h->d_stamps[0], B * (N + 1) * 8, "time stamps"); alloc(h->d_stamps[1], B * (N + 1) * 8, "time stamps");
+  if (rc != HSQP_OK) return fail(rc, h->err);
+  if (hipHostMalloc((void**)&h->h_gate, gate_block_bytes(B)) != hipSuccess) { h->h_gate = nullptr; return fail(HSQP_ERR_OOM, "hipHostMalloc failed (gate block)"); }
   h->d_ginf = h->d_kkt + 2 * B;   // one block [kkt (2 per instance of max_batch) | |g|_inf | flags of the scan kernels]: one memset, one read-back for the scan's gate
   h->d_scanst = reinterpret_cast<int*>(h->d_kkt + 3 * B);
   if (hipMemcpy(h->d_dm, &h->hdm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) return fail(HSQP_ERR_HIP, "model upload failed");
   if (hipMemset(h->d_prof, 0, 4 * 128 * sizeof(long long)) != hipSuccess) return fail(HSQP_ERR_HIP, "memset failed");
   // the limb-lane LQ kernel never writes record entries that are zero for every state (hsqp_lql.h)
   if (hipMemset(h->d_rec, 0, B * N * (size_t)REC_SIZE * 8) != hipSuccess) return fail(HSQP_ERR_HIP, "memset failed");
-  // the kernels use up to ~158 KB of dynamic LDS (gfx950: 160 KB per workgroup)
-  hipError_t a1 = hipFuncSetAttribute((const void*)k_lq<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LqWS));
   if (h->poison_lds) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) h->poison_blocks = 2 * prop.multiProcessorCount;
-    if (a1 == hipSuccess) a1 = hipFuncSetAttribute((const void*)k_poison_lds, hipFuncAttributeMaxDynamicSharedMemorySize, POISON_LDS_BYTES);
   }
-  hipError_t a2 = hipFuncSetAttribute((const void*)k_lq<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LqWST<false>));
-  if (a2 == hipSuccess) a2 = hipFuncSetAttribute((const void*)k_step_value, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LqWST<false>));
-  if (a2 == hipSuccess) a2 = hipFuncSetAttribute((const void*)k_lq_cent2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(CentWST<true>));
-  hipError_t a3 = hipFuncSetAttribute((const void*)k_project, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ProjWS));
-  hipError_t a4 = hipFuncSetAttribute((const void*)k_riccati<NX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicWS));
-  if (a4 == hipSuccess) a4 = hipFuncSetAttribute((const void*)k_riccati_fact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicFWS));
-  hipError_t a5 = hipFuncSetAttribute((const void*)k_riccati<CNX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicWS));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_init<CNX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ScanInitWS<CNX>));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_combine<CNX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ScanCombWS<CNX>));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_gains<CNX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicWS));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_forward<CNX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicWS));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_init<NX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ScanInitWS<NX>));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_combine<NX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ScanCombWS<NX>));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_gains<NX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicWS));
-  if (a5 == hipSuccess) a5 = hipFuncSetAttribute((const void*)k_scan_forward<NX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicWS));
-  for (const void* f : {(const void*)k_seg_elem_ric<NX>, (const void*)k_seg_elem_ric<CNX>, (const void*)k_seg_riccati<NX>, (const void*)k_seg_riccati<CNX>,
-                        (const void*)k_ric_forward<NX>, (const void*)k_ric_forward<CNX>})
-    if (a5 == hipSuccess) a5 = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RicWS));
-  for (const void* f : {(const void*)k_seg_accumulate<NX>, (const void*)k_seg_accumulate<CNX>})
-    if (a5 == hipSuccess) a5 = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SegAccWS));
-  if (a1 != hipSuccess || a2 != hipSuccess || a3 != hipSuccess || a4 != hipSuccess || a5 != hipSuccess) return fail(HSQP_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  // the kernels use up to ~158 KB of dynamic LDS (gfx950: 160 KB per workgroup)
+  const struct { const void* f; int bytes; } lds_limits[] = {
+      {(const void*)k_lq<true>, (int)sizeof(LqWS)},
+      {h->poison_lds ? (const void*)k_poison_lds : nullptr, POISON_LDS_BYTES},
+      {(const void*)k_lq<false>, (int)sizeof(LqWST<false>)}, {(const void*)k_step_value, (int)sizeof(LqWST<false>)},
+      {(const void*)k_lq_cent2, (int)sizeof(CentWST<true>)},
+      {(const void*)k_project, (int)sizeof(ProjWS)},
+      {(const void*)k_riccati<NX>, (int)sizeof(RicWS)}, {(const void*)k_riccati_fact, (int)sizeof(RicFWS)}, {(const void*)k_riccati<CNX>, (int)sizeof(RicWS)},
+      {(const void*)k_scan_init<CNX>, (int)sizeof(ScanInitWS<CNX>)}, {(const void*)k_scan_combine<CNX>, (int)sizeof(ScanCombWS<CNX>)},
+      {(const void*)k_scan_gains<CNX>, (int)sizeof(RicWS)}, {(const void*)k_scan_forward<CNX>, (int)sizeof(RicWS)},
+      {(const void*)k_scan_init<NX>, (int)sizeof(ScanInitWS<NX>)}, {(const void*)k_scan_combine<NX>, (int)sizeof(ScanCombWS<NX>)},
+      {(const void*)k_scan_gains<NX>, (int)sizeof(RicWS)}, {(const void*)k_scan_forward<NX>, (int)sizeof(RicWS)},
+      {(const void*)k_seg_elem_ric<NX>, (int)sizeof(RicWS)}, {(const void*)k_seg_elem_ric<CNX>, (int)sizeof(RicWS)},
+      {(const void*)k_seg_riccati<NX>, (int)sizeof(RicWS)}, {(const void*)k_seg_riccati<CNX>, (int)sizeof(RicWS)},
+      {(const void*)k_ric_forward<NX>, (int)sizeof(RicWS)}, {(const void*)k_ric_forward<CNX>, (int)sizeof(RicWS)},
+      {(const void*)k_seg_accumulate<NX>, (int)sizeof(SegAccWS)}, {(const void*)k_seg_accumulate<CNX>, (int)sizeof(SegAccWS)}};
+  for (const auto& k : lds_limits)
+    if (k.f && hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes) != hipSuccess)
+      return fail(HSQP_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   *out = h;
   g_create_error.clear();
   return HSQP_OK;
@@ -1336,13 +1303,32 @@ static int set_grid(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   return HSQP_OK;
 }
 
+// the first failing call of a sequence goes to h->err and rc; the later calls are still made, their results ignored
+struct StickyError {
+  hsqp_handle* h; int rc = HSQP_OK;
+  void operator()(hipError_t e, const char* what) { if (rc == HSQP_OK && e != hipSuccess) { h->err = std::string(what) + ": " + hipGetErrorString(e); rc = HSQP_ERR_HIP; } }
+};
+
+// the problem fits the handle (hsqp_settings::max_batch, max_nodes) and has a grid
+static bool fits_handle(hsqp_handle* h, const hsqp_problem* p) {
+  const bool ok = p->batch >= 1 && p->batch <= h->st.max_batch && p->n_nodes >= 1 && p->n_nodes <= h->st.max_nodes && (p->dt_nodes || p->dt > 0.0);
+  if (!ok) h->err = "batch / n_nodes outside the handle's capacity, or dt <= 0";
+  return ok;
+}
+
+// the uploaded problem is now the resident one (no solution yet).  The gate's history belongs to the problem that produced it: the back-off
+// restarts unless the caller asked to keep it across uploads of the same shape (receding-horizon callers)
+static void commit_problem(hsqp_handle* h, const hsqp_problem* p, bool have_stamps) {
+  const bool same_shape = h->B == p->batch && h->N == p->n_nodes;
+  h->B = p->batch; h->N = p->n_nodes; h->dt = p->dt;
+  h->have_problem = true; h->have_solution = false; h->have_stamps = have_stamps;
+  if (!(h->backoff_persistent && same_shape)) { h->seg_backoff = 0; h->seg_backoff_len = 0; }
+}
+
 static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   if (!h) return HSQP_ERR_BAD_ARG;
   if (!p || !p->x_init || !p->x_traj || !p->u_traj || !p->node_params) { h->err = "null problem pointer"; return HSQP_ERR_BAD_ARG; }
-  if (p->batch < 1 || p->batch > h->st.max_batch || p->n_nodes < 1 || p->n_nodes > h->st.max_nodes || (!p->dt_nodes && !(p->dt > 0.0))) {
-    h->err = "batch / n_nodes outside the handle's capacity, or dt <= 0";
-    return HSQP_ERR_BAD_ARG;
-  }
+  if (!fits_handle(h, p)) return HSQP_ERR_BAD_ARG;
   if (!device_src && !padding_is_zero(h, p)) return HSQP_ERR_BAD_ARG;   // device-resident inputs: the caller guarantees the zero padding
   HCHECK(hipSetDevice(h->device));
   const size_t B = p->batch, N = p->n_nodes;
@@ -1355,10 +1341,7 @@ static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   HCHECK(hipMemcpyAsync(h->d_u, p->u_traj, B * N * NU * 8, kind, h->stream));
   HCHECK(hipMemcpyAsync(h->d_par, p->node_params, B * (N + 1) * NP * 8, kind, h->stream));
   HCHECK(hipStreamSynchronize(h->stream));
-  const bool same_shape = h->B == p->batch && h->N == p->n_nodes;
-  h->B = p->batch; h->N = p->n_nodes; h->dt = p->dt;
-  h->have_problem = true; h->have_solution = false;
-  if (!(h->backoff_persistent && same_shape)) { h->seg_backoff = 0; h->seg_backoff_len = 0; }   // the gate's history belongs to the problem that produced it (receding-horizon callers opt out)
+  commit_problem(h, p, false);
   return HSQP_OK;
 }
 
@@ -1391,10 +1374,7 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
     h->err = warm == HSQP_WARM_CALLER ? "null problem / reference pointer" : "warm_start SHIFT / COLD: hsqp_problem::x_traj and u_traj must be NULL";
     return HSQP_ERR_BAD_ARG;
   }
-  if (p->batch < 1 || p->batch > h->st.max_batch || p->n_nodes < 1 || p->n_nodes > h->st.max_nodes || (!p->dt_nodes && !(p->dt > 0.0))) {
-    h->err = "batch / n_nodes outside the handle's capacity, or dt <= 0";
-    return HSQP_ERR_BAD_ARG;
-  }
+  if (!fits_handle(h, p)) return HSQP_ERR_BAD_ARG;
   if (r->batch != p->batch || r->n_nodes != p->n_nodes || (!r->node_times && r->dt != p->dt) || r->max_events < 1 || r->n_knots < 1) {
     h->err = "reference does not match the problem (batch, n_nodes, dt) or is empty";
     return HSQP_ERR_BAD_ARG;
@@ -1427,8 +1407,8 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   const size_t o_ne = 0, o_seq = o_ne + align256(B * 4), o_bad = o_seq + align256(B * (E + 1) * 4), o_ev = o_bad + 256,
                o_tt = o_ev + align256(B * E * 8), o_ts = o_tt + align256(B * K * 8), o_nt = o_ts + align256(B * K * NX * 8),
                total = o_nt + align256(r->node_times ? B * (N + 1) * 8 : 0);
-  char* base = static_cast<char*>(stage_area(h, total));
-  if (!base) { h->err = "hipMalloc failed (reference staging)"; return HSQP_ERR_OOM; }
+  DEV_ENSURE(h->d_stage, total, "reference staging");
+  char* base = h->d_stage;
   int* d_ne = reinterpret_cast<int*>(base + o_ne);
   int* d_seq = reinterpret_cast<int*>(base + o_seq);
   int* d_bad = reinterpret_cast<int*>(base + o_bad);
@@ -1436,11 +1416,9 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   double* d_tt = reinterpret_cast<double*>(base + o_tt);
   double* d_ts = reinterpret_cast<double*>(base + o_ts);
   double* d_nt = r->node_times ? reinterpret_cast<double*>(base + o_nt) : nullptr;
-  auto release = []() {};
   h->have_problem = false; h->have_solution = false; h->have_stamps = false;   // a failure below leaves no half-uploaded problem behind
-  int rc = set_grid(h, p, false);
-  if (rc != HSQP_OK) return rc;
-  auto step = [&](hipError_t e, const char* what) { if (rc == HSQP_OK && e != hipSuccess) { h->err = std::string(what) + ": " + hipGetErrorString(e); rc = HSQP_ERR_HIP; } };
+  { const int rc = set_grid(h, p, false); if (rc != HSQP_OK) return rc; }
+  StickyError step{h};
   if (d_nt) step(hipMemcpyAsync(d_nt, r->node_times, B * (N + 1) * 8, hipMemcpyHostToDevice, h->stream), "upload node_times");
   step(hipMemcpyAsync(d_ne, r->n_events, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
   step(hipMemcpyAsync(d_seq, r->mode_sequence, B * (E + 1) * 4, hipMemcpyHostToDevice, h->stream), "upload mode_sequence");
@@ -1453,7 +1431,7 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
     step(hipMemcpyAsync(h->d_x, p->x_traj, B * (N + 1) * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
     step(hipMemcpyAsync(h->d_u, p->u_traj, B * N * NU * 8, hipMemcpyHostToDevice, h->stream), "upload u");
   }
-  if (rc == HSQP_OK) {
+  if (step.rc == HSQP_OK) {
     const int total = (int)(B * (N + 1));
     HSQP_LAUNCH(k_params, dim3((total + 63) / 64), dim3(64), 0, h->stream, h->d_dm, r->swing, r->terrain_height, r->arm_swing, (int)E, d_ne, d_ev, d_seq,
                        (int)K, d_tt, d_ts, r->t0, r->dt, (const double*)d_nt, (int)N, (int)B, h->d_par, d_bad);
@@ -1461,7 +1439,7 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
       HSQP_LAUNCH(k_params_cent_torso, dim3(total), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_par);
     step(hipGetLastError(), "k_params");
   }
-  if (rc == HSQP_OK) {   // the grid's raw stamps (every mode) and the device-built warm start (SHIFT / COLD), after k_params wrote the contact flags
+  if (step.rc == HSQP_OK) {   // the grid's raw stamps (every mode) and the device-built warm start (SHIFT / COLD), after k_params wrote the contact flags
     WarmArgs w{};
     w.mode = warm; w.B = (int)B; w.N = (int)N; w.N_prev = warm == HSQP_WARM_SHIFT ? N_prev : 0; w.cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
     w.t0 = r->t0; w.dt = r->dt; w.total_mass = h->hdm.total_mass;
@@ -1475,15 +1453,49 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   int bad = 0;
   step(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream), "download status");
   step(hipStreamSynchronize(h->stream), "sync");
-  release();
-  if (rc != HSQP_OK) return rc;
+  if (step.rc != HSQP_OK) return step.rc;
   if (bad) { h->err = "a swing phase has no lift-off / touch-down inside the mode schedule"; return HSQP_ERR_BAD_ARG; }
-  const bool same_shape = h->B == p->batch && h->N == p->n_nodes;
-  h->B = p->batch; h->N = p->n_nodes; h->dt = p->dt;
-  h->have_problem = true; h->have_solution = false;
-  h->stamps_cur = 1 - h->stamps_cur; h->have_stamps = sorted;
-  if (!(h->backoff_persistent && same_shape)) { h->seg_backoff = 0; h->seg_backoff_len = 0; }
+  h->stamps_cur = 1 - h->stamps_cur;
+  commit_problem(h, p, sorted);
   return HSQP_OK;
+}
+
+// The backward sweep of an iteration: serial recursion, or — one or two instances on a long horizon, or on request — the associative scan over the
+// stages (hsqp_scan.h), or on request the two-level sweep with P segments per instance (hsqp_segment.h).  The scan inverts I + C1 J2 of partial
+// horizons (condition number up to 1e5 centroidal, 1e9 whole-body): on the QPs of a cold start or of a tracking MPC it reproduces the serial
+// recursion to 1e-11 of the step's scale, on a far-from-feasible line-search iterate it can lose five digits.  Both are therefore GATED: the KKT
+// residual of the QP is evaluated (k_kkt, one small kernel + one 3 B-double read-back) and, if a residual exceeds the gate (scan_gate_accepts,
+// hsqp_scan.h), the iteration is redone with the serial recursion (hsqp_scan_fallbacks counts these).
+// A problem class whose sweeps keep failing the gate (badly scaled QPs: |S| ~ 1e6 on perturbed centroidal batches) would pay sweep + fallback every
+// iteration — a rejected scan costs scan + serial sweep (0.55 + 1.45 ms at one whole-body instance), and the iterates that fail the gate, far-from-
+// feasible line-search iterates, come in runs: after a rejection the handle backs off to the serial recursion for 1, 3, 7, .. 63 iterations before
+// it tries again.  The back-off is part of the automatic choice only: a sweep the caller FORCED by a flag (the two-level sweep always is) is
+// attempted every iteration, so forced timings and the parity tests of the forced sweeps never silently measure the serial recursion.
+struct Sweep { enum Kind { SERIAL, SCAN, SEGMENTED } kind; int P; };   // P: segments per instance (SEGMENTED)
+static Sweep choose_sweep(hsqp_handle* h, int B, int N) {
+  const int flags = h->st.flags;
+  if (flags & HSQP_FLAG_SEGMENTED_RICCATI) {
+    const int P = segment_count(h, B, N);
+    return P > 0 ? Sweep{Sweep::SEGMENTED, P} : Sweep{Sweep::SERIAL, 0};
+  }
+  if (flags & HSQP_FLAG_PARALLEL_RICCATI) return {Sweep::SCAN, 0};
+  if ((flags & HSQP_FLAG_SERIAL_RICCATI) || !(B <= HSQP_SCAN_AUTO_BATCH && N >= HSQP_SCAN_AUTO_MIN_NODES)) return {Sweep::SERIAL, 0};
+  if (h->seg_backoff > 0) { --h->seg_backoff; ++h->backoff_iterations; return {Sweep::SERIAL, 0}; }
+  return {Sweep::SCAN, 0};
+}
+
+// the value pass of the trial (d_xnew, d_unew): per-node {ne, dt*cost, dt*eq^2, dt*dyn^2} in d_misc.  mask: the line search's state (only the
+// instances whose trial is pending), or null.  (Whole-body without the quad form: the step path fuses it into k_step_value)
+static void launch_value_pass(hsqp_handle* h, const LsState* mask) {
+  const int N = h->N, nodes = h->B * h->N;
+  if (h->hdm.formulation == HSQP_FORM_CENTROIDAL)
+    HSQP_LAUNCH(k_lq_cent2_value, dim3(nodes), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt, N, h->d_misc, mask);
+  else if (h->value_quad)   // quads of lanes (hsqp_lqv.h)
+    HSQP_LAUNCH(k_value_quad, dim3((nodes + QV_NODES * QV_WAVES - 1) / (QV_NODES * QV_WAVES)), dim3(QV_THREADS * QV_WAVES), 0, h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt,
+                N, nodes, h->d_misc, mask);
+  else
+    HSQP_LAUNCH(k_lq<false>, dim3(nodes), dim3(LQV_THREADS), sizeof(LqWST<false>), h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt,
+                N, (double*)nullptr, h->d_misc, (long long*)nullptr, mask);
 }
 
 int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
@@ -1533,39 +1545,19 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
       HSQP_LAUNCH(k_lq<true>, dim3(nodes), dim3(LQ_THREADS), sizeof(LqWS), h->stream, h->d_dm, h->d_x, h->d_u, h->d_par, h->d_dt, N,
                          h->d_rec, (double*)nullptr, h->d_prof, (const LsState*)nullptr);
     if (last) HCHECK(hipEventRecord(h->ev[1], h->stream));
-    // The backward sweep: serial recursion, or — one or two instances on a long horizon, or on request — the associative scan over the
-    // stages (hsqp_scan.h).  The scan inverts I + C1 J2 of partial horizons (condition number up to 1e5 centroidal, 1e9 whole-body): on
-    // the QPs of a cold start or of a tracking MPC it reproduces the serial recursion to 1e-11 of the step's scale, on a far-from-
-    // feasible line-search iterate it can lose five digits.  Its result is therefore GATED: the KKT residual of the QP is evaluated
-    // (k_kkt, one small kernel + one 3 B-double read-back) and, if a residual exceeds the gate (scan_gate_accepts, hsqp_scan.h), the
-    // iteration is redone with the serial recursion (hsqp_scan_fallbacks counts these).
-    // > 0: the two-level sweep with segP segments per instance (hsqp_segment.h; opt-in).  A problem class whose sweeps keep failing the gate
-    // (badly scaled QPs: |S| ~ 1e6 on perturbed centroidal batches) would pay sweep + fallback every iteration: after a rejection the handle
-    // backs off to the serial recursion for 1, 3, 7, .. 63 iterations before it tries again
-    int segP = segment_count(h, B, N);
-    // (a sweep the caller FORCED by a flag is attempted every iteration: the back-off is part of the automatic choice only, so forced
-    //  timings and the parity tests of the forced sweeps never silently measure the serial recursion)
-    const bool forced_seg = (h->st.flags & HSQP_FLAG_SEGMENTED_RICCATI) != 0, forced_scan = (h->st.flags & HSQP_FLAG_PARALLEL_RICCATI) != 0;
-    if (segP > 0 && !forced_seg && h->seg_backoff > 0) { --h->seg_backoff; ++h->backoff_iterations; segP = 0; }
-    bool pscan = segP == 0 && !(h->st.flags & HSQP_FLAG_SERIAL_RICCATI) && !(h->st.flags & HSQP_FLAG_SEGMENTED_RICCATI) &&
-                 ((h->st.flags & HSQP_FLAG_PARALLEL_RICCATI) || (B <= HSQP_SCAN_AUTO_BATCH && N >= HSQP_SCAN_AUTO_MIN_NODES));
-    // the same back-off for the scan: a rejected scan costs scan + serial sweep (0.55 + 1.45 ms at one whole-body instance), and the
-    // iterates that fail the gate — far-from-feasible line-search iterates — come in runs
-    if (pscan && !forced_scan && h->seg_backoff > 0) { --h->seg_backoff; ++h->backoff_iterations; pscan = false; }
-    const bool scan = pscan || segP > 0;        // either way a KKT-gated sweep with the serial recursion as fallback
+    const Sweep sweep = choose_sweep(h, B, N);
+    const int segP = sweep.kind == Sweep::SEGMENTED ? sweep.P : 0;
+    const bool scan = sweep.kind != Sweep::SERIAL;   // a KKT-gated sweep with the serial recursion as fallback
     // The joint rows of A~ / B~ (46 of 58: scaled copies of rows of [Px | Pu]) are written only for those who read A~ / B~ as dense blocks: the
     // parallel-in-time and two-level sweeps, the KKT report, the centroidal stage.  The whole-body serial sweep works on the factors.
     const bool joint_rows = cent || !h->ric_fact || scan || want_kkt;
     HSQP_LAUNCH(k_project, dim3(nodes), dim3(PROJ_THREADS), sizeof(ProjWS), h->stream, h->d_rec, h->d_dt, h->d_qp, h->d_prof + 128, cent ? 1 : 0, joint_rows ? 1 : 0, (!cent && h->lq_limb && h->chain_fused) ? 1 : 0);
+    h->qp_joint_rows = joint_rows;
     if (h->has_events) HSQP_LAUNCH(k_jump, dim3(nodes), dim3(256), 0, h->stream, h->d_dt, h->d_rec, h->d_qp);
     if (last) HCHECK(hipEventRecord(h->ev[2], h->stream));
-    if (want_kkt && !h->d_vf) {
-      const size_t bytes = (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8;
-      if (hipMalloc(&h->d_vf, bytes) != hipSuccess) { h->d_vf = nullptr; h->err = "hipMalloc failed (value function for the KKT check, " + std::to_string(bytes) + " bytes)"; return HSQP_ERR_OOM; }
-      poison_hbm(h, h->d_vf, bytes);
-    }
+    if (want_kkt) DEV_ENSURE(h->d_vf, vf_bytes(h), "value functions");
     const int Bm = h->st.max_batch;
-    const size_t gate_bytes = (size_t)Bm * 3 * 8 + (((size_t)Bm * sizeof(int) + 7) / 8) * 8;   // [kkt | |g|_inf | scan flags]
+    const size_t gate_bytes = gate_block_bytes(Bm);
     int ut_given = 0;   // the last sweep's roll-out left ut = k + K dx of every node in d_ut (the serial roll-out does, the scan's closed-loop roll-out does not)
     int fj_given = 0;   // ... and rows 12 .. 34 of Px dx + Pu ut in d_fj (the factored roll-out does)
     auto launch_sweep = [&](bool use_scan, bool need_vf) -> int {
@@ -1585,23 +1577,21 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
       return HSQP_OK;
     };
     auto launch_step = [&]() {
-      if (cent)
-        HSQP_LAUNCH(k_step, dim3(nodes), dim3(64), 0, h->stream, h->d_qp, h->d_ric, h->d_dx, h->d_x, h->d_u, N, 1.0, h->d_ut, h->d_du,
-                           h->d_xnew, h->d_unew, h->d_stepinfo, ut_given, fj_given ? (const double*)h->d_fj : (const double*)nullptr);
-      else if (h->value_quad) {   // whole-body: the step (HBM-bound), then the value pass on quads of lanes (hsqp_lqv.h)
-        HSQP_LAUNCH(k_step, dim3(nodes), dim3(64), 0, h->stream, h->d_qp, h->d_ric, h->d_dx, h->d_x, h->d_u, N, 1.0, h->d_ut, h->d_du,
-                           h->d_xnew, h->d_unew, h->d_stepinfo, ut_given, fj_given ? (const double*)h->d_fj : (const double*)nullptr);
-        HSQP_LAUNCH(k_value_quad, dim3((nodes + QV_NODES * QV_WAVES - 1) / (QV_NODES * QV_WAVES)), dim3(QV_THREADS * QV_WAVES), 0, h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt,
-                           N, nodes, h->d_misc, (const LsState*)nullptr);
-      } else   // a tree with more than four limbs: the phase form of the value pass, fused with the step (k_step_value)
+      if (!cent && !h->value_quad)   // a tree with more than four limbs: the phase form of the value pass, fused with the step (k_step_value)
         HSQP_LAUNCH(k_step_value, dim3(nodes), dim3(LQV_THREADS), sizeof(LqWST<false>), h->stream, h->d_dm, h->d_qp, h->d_ric, h->d_dx, h->d_x, h->d_u,
                            h->d_par, h->d_dt, N, 1.0, h->d_ut, h->d_du, h->d_xnew, h->d_unew, h->d_stepinfo, h->d_misc, h->d_prof + 384, ut_given,
                            fj_given ? (const double*)h->d_fj : (const double*)nullptr);
+      else {   // the step (HBM-bound); whole-body: then the value pass on quads of lanes (centroidal: launch_perf)
+        HSQP_LAUNCH(k_step, dim3(nodes), dim3(64), 0, h->stream, h->d_qp, h->d_ric, h->d_dx, h->d_x, h->d_u, N, 1.0, h->d_ut, h->d_du,
+                           h->d_xnew, h->d_unew, h->d_stepinfo, ut_given, fj_given ? (const double*)h->d_fj : (const double*)nullptr);
+        if (!cent) launch_value_pass(h, nullptr);
+      }
     };
-    auto launch_kkt = [&](bool from_scan) -> int {
-      if (!from_scan) HCHECK(hipMemsetAsync(h->d_kkt, 0, gate_bytes, h->stream));   // kkt, |g|_inf (and the scan flags) are one block; the scan path has zeroed it before its kernels
-      HSQP_LAUNCH(k_kkt, dim3(nodes), dim3(256), 0, h->stream, h->d_xinit, h->d_x, h->d_qp, from_scan ? h->d_vf2 : h->d_vf, h->d_dx, h->d_ut, N, h->d_kkt, h->d_ginf);
-      return HSQP_OK;
+    // vf: the value functions of the sweep whose step is checked.  zeroed: the scan path has zeroed the block before its kernels
+    auto launch_kkt = [&](const double* vf, bool zeroed) {
+      const hipError_t e = zeroed ? hipSuccess : hipMemsetAsync(h->d_kkt, 0, gate_bytes, h->stream);   // kkt, |g|_inf (and the scan flags) are one block
+      if (e == hipSuccess) HSQP_LAUNCH(k_kkt, dim3(nodes), dim3(256), 0, h->stream, h->d_xinit, h->d_x, h->d_qp, vf, h->d_dx, h->d_ut, N, h->d_kkt, h->d_ginf);
+      return e;
     };
     if (scan) HCHECK(hipMemsetAsync(h->d_kkt, 0, gate_bytes, h->stream));   // also the flags the scan kernels OR into
     { const int rc = launch_sweep(scan, want_kkt || scan); if (rc != HSQP_OK) return rc; }
@@ -1609,18 +1599,15 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     launch_step();
     if (scan) {   // the gate's inputs: KKT residuals, |g|_inf and the scan kernels' flags travel to pinned host memory while the kernels below run
       // (two-level sweep: the gate block holds its boundary-consistency numbers instead — no KKT kernel; the KKT report, if asked for, follows the verdict)
-      if (segP == 0) { const int rc = launch_kkt(true); if (rc != HSQP_OK) return rc; }
+      if (segP == 0) HCHECK(launch_kkt(h->d_vf2, true));
       else HSQP_LAUNCH(k_kkt_boundaries, dim3(B * (segP - 1)), dim3(256), 0, h->stream, h->d_xinit, h->d_x, h->d_qp, (const double*)h->d_vf2, h->d_dx, h->d_ut, N, segP,
                               h->d_kkt, h->d_ginf);
       HCHECK(hipMemcpyAsync(h->h_gate, h->d_kkt, gate_bytes, hipMemcpyDeviceToHost, h->stream));
     } else if (want_kkt) {
-      const int rc = launch_kkt(false);
-      if (rc != HSQP_OK) return rc;
+      HCHECK(launch_kkt(h->d_vf, false));
     }
     auto launch_perf = [&]() {   // value pass of the centroidal trial, performance indices before / after, line-search state of the full-step trial
-      if (cent)
-        HSQP_LAUNCH(k_lq_cent2_value, dim3(nodes), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt, N, h->d_misc,
-                           (const LsState*)nullptr);
+      if (cent) launch_value_pass(h, nullptr);
       HSQP_LAUNCH(k_perf_trio, dim3(B, 3), dim3(64), 0, h->stream, h->d_dm, h->d_rec + REC_MISC, REC_SIZE, h->d_x, h->d_misc, 8, h->d_xnew, h->d_par, N,
                          h->d_perf_before, h->d_perf_after, h->d_stepinfo, h->d_dx, h->d_ls);
     };
@@ -1641,19 +1628,15 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
         for (int b = 0; b < B; ++b) { m0 = fmax(m0, hk[2 * b]); m1 = fmax(m1, hk[2 * b + 1]); m2 = fmax(m2, hk[2 * Bm + b]); fl |= flags[b]; }
         fprintf(stderr, "[hsqp seg gate] P=%d boundary-stage KKT stat %.3e prim %.3e |g| %.3e flags %d accept %d\n", segP, m0, m1, m2, fl, (int)accept);
       }
-      if (accept && segP > 0 && want_kkt) {   // the KKT report of an accepted two-level sweep (the gate block is reused: zero it first)
-        HCHECK(hipMemsetAsync(h->d_kkt, 0, gate_bytes, h->stream));
-        HSQP_LAUNCH(k_kkt, dim3(nodes), dim3(256), 0, h->stream, h->d_xinit, h->d_x, h->d_qp, h->d_vf2, h->d_dx, h->d_ut, N, h->d_kkt, h->d_ginf);
-      }
-      if (accept) h->seg_backoff_len = 0;
-      else { h->seg_backoff_len = std::min(2 * h->seg_backoff_len + 1, 63); h->seg_backoff = h->seg_backoff_len; }
-      if (!accept) {
+      if (accept && segP > 0 && want_kkt) HCHECK(launch_kkt(h->d_vf2, false));   // the KKT report of an accepted two-level sweep (the gate block is reused)
+      if (accept) h->seg_backoff_len = 0;   // (the back-off: choose_sweep)
+      else {
+        h->seg_backoff_len = std::min(2 * h->seg_backoff_len + 1, 63); h->seg_backoff = h->seg_backoff_len;
         ++h->scan_fallbacks;
-        if (want_kkt && !h->d_vf) { h->err = "internal: value-function buffer missing"; return HSQP_ERR_HIP; }
         { const int rc = launch_sweep(false, want_kkt != 0); if (rc != HSQP_OK) return rc; }
         if (last) HCHECK(hipEventRecord(h->ev[3], h->stream));
         launch_step();
-        if (want_kkt) { const int rc = launch_kkt(false); if (rc != HSQP_OK) return rc; }
+        if (want_kkt) HCHECK(launch_kkt(h->d_vf, false));
         launch_perf();
         if (ev4_early) HCHECK(hipEventRecord(h->ev[4], h->stream));
       }
@@ -1677,15 +1660,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
           HCHECK(hipMemsetAsync(h->d_counts, 0, 2 * sizeof(int), h->stream));
           HSQP_LAUNCH(k_ls_decide, dim3((B + 63) / 64), dim3(64), 0, h->stream, lst, h->d_perf_before, h->d_perf_after, B, h->d_ls, h->d_counts);
           HSQP_LAUNCH(k_ls_retake, dim3(nodes), dim3(64), 0, h->stream, h->d_x, h->d_u, h->d_dx, h->d_du, N, h->d_ls, h->d_xnew, h->d_unew);
-          if (cent)
-            HSQP_LAUNCH(k_lq_cent2_value, dim3(nodes), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt, N, h->d_misc,
-                               (const LsState*)h->d_ls);
-          else if (h->value_quad)
-            HSQP_LAUNCH(k_value_quad, dim3((nodes + QV_NODES * QV_WAVES - 1) / (QV_NODES * QV_WAVES)), dim3(QV_THREADS * QV_WAVES), 0, h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt,
-                               N, nodes, h->d_misc, (const LsState*)h->d_ls);
-          else
-            HSQP_LAUNCH(k_lq<false>, dim3(nodes), dim3(LQV_THREADS), sizeof(LqWST<false>), h->stream, h->d_dm, h->d_xnew, h->d_unew, h->d_par, h->d_dt,
-                               N, (double*)nullptr, h->d_misc, (long long*)nullptr, (const LsState*)h->d_ls);
+          launch_value_pass(h, h->d_ls);
           HSQP_LAUNCH(k_perf_reduce, dim3(B), dim3(64), 0, h->stream, h->d_dm, h->d_misc, 8, h->d_xnew, h->d_par, N, h->d_perf_after,
                              (const LsState*)h->d_ls);
         }
@@ -1893,23 +1868,22 @@ static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s
   const size_t nin = from_solution ? (size_t)n : (size_t)n * (NX + NU);
   const size_t o_in = 0, o_x = o_in + align256(nin * 8), o_u = o_x + align256((size_t)n * NX * 8), o_tau = o_u + align256((size_t)n * NU * 8),
                o_xw = o_tau + align256((size_t)n * NJ * 8), o_uw = o_xw + align256((size_t)n * NX * 8), total = o_uw + align256((size_t)n * NU * 8);
-  char* base = static_cast<char*>(stage_area(h, total));
-  if (!base) { h->err = "hipMalloc failed (policy evaluation staging)"; return HSQP_ERR_OOM; }
+  DEV_ENSURE(h->d_stage, total, "policy evaluation staging");
+  char* base = h->d_stage;
   double* d_in = reinterpret_cast<double*>(base + o_in);
   double* d_x = reinterpret_cast<double*>(base + o_x);
   double* d_u = reinterpret_cast<double*>(base + o_u);
   double* d_tau = reinterpret_cast<double*>(base + o_tau);
   double* d_xw = reinterpret_cast<double*>(base + o_xw);
   double* d_uw = reinterpret_cast<double*>(base + o_uw);
-  int rc = HSQP_OK;
-  auto step = [&](hipError_t e, const char* what) { if (rc == HSQP_OK && e != hipSuccess) { h->err = std::string(what) + ": " + hipGetErrorString(e); rc = HSQP_ERR_HIP; } };
+  StickyError step{h};
   if (from_solution) {
     step(hipMemcpyAsync(d_in, s_or_x, (size_t)n * 8, hipMemcpyHostToDevice, h->stream), "upload s");
   } else {
     step(hipMemcpyAsync(d_in, s_or_x, (size_t)n * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
     step(hipMemcpyAsync(d_in + (size_t)n * NX, u_in, (size_t)n * NU * 8, hipMemcpyHostToDevice, h->stream), "upload u");
   }
-  if (rc == HSQP_OK) {
+  if (step.rc == HSQP_OK) {
     step(hipFuncSetAttribute((const void*)k_policy_torques, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PolicyWS)), "hipFuncSetAttribute");
     if (from_solution)
       HSQP_LAUNCH(k_policy_inputs, dim3(n), dim3(64), 0, h->stream, (const double*)h->d_xnew, (const double*)h->d_unew, h->N, h->dt,
@@ -1929,7 +1903,7 @@ static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s
   if (u_out) step(hipMemcpyAsync(u_out, d_u, (size_t)n * NU * 8, hipMemcpyDeviceToHost, h->stream), "download u");
   if (tau) step(hipMemcpyAsync(tau, d_tau, (size_t)n * NJ * 8, hipMemcpyDeviceToHost, h->stream), "download tau");
   step(hipStreamSynchronize(h->stream), "sync");
-  return rc;
+  return step.rc;
 }
 
 int hsqp_joint_torques(hsqp_handle* h, int n, const double* x, const double* u, double* tau) {
@@ -1953,6 +1927,11 @@ int hsqp_last_kernel_ms(hsqp_handle* h, double out_ms[5]) {
 
 long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes) {
   if (!h) return HSQP_ERR_BAD_ARG;
+  // a block that is a plain device array of `size` bytes: its first min(bytes, size) bytes to dst
+  auto copy_block = [&](const void* src, long long size) -> long long {
+    if (dst && bytes > 0 && hipMemcpy(dst, src, (size_t)std::min(bytes, size), hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP;
+    return size;
+  };
   if (what == HSQP_BLK_FORMS) {
     const int forms[5] = {h->lq_limb ? 1 : 0, h->value_quad ? 1 : 0, h->lq_limb ? h->lq_split : 0, h->ric_fact ? 1 : 0, h->chain_fused ? 1 : 0};
     if (dst && bytes > 0) memcpy(dst, forms, (size_t)(bytes < 20 ? bytes : 20));
@@ -1961,9 +1940,7 @@ long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes) 
   if (what == HSQP_BLK_PARAMS) {   // available as soon as a problem is resident
     if (!h->have_problem) { h->err = "no problem uploaded"; return HSQP_ERR_BAD_ARG; }
     if (hipSetDevice(h->device) != hipSuccess) return HSQP_ERR_HIP;
-    const long long size = (long long)h->B * (h->N + 1) * NP * 8;
-    if (dst && bytes > 0 && hipMemcpy(dst, h->d_par, (size_t)(bytes < size ? bytes : size), hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP;
-    return size;
+    return copy_block(h->d_par, (long long)h->B * (h->N + 1) * NP * 8);
   }
   if (what == HSQP_BLK_X || what == HSQP_BLK_U || what == HSQP_BLK_STAMPS) {   // the resident linearisation trajectory and grid stamps
     if (!h->have_problem || (what == HSQP_BLK_STAMPS && !h->have_stamps)) {
@@ -1972,9 +1949,7 @@ long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes) 
     }
     if (hipSetDevice(h->device) != hipSuccess) return HSQP_ERR_HIP;
     const double* src = what == HSQP_BLK_X ? h->d_x : what == HSQP_BLK_U ? h->d_u : h->d_stamps[h->stamps_cur];
-    const long long size = (long long)h->B * (what == HSQP_BLK_X ? (h->N + 1) * NX : what == HSQP_BLK_U ? h->N * NU : h->N + 1) * 8;
-    if (dst && bytes > 0 && hipMemcpy(dst, src, (size_t)(bytes < size ? bytes : size), hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP;
-    return size;
+    return copy_block(src, (long long)h->B * (what == HSQP_BLK_X ? (h->N + 1) * NX : what == HSQP_BLK_U ? h->N * NU : h->N + 1) * 8);
   }
   if (!h->have_solution) { h->err = "no iteration has run"; return HSQP_ERR_BAD_ARG; }
   if (hipSetDevice(h->device) != hipSuccess) return HSQP_ERR_HIP;
@@ -2061,16 +2036,16 @@ long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes) 
       }
       break;
     }
-    case HSQP_BLK_DX: out.resize(B * (N + 1) * NX); if (hipMemcpy(out.data(), h->d_dx, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP; break;
-    case HSQP_BLK_DU: out.resize(B * N * NU); if (hipMemcpy(out.data(), h->d_du, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP; break;
-    case 100: {  // phase-profile ticks (only meaningful in -DHSQP_PHASE_PROFILE builds)
-      std::vector<long long> t(4 * 128);
-      if (hipMemcpy(t.data(), h->d_prof, t.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP;
-      if (dst && bytes > 0) memcpy(dst, t.data(), (size_t)(bytes < (long long)t.size() * 8 ? bytes : (long long)t.size() * 8));
-      return (long long)t.size() * 8;
-    }
-    case 101: out.resize(nodes * (size_t)RIC_SIZE); if (hipMemcpy(out.data(), h->d_ric, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP; break;   // raw gains record (debug tools)
-    case 102: out.resize(nodes * (size_t)QP_SIZE); if (hipMemcpy(out.data(), h->d_qp, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return HSQP_ERR_HIP; break;    // raw QP record (debug tools)
+    case HSQP_BLK_DX: return copy_block(h->d_dx, (long long)(B * (N + 1) * NX * 8));
+    case HSQP_BLK_DU: return copy_block(h->d_du, (long long)(B * N * NU * 8));
+    case 100: return copy_block(h->d_prof, 4 * 128 * 8);   // phase-profile ticks (only meaningful in -DHSQP_PHASE_PROFILE builds)
+    case 101: return copy_block(h->d_ric, (long long)(nodes * RIC_SIZE * 8));   // raw gains record (debug tools)
+    case 102:   // raw QP record (debug tools)
+      if (!h->qp_joint_rows) {
+        h->err = "block 102: the last k_project did not write the joint rows of A~ / B~ or the lower triangle of Q~ (whole-body serial sweep without a KKT report)";
+        return HSQP_ERR_BAD_ARG;
+      }
+      return copy_block(h->d_qp, (long long)(nodes * QP_SIZE * 8));
     default: h->err = "unknown block id"; return HSQP_ERR_BAD_ARG;
   }
   const long long size = iout.empty() ? (long long)out.size() * 8 : (long long)iout.size() * 4;

@@ -15,7 +15,9 @@
 
 namespace hsqp {
 
-// ---- per-node QP record (doubles) written by the projection kernel, read by the Riccati kernel
+// ---- per-node QP record (doubles) written by the projection kernel, read by the Riccati kernel.
+// Conditional regions: with joint_rows = false (project_node; the whole-body serial sweep on the factors without a KKT report) the 46 joint rows
+// of A~ and B~ and the strict lower triangle of Q~ are not written and keep whatever was there before (hsqp_debug_read refuses block 102 then).
 constexpr int QP_A = 0;                        // [58][58]
 constexpr int QP_B = QP_A + NX * NX;           // [58][23]
 constexpr int QP_BV = QP_B + NX * NUT;         // [58]
