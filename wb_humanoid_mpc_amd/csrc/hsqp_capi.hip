@@ -16,6 +16,8 @@
 #include "hsqp_riccati_fact.h"
 #include "hsqp_params.h"
 #include "hsqp_policy.h"
+#include "hsqp_feedback.h"
+#include "../../include/hsqp_feedback.h"
 #include "hsqp_warm.h"
 #include "hsqp_cent.h"
 #include "hsqp_cent_lq.h"
@@ -843,6 +845,57 @@ __global__ __launch_bounds__(128) void k_policy_torques(const DevModel* __restri
   policy_node(ctx, *dm, w.st, w.x, w.u, tau + (size_t)b * NJ);
 }
 
+// ---- Riccati feedback policy (hsqp_feedback.h), formed lazily by the feedback entry points: nothing of it runs inside an iteration.
+//  k_feedback_gains: one workgroup per (entry first + blockIdx.x, instance blockIdx.y) — (K, uff) of the entry's source node into
+//                    K [B][count][35][58] / uff [B][count][35] (either may be null).
+//  k_feedback_eval:  one workgroup per instance — the entries of the input segment at s[b] (policy_segment_*: the one the feed-forward
+//                    evaluation takes), blended with its weight, applied to the measured state: u[b] = uff(s) + K(s) x_meas[b].
+constexpr int FB_THREADS = 256;
+__global__ __launch_bounds__(FB_THREADS) void k_feedback_gains(const double* __restrict__ qp, const double* __restrict__ ric, const double* __restrict__ x,
+                                                               const double* __restrict__ u, const double* __restrict__ dts, int N, int first, int count, int cent,
+                                                               double* __restrict__ K, double* __restrict__ uff) {
+  FeedbackWS& w = *reinterpret_cast<FeedbackWS*>(hsqp_smem);
+  const int j = blockIdx.x, b = blockIdx.y;
+  const int k = feedback_source_node(dts + (size_t)b * N, N, first + j);
+  const size_t node = (size_t)b * N + k;
+  feedback_node(Ctx{(int)threadIdx.x, FB_THREADS, nullptr}, qp + node * QP_SIZE, ric + node * RIC_SIZE, x + ((size_t)b * (N + 1) + k) * NX, u + node * NU, cent, w);
+  const size_t e = (size_t)b * count + j;
+  if (K) for (int i = threadIdx.x; i < NU * NX; i += FB_THREADS) K[e * NU * NX + i] = (&w.K[0][0])[i];
+  if (uff) for (int i = threadIdx.x; i < NU; i += FB_THREADS) uff[e * NU + i] = w.uff[i];
+}
+struct FeedbackEvalWS { FeedbackWS fb; double K0[NU][NX]; double uff0[NU]; double xm[NX]; };
+static_assert(sizeof(FeedbackEvalWS) <= 65536, "the feedback kernels run without a dynamic-LDS attribute");
+__global__ __launch_bounds__(FB_THREADS) void k_feedback_eval(const double* __restrict__ qp, const double* __restrict__ ric, const double* __restrict__ x,
+                                                              const double* __restrict__ u, const double* __restrict__ dts, int N, double dt, int uniform, int cent,
+                                                              const double* __restrict__ s, const double* __restrict__ x_meas, double* __restrict__ u_out) {
+  FeedbackEvalWS& w = *reinterpret_cast<FeedbackEvalWS*>(hsqp_smem);
+  const int b = blockIdx.x;
+  const Ctx ctx{(int)threadIdx.x, FB_THREADS, nullptr};
+  const double* db = dts + (size_t)b * N;
+  const PolicySegment g = uniform ? policy_segment_uniform(N, dt, s[b]) : policy_segment_grid(N, db, s[b]);
+  const double a = g.au;
+  for (int i = threadIdx.x; i < NX; i += FB_THREADS) w.xm[i] = x_meas[(size_t)b * NX + i];
+  for (int e = 0; e < 2; ++e) {
+    const int k = feedback_source_node(db, N, g.ku + e);
+    const size_t node = (size_t)b * N + k;
+    feedback_node(ctx, qp + node * QP_SIZE, ric + node * RIC_SIZE, x + ((size_t)b * (N + 1) + k) * NX, u + node * NU, cent, w.fb);
+    if (e == 0) {
+      for (int i = threadIdx.x; i < NU * NX + NU; i += FB_THREADS) {
+        if (i < NU * NX) (&w.K0[0][0])[i] = (&w.fb.K[0][0])[i];
+        else w.uff0[i - NU * NX] = w.fb.uff[i - NU * NX];
+      }
+      __syncthreads();
+    }
+  }
+  // (entry ku + 1 is in w.fb) interpolated gain and bias, then the linear controller at the measured state
+  const int nc = cent ? HSQP_CNX : NX;
+  for (int r = threadIdx.x; r < NU; r += FB_THREADS) {
+    double kx = 0.0;
+    for (int c = 0; c < nc; ++c) kx += ((1.0 - a) * w.K0[r][c] + a * w.fb.K[r][c]) * w.xm[c];
+    u_out[(size_t)b * NU + r] = ((1.0 - a) * w.uff0[r] + a * w.fb.uff[r]) + kx;
+  }
+}
+
 // ---- per-instance performance index from per-node {ne, dt*cost, dt*eq^2, dt*dyn^2} + terminal cost
 __device__ inline void perf_reduce_instance(int b, const DevModel* __restrict__ dm, const double* __restrict__ misc, int misc_stride, const double* __restrict__ x,
                                             const double* __restrict__ par, int N, hsqp_perf* __restrict__ out, const LsState* __restrict__ ls) {
@@ -954,6 +1007,8 @@ struct hsqp_handle {
   int B = 0, N = 0;
   double dt = 0.0;
   bool have_problem = false, have_solution = false;
+  bool have_policy = false;       // the QP / Riccati records and the solution are those of the last successful iteration (feedback entry points)
+  DevBuf<double> d_fb;            // staging of hsqp_feedback_policy (host destinations)
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
   // with non-decreasing stamps
@@ -1327,6 +1382,7 @@ static void commit_problem(hsqp_handle* h, const hsqp_problem* p, bool have_stam
 
 static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   if (!h) return HSQP_ERR_BAD_ARG;
+  h->have_policy = false;
   if (!p || !p->x_init || !p->x_traj || !p->u_traj || !p->node_params) { h->err = "null problem pointer"; return HSQP_ERR_BAD_ARG; }
   if (!fits_handle(h, p)) return HSQP_ERR_BAD_ARG;
   if (!device_src && !padding_is_zero(h, p)) return HSQP_ERR_BAD_ARG;   // device-resident inputs: the caller guarantees the zero padding
@@ -1361,6 +1417,7 @@ static int check_status(hsqp_handle* h, const std::vector<int>& status) {
 
 int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r) {
   if (!h) return HSQP_ERR_BAD_ARG;
+  h->have_policy = false;
   if (!p || !r || !p->x_init || !r->n_events || !r->event_times || !r->mode_sequence || !r->target_times || !r->target_states) {
     h->err = "null problem / reference pointer";
     return HSQP_ERR_BAD_ARG;
@@ -1501,6 +1558,7 @@ static void launch_value_pass(hsqp_handle* h, const LsState* mask) {
 int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
   const int take_step = flags & HSQP_ITER_TAKE_STEP, want_kkt = (flags & HSQP_ITER_KKT) ? 1 : 0, linesearch = (flags & HSQP_ITER_LINESEARCH) ? 1 : 0;
   if (!h) return HSQP_ERR_BAD_ARG;
+  h->have_policy = false;   // (a failed iteration leaves the records half written)
   if (!h->have_problem || n_iterations < 1) { h->err = "no problem uploaded or n_iterations < 1"; return HSQP_ERR_BAD_ARG; }
   HCHECK(hipSetDevice(h->device));
   const int B = h->B, N = h->N;
@@ -1719,6 +1777,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
   }
   h->kernel_ms[4] = h->kernel_ms[0] + h->kernel_ms[1] + h->kernel_ms[2] + h->kernel_ms[3];
   h->have_solution = true;
+  h->have_policy = true;
   return HSQP_OK;
 }
 
@@ -1862,10 +1921,12 @@ int hsqp_solve(hsqp_handle* h, const hsqp_problem* problem, hsqp_solution* solut
   return hsqp_download(h, solution);
 }
 
-static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s_or_x, const double* u_in, double* x_out, double* u_out, double* tau) {
+// x_meas (from_solution only; null: the feed-forward policy): the measured states of the feedback policy, whose input replaces the interpolated one
+static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s_or_x, const double* u_in, const double* x_meas, double* x_out, double* u_out,
+                      double* tau) {
   HCHECK(hipSetDevice(h->device));
   const bool cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
-  const size_t nin = from_solution ? (size_t)n : (size_t)n * (NX + NU);
+  const size_t nin = from_solution ? (size_t)n * (x_meas ? 1 + NX : 1) : (size_t)n * (NX + NU);
   const size_t o_in = 0, o_x = o_in + align256(nin * 8), o_u = o_x + align256((size_t)n * NX * 8), o_tau = o_u + align256((size_t)n * NU * 8),
                o_xw = o_tau + align256((size_t)n * NJ * 8), o_uw = o_xw + align256((size_t)n * NX * 8), total = o_uw + align256((size_t)n * NU * 8);
   DEV_ENSURE(h->d_stage, total, "policy evaluation staging");
@@ -1879,6 +1940,7 @@ static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s
   StickyError step{h};
   if (from_solution) {
     step(hipMemcpyAsync(d_in, s_or_x, (size_t)n * 8, hipMemcpyHostToDevice, h->stream), "upload s");
+    if (x_meas) step(hipMemcpyAsync(d_in + n, x_meas, (size_t)n * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x_meas");
   } else {
     step(hipMemcpyAsync(d_in, s_or_x, (size_t)n * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
     step(hipMemcpyAsync(d_in + (size_t)n * NX, u_in, (size_t)n * NU * 8, hipMemcpyHostToDevice, h->stream), "upload u");
@@ -1891,6 +1953,10 @@ static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s
     else
       HSQP_LAUNCH(k_policy_inputs, dim3(n), dim3(64), 0, h->stream, (const double*)nullptr, (const double*)nullptr, 0, 0.0, (const double*)nullptr,
                          (const double*)nullptr, (const double*)d_in, (const double*)(d_in + (size_t)n * NX), d_x, d_u);
+    if (from_solution && x_meas)
+      HSQP_LAUNCH(k_feedback_eval, dim3(n), dim3(FB_THREADS), sizeof(FeedbackEvalWS), h->stream, (const double*)h->d_qp, (const double*)h->d_ric,
+                         (const double*)h->d_xnew, (const double*)h->d_unew, (const double*)h->d_dt, h->N, h->dt, h->uniform_grid ? 1 : 0, cent ? 1 : 0,
+                         (const double*)d_in, (const double*)(d_in + n), d_u);
     if (cent) {
       HSQP_LAUNCH(k_cent_policy_map, dim3(n), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, n, (const double*)d_x, (const double*)d_u, d_xw, d_uw);
       HSQP_LAUNCH(k_policy_torques, dim3(n), dim3(128), sizeof(PolicyWS), h->stream, h->d_dm, (const double*)d_xw, (const double*)d_uw, d_tau);
@@ -1909,14 +1975,64 @@ static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s
 int hsqp_joint_torques(hsqp_handle* h, int n, const double* x, const double* u, double* tau) {
   if (!h) return HSQP_ERR_BAD_ARG;
   if (n < 1 || !x || !u || !tau) { h->err = "hsqp_joint_torques: n < 1 or null pointer"; return HSQP_ERR_BAD_ARG; }
-  return run_policy(h, n, false, x, u, nullptr, nullptr, tau);
+  return run_policy(h, n, false, x, u, nullptr, nullptr, nullptr, tau);
 }
 
 int hsqp_evaluate_policy(hsqp_handle* h, const double* s, double* x, double* u, double* tau) {
   if (!h) return HSQP_ERR_BAD_ARG;
   if (!h->have_solution) { h->err = "no solution on the device"; return HSQP_ERR_BAD_ARG; }
   if (!s) { h->err = "hsqp_evaluate_policy: null time offsets"; return HSQP_ERR_BAD_ARG; }
-  return run_policy(h, h->B, true, s, nullptr, x, u, tau);
+  return run_policy(h, h->B, true, s, nullptr, nullptr, x, u, tau);
+}
+
+// ---- Riccati feedback policy (include/hsqp_feedback.h, csrc/hsqp_feedback.h)
+// the policy of the resident solution can be formed: the last call that touched the records was a successful iteration, and no instance failed
+static int feedback_ready(hsqp_handle* h, const char* who) {
+  if (!h->have_policy) { h->err = std::string(who) + ": no feedback policy (no successful iteration since the last upload)"; return HSQP_ERR_BAD_ARG; }
+  HCHECK(hipSetDevice(h->device));
+  std::vector<int> status(h->B);
+  HCHECK(hipMemcpy(status.data(), h->d_status, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost));
+  return check_status(h, status);
+}
+
+static int feedback_policy_impl(hsqp_handle* h, int first, int count, double* K, double* uff, bool device_dst) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = device_dst ? "hsqp_feedback_policy_device" : "hsqp_feedback_policy";
+  { const int rc = feedback_ready(h, who); if (rc != HSQP_OK) return rc; }
+  if (first < 0 || count < 1 || count > h->N + 1 - first) {
+    h->err = std::string(who) + ": window [first, first + count) outside the policy's entries [0, N]";
+    return HSQP_ERR_BAD_ARG;
+  }
+  if (!K && !uff) return HSQP_OK;
+  const size_t B = h->B, nK = B * count * NU * NX, nu = B * count * NU;
+  double* dK = K;
+  double* du = uff;
+  if (!device_dst) {
+    DEV_ENSURE(h->d_fb, ((K ? nK : 0) + (uff ? nu : 0)) * 8, "feedback policy staging");
+    dK = K ? h->d_fb.p : nullptr;
+    du = uff ? h->d_fb.p + (K ? nK : 0) : nullptr;
+  }
+  StickyError step{h};
+  HSQP_LAUNCH(k_feedback_gains, dim3(count, B), dim3(FB_THREADS), sizeof(FeedbackWS), h->stream, (const double*)h->d_qp, (const double*)h->d_ric,
+              (const double*)h->d_xnew, (const double*)h->d_unew, (const double*)h->d_dt, h->N, first, count,
+              h->hdm.formulation == HSQP_FORM_CENTROIDAL ? 1 : 0, dK, du);
+  step(hipGetLastError(), "k_feedback_gains");
+  if (!device_dst) {
+    if (K) step(hipMemcpyAsync(K, dK, nK * 8, hipMemcpyDeviceToHost, h->stream), "download K");
+    if (uff) step(hipMemcpyAsync(uff, du, nu * 8, hipMemcpyDeviceToHost, h->stream), "download uff");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+
+int hsqp_feedback_policy(hsqp_handle* h, int first, int count, double* K, double* uff) { return feedback_policy_impl(h, first, count, K, uff, false); }
+int hsqp_feedback_policy_device(hsqp_handle* h, int first, int count, double* d_K, double* d_uff) { return feedback_policy_impl(h, first, count, d_K, d_uff, true); }
+
+int hsqp_evaluate_feedback_policy(hsqp_handle* h, const double* s, const double* x_meas, double* x, double* u, double* tau) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  { const int rc = feedback_ready(h, "hsqp_evaluate_feedback_policy"); if (rc != HSQP_OK) return rc; }
+  if (!s || !x_meas) { h->err = "hsqp_evaluate_feedback_policy: null time offsets or measured states"; return HSQP_ERR_BAD_ARG; }
+  return run_policy(h, h->B, true, s, nullptr, x_meas, x, u, tau);
 }
 
 int hsqp_last_kernel_ms(hsqp_handle* h, double out_ms[5]) {

@@ -8,6 +8,7 @@
 //   tau_j = S_j . ( sum_{i in subtree(j)} (f_i + I_i D)  -  sum_{contacts in subtree(j)} {m_c + r_c x f_c, f_c} ).
 #pragma once
 #include "hsqp_model.h"
+#include "hsqp_feedback.h"   // the evaluation segment (policy_segment_*)
 
 namespace hsqp {
 
@@ -63,15 +64,9 @@ HSQP_HD void policy_node(const Ctx& ctx, const DevModel& dm, SW& ws, const doubl
 // Feed-forward policy at time offset s (seconds after the first node) on a uniform grid: clamped linear interpolation of the
 // state (N+1 nodes) and input (N nodes) trajectories — ocs2 LinearInterpolation on the PrimalSolution time stamps.
 HSQP_HD void policy_interpolate(const Ctx& ctx, const double* xt, const double* ut, int N, double dt, double s, double* x, double* u) {
-  double a = s / dt;
-  if (a < 0.0) a = 0.0;
-  int kx = (int)a;
-  if (kx > N - 1) kx = N - 1;
-  double ax = a - kx;
-  if (ax > 1.0) ax = 1.0;
-  int ku = (int)a;
-  double au = a - ku;
-  if (ku > N - 2) { ku = N - 2 > 0 ? N - 2 : 0; au = N >= 2 ? (a - ku > 1.0 ? 1.0 : a - ku) : 0.0; }
+  const PolicySegment g = policy_segment_uniform(N, dt, s);
+  const int kx = g.kx, ku = g.ku;
+  const double ax = g.ax, au = g.au;
   WG_FOR(ctx, i, NX + NU) {
     if (i < NX) x[i] = (1.0 - ax) * xt[(size_t)kx * NX + i] + ax * xt[(size_t)(kx + 1) * NX + i];
     else { const int c = i - NX; u[c] = N >= 2 ? (1.0 - au) * ut[(size_t)ku * NU + c] + au * ut[(size_t)(ku + 1) * NU + c] : ut[c]; }
@@ -79,25 +74,11 @@ HSQP_HD void policy_interpolate(const Ctx& ctx, const double* xt, const double* 
   WG_SYNC(ctx);
 }
 
-// The same on a non-uniform grid (hsqp_problem::dt_nodes; zero-length event intervals): node k of the state trajectory sits at
-// t_k = sum_{i<k} dts[i], the inputs at t_0 .. t_{N-1}.  At an event time the post-event node is taken (the last node with t_k <= s).
+// The same on a non-uniform grid (hsqp_problem::dt_nodes; zero-length event intervals): the segment rule is policy_segment_grid.
 HSQP_HD void policy_interpolate_grid(const Ctx& ctx, const double* xt, const double* ut, int N, const double* dts, double s, double* x, double* u) {
-  if (s < 0.0) s = 0.0;
-  double tk = 0.0;       // start of interval kx
-  int kx = 0;
-  while (kx < N - 1 && tk + dts[kx] <= s) { tk += dts[kx]; ++kx; }
-  while (kx < N - 1 && dts[kx] == 0.0) ++kx;              // never interpolate across a jump
-  const double h = dts[kx];
-  double ax = h > 0.0 ? (s - tk) / h : 1.0;
-  if (ax > 1.0) ax = 1.0;
-  // inputs: stamps t_0 .. t_{N-1}; beyond the last stamp the last input is held
-  int ku = kx;
-  double au = ax;
-  if (ku > N - 2) { ku = N - 2 > 0 ? N - 2 : 0; au = N >= 2 ? 1.0 : 0.0; }
-  if (N >= 2 && dts[ku] == 0.0) au = 1.0;
-  // node ku + 1 is a PRE-event node when interval ku + 1 is an event: it carries no optimised input of its own (du = 0 there;
-  // upstream multiple_shooting::toPrimalSolution gives it the input of the node before), so the input is held up to the switch
-  else if (N >= 2 && ku + 1 <= N - 1 && dts[ku + 1] == 0.0) au = 0.0;
+  const PolicySegment g = policy_segment_grid(N, dts, s);
+  const int kx = g.kx, ku = g.ku;
+  const double ax = g.ax, au = g.au;
   WG_FOR(ctx, i, NX + NU) {
     if (i < NX) x[i] = (1.0 - ax) * xt[(size_t)kx * NX + i] + ax * xt[(size_t)(kx + 1) * NX + i];
     else { const int c = i - NX; u[c] = N >= 2 ? (1.0 - au) * ut[(size_t)ku * NU + c] + au * ut[(size_t)(ku + 1) * NU + c] : ut[c]; }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/hsqp.h"
+#include "../../include/hsqp_feedback.h"
 
 namespace hsqp_host {
 
@@ -117,6 +118,26 @@ class HipSqpSolver {
     state.assign(B * HSQP_NX, 0.0); input.assign(B * HSQP_NU, 0.0); jointTorques.assign(B * HSQP_NJ, 0.0);
     const int rc = hsqp_evaluate_policy(h_, secondsAfterStart.data(), state.data(), input.data(), jointTorques.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_evaluate_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** Riccati feedback policy of the last run (ocs2 LinearController, u = uff + K x; include/hsqp_feedback.h): entries [first, first + count)
+   *  of every instance, K [batch][count][HSQP_NU][HSQP_NX] and uff [batch][count][HSQP_NU], row-major; count < 0: up to node N. */
+  void feedbackPolicy(int first, int count, std::vector<double>& K, std::vector<double>& uff) {
+    const size_t B = (size_t)solution_.batch;
+    if (count < 0) count = solution_.nodes + 1 - first;
+    K.assign(B * (count > 0 ? count : 0) * HSQP_NU * HSQP_NX, 0.0); uff.assign(B * (count > 0 ? count : 0) * HSQP_NU, 0.0);
+    const int rc = hsqp_feedback_policy(h_, first, count, K.data(), uff.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_feedback_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** MPC_MRT_Interface::evaluatePolicy with the feedback policy: the input at the measured states (one HSQP_NX row per instance). */
+  void evaluatePolicy(const std::vector<double>& secondsAfterStart, const std::vector<double>& measuredState, std::vector<double>& state,
+                      std::vector<double>& input, std::vector<double>& jointTorques) {
+    const size_t B = (size_t)solution_.batch;
+    if (secondsAfterStart.size() != B || measuredState.size() != B * HSQP_NX)
+      throw std::runtime_error("[HipSqpSolver] evaluatePolicy: one time and one measured state per instance expected");
+    state.assign(B * HSQP_NX, 0.0); input.assign(B * HSQP_NU, 0.0); jointTorques.assign(B * HSQP_NJ, 0.0);
+    const int rc = hsqp_evaluate_feedback_policy(h_, secondsAfterStart.data(), measuredState.data(), state.data(), input.data(), jointTorques.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_evaluate_feedback_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
   const PrimalSolution& getPrimalSolution() const { return solution_; }

@@ -16,14 +16,17 @@
 //      per-node parameter table there: contact flags, swing-foot references, impact proximity, arm-swing phase, target interpolation);
 //   4. sqpIteration x { LQ approximation, projection, Riccati QP, filter line search } on the GPU (hsqp_iterate_device), stopping
 //      early when the step falls below deltaTol;
-//   5. PrimalSolution (time stamps, states, inputs, mode schedule, FeedforwardController — useFeedbackPolicy false, task.info:91),
-//      PerformanceIndex log, SqpSolver::getBenchmarks() buckets.
+//   5. PrimalSolution (time stamps, states, inputs, mode schedule, and the controller: FeedforwardController with useFeedbackPolicy false —
+//      task.info:91 —, otherwise the LinearController of the last QP's Riccati gains, include/hsqp_feedback.h), PerformanceIndex log,
+//      SqpSolver::getBenchmarks() buckets.
 // Compiled and run in this repository against stand-in ocs2 headers (tests/stubs/ocs2, tests/test_adaptor.py).
 #pragma once
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
+#include <ocs2_core/control/LinearController.h>
 #include <ocs2_core/initialization/Initializer.h>
 #include <ocs2_mpc/MPC_BASE.h>
 #include <ocs2_oc/oc_solver/SolverBase.h>
@@ -87,7 +90,7 @@ class HipSqpSolverAdaptor final : public SolverBase {
     impl_.setLinesearchSettings(ls);
   }
 
-  void reset() override { primal_.clear(); log_.clear(); numIterations_ = 0; benchmarks_ = HipSqpBenchmarks(); }
+  void reset() override { primal_.clear(); gainK_.clear(); gainUff_.clear(); log_.clear(); numIterations_ = 0; benchmarks_ = HipSqpBenchmarks(); }
   size_t getNumIterations() const override { return numIterations_; }
   scalar_t getFinalTime() const override { return primal_.timeTrajectory_.empty() ? 0.0 : primal_.timeTrajectory_.back(); }
   const PerformanceIndex& getPerformanceIndeces() const override {
@@ -108,7 +111,26 @@ class HipSqpSolverAdaptor final : public SolverBase {
     out->inputTrajectory_.assign(primal_.inputTrajectory_.begin(), primal_.inputTrajectory_.begin() + n);
     for (size_t i : primal_.postEventIndices_) if (i < n) out->postEventIndices_.push_back(i);
     out->modeSchedule_ = primal_.modeSchedule_;
-    out->controllerPtr_.reset(new FeedforwardController(out->timeTrajectory_, out->inputTrajectory_));
+    if (!settings_.useFeedbackPolicy) {
+      out->controllerPtr_.reset(new FeedforwardController(out->timeTrajectory_, out->inputTrajectory_));
+      return;
+    }
+    // the policy entries of the same stamps; the device rows are row-major [HSQP_NU][HSQP_NX], matrix_t is column-major: element by element
+    if (gainK_.size() < n * HSQP_NU * HSQP_NX) throw std::runtime_error("[HipSqpSolverAdaptor] no feedback policy: no problem solved yet?");
+    const int nx = cfg_.stateDim;
+    vector_array_t bias;
+    matrix_array_t gain;
+    for (size_t k = 0; k < n; ++k) {
+      const double* Kk = &gainK_[k * HSQP_NU * HSQP_NX];
+      vector_t b(HSQP_NU);
+      matrix_t K(HSQP_NU, nx);
+      for (int i = 0; i < HSQP_NU; ++i) {
+        b[i] = gainUff_[k * HSQP_NU + i];
+        for (int j = 0; j < nx; ++j) K(i, j) = Kk[(size_t)i * HSQP_NX + j];
+      }
+      bias.push_back(std::move(b)); gain.push_back(std::move(K));
+    }
+    out->controllerPtr_.reset(new LinearController(out->timeTrajectory_, std::move(bias), std::move(gain)));
   }
   // ---- the rest of SolverBase's pure-virtual query interface.  Upstream SqpSolver answers these the same way: it throws "not
   //      implemented" for the value function, the Hamiltonian, the Lagrangian and the multipliers (ocs2_sqp/SqpSolver.h); the
@@ -141,6 +163,8 @@ class HipSqpSolverAdaptor final : public SolverBase {
   }
   /** Step length / FilterLinesearch step type (HSQP_STEP_*) of the last iteration. */
   scalar_t lastStepSize() const { return stepSize_; }
+  /** the handle of the device solver (the C ABI's other entry points, e.g. hsqp_evaluate_feedback_policy, on the resident solution) */
+  hsqp_handle* handle() { return impl_.handle(); }
   int lastStepType() const { return stepType_; }
   /** the device-side policy sample + feed-forward torques of the last solution (WBMpcMrtJointController.cpp:136-158) */
   void evaluatePolicy(scalar_t time, vector_t& state, vector_t& input, vector_t& jointTorques) {
@@ -274,6 +298,14 @@ class HipSqpSolverAdaptor final : public SolverBase {
       primal_.stateTrajectory_.push_back(std::move(xs)); primal_.inputTrajectory_.push_back(std::move(us));
       if (post[k]) primal_.postEventIndices_.push_back((size_t)k);
     }
+    //    useFeedbackPolicy: the N + 1 entries of the Riccati feedback policy (pre-event and terminal nodes carry the entries of the node before,
+    //    like the inputs above); their formation is the solver's computeController time
+    if (settings_.useFeedbackPolicy) {
+      const auto t0 = std::chrono::steady_clock::now();
+      impl_.feedbackPolicy(0, N + 1, gainK_, gainUff_);
+      const scalar_t sec = std::chrono::duration<scalar_t>(std::chrono::steady_clock::now() - t0).count();
+      benchmarks_.computeControllerTime += sec;
+    }
   }
 
   HipSqpAdaptorConfig cfg_;
@@ -281,6 +313,7 @@ class HipSqpSolverAdaptor final : public SolverBase {
   std::unique_ptr<Initializer> initializer_;
   hsqp_host::HipSqpSolver impl_;
   PrimalSolution primal_;
+  std::vector<double> gainK_, gainUff_;   // useFeedbackPolicy: the policy entries of primal_'s N + 1 nodes, [N + 1][HSQP_NU][HSQP_NX] / [N + 1][HSQP_NU]
   std::vector<PerformanceIndex> log_;
   size_t numIterations_ = 0;
   HipSqpBenchmarks benchmarks_;

@@ -628,3 +628,75 @@ def make_centroidal_problem(model, n_nodes=100, batch=1, gait="walk", v_cmd=(0.3
     if with_reference:
         return np.stack(x0s), np.stack(xs), np.stack(us), np.stack(ps), dt, (schedules, targets_all, t0)
     return np.stack(x0s), np.stack(xs), np.stack(us), np.stack(ps), dt
+
+
+# ---- Riccati feedback policy (include/hsqp_feedback.h): the rules of csrc/hsqp_feedback.h restated for the tests
+def feedback_source_nodes(dts):
+    """Node whose gains each of the N + 1 policy entries carries (dts: the N interval lengths, 0 = event): node N takes node N - 1's, a
+    pre-event node i (0 < i, dts[i] == 0) node i - 1's, chained over consecutive events."""
+    dts = np.asarray(dts, dtype=float)
+    N = len(dts)
+    out = np.empty(N + 1, dtype=int)
+    for i in range(N + 1):
+        k = min(i, N - 1)
+        while k > 0 and dts[k] == 0.0:
+            k -= 1
+        out[i] = k
+    return out
+
+
+def feedback_gains(Px, Pu, Kt, nut, cent=False):
+    """K = Px + Pu[:, :nut] K~[:nut] of one node (Px [35][58], Pu [35][23], K~ [23][58]); centroidal: columns 35.. are zero."""
+    nc = _abi.CNX if cent else _abi.NX
+    K = np.zeros((_abi.NU, _abi.NX))
+    K[:, :nc] = Px[:, :nc] + Pu[:, :nut] @ Kt[:nut, :nc]
+    return K
+
+
+def policy_input_segment(N, dt, s, dts=None):
+    """(ku, au): the input segment and weight of the policy evaluation at s (csrc/hsqp_feedback.h policy_segment_*; dts None: uniform dt)."""
+    if dts is None:
+        a = max(s / dt, 0.0)
+        ku = int(a)
+        au = a - ku
+        if ku > N - 2:
+            ku = max(N - 2, 0)
+            au = min(a - ku, 1.0) if N >= 2 else 0.0
+        return ku, au
+    s = max(s, 0.0)
+    tk, kx = 0.0, 0
+    while kx < N - 1 and tk + dts[kx] <= s:
+        tk += dts[kx]
+        kx += 1
+    while kx < N - 1 and dts[kx] == 0.0:
+        kx += 1
+    h = dts[kx]
+    ax = min((s - tk) / h if h > 0.0 else 1.0, 1.0)
+    ku, au = kx, ax
+    if ku > N - 2:
+        ku, au = max(N - 2, 0), (1.0 if N >= 2 else 0.0)
+    if N >= 2 and dts[ku] == 0.0:
+        au = 1.0
+    elif N >= 2 and ku + 1 <= N - 1 and dts[ku + 1] == 0.0:
+        au = 0.0
+    return ku, au
+
+
+def linear_controller_input(times, uff, K, t, x):
+    """ocs2 LinearController::computeInput: uff(t) + K(t) x on LinearInterpolation::timeSegment (std::lower_bound on the stamps; the value is
+    alpha v[i] + (1 - alpha) v[i + 1]).  times [n], uff [n][nu], K [n][nu][nx], x [nx]."""
+    times = np.asarray(times, dtype=float)
+    n = len(times)
+    if n <= 1:
+        i, alpha = 0, 1.0
+    else:
+        idx = int(np.searchsorted(times, t, side="left"))
+        if idx <= 0:
+            i, alpha = 0, 1.0
+        elif idx > n - 1:
+            i, alpha = n - 2, 0.0
+        else:
+            i, alpha = idx - 1, (times[idx] - t) / (times[idx] - times[idx - 1])
+    j = min(i + 1, n - 1)
+    Ks = alpha * K[i] + (1.0 - alpha) * K[j]
+    return alpha * uff[i] + (1.0 - alpha) * uff[j] + Ks @ x

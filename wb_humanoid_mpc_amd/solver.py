@@ -86,6 +86,10 @@ def load_library():
         raise RuntimeError(f"libhsqp_hip ABI {lib.hsqp_abi_version()} != the binding's {_abi.ABI_VERSION} (include/hsqp.h: HSQP_ABI_VERSION)")
     lib.hsqp_joint_torques.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.hsqp_evaluate_policy.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+    # include/hsqp_feedback.h
+    lib.hsqp_feedback_policy.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
+    lib.hsqp_feedback_policy_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
+    lib.hsqp_evaluate_feedback_policy.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -368,6 +372,32 @@ class HipSqpSolver:
         s = _c(np.broadcast_to(s, (B,)))
         x, u, tau = np.zeros((B, _abi.NX)), np.zeros((B, _abi.NU)), np.zeros((B, _abi.NJ))
         self._check(self.lib.hsqp_evaluate_policy(self.h, s.ctypes.data_as(_dp), x.ctypes.data_as(_dp), u.ctypes.data_as(_dp), tau.ctypes.data_as(_dp)))
+        return x, u, tau
+
+    # ---- the Riccati feedback policy (include/hsqp_feedback.h; ocs2 LinearController, useFeedbackPolicy)
+    def feedback_policy(self, first=0, count=None):
+        """Entries [first, first + count) of the feedback policy u = uff + K x of every instance (count None: up to node N):
+        (K[B, count, 35, 58], uff[B, count, 35])."""
+        B, N = self._shape
+        if count is None:
+            count = N + 1 - first
+        K, uff = np.zeros((B, max(count, 0), _abi.NU, _abi.NX)), np.zeros((B, max(count, 0), _abi.NU))
+        self._check(self.lib.hsqp_feedback_policy(self.h, int(first), int(count), K.ctypes.data_as(_dp), uff.ctypes.data_as(_dp)))
+        return K, uff
+
+    def feedback_policy_device(self, first, count, K_ptr=0, uff_ptr=0):
+        """hsqp_feedback_policy_device: the same entries into device memory (K_ptr / uff_ptr: device addresses, 0 = not wanted)."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_feedback_policy_device(self.h, int(first), int(count), cast(K_ptr), cast(uff_ptr)))
+
+    def evaluate_feedback_policy(self, s, x_meas):
+        """Feedback policy at s[b] seconds after the first node and the measured states x_meas[b]: (x[B,58], u[B,35], tau[B,23])."""
+        B, _ = self._shape
+        s = _c(np.broadcast_to(s, (B,)))
+        x_meas = _c(np.broadcast_to(x_meas, (B, _abi.NX)))
+        x, u, tau = np.zeros((B, _abi.NX)), np.zeros((B, _abi.NU)), np.zeros((B, _abi.NJ))
+        self._check(self.lib.hsqp_evaluate_feedback_policy(self.h, s.ctypes.data_as(_dp), x_meas.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                                           u.ctypes.data_as(_dp), tau.ctypes.data_as(_dp)))
         return x, u, tau
 
     def joint_torques(self, x, u):
