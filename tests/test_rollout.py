@@ -1,0 +1,291 @@
+"""The batched policy rollout (include/hsqp_rollout.h, csrc/hsqp_rollout.h) on the CPU: the header and the exported entry points, the defaults
+of the task.info rollout block, and the host build of the kernel source (tests/rollout/rollout_emu.cpp) against the numpy restatement
+(tests/rollout_ref.py) on the oracle's flow maps — both formulations, uniform and event grids, both controllers, both integrators — with the
+sample / chaining / step-cap semantics of the header."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import rollout_ref as R
+from conftest import random_state_input
+from test_oracle_centroidal import cent_state_input
+from wb_humanoid_mpc_amd import _abi, solver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "wb_humanoid_mpc_amd", "csrc")
+LIBDIR = os.path.join(ROOT, "wb_humanoid_mpc_amd")
+NX, NU, CNX = _abi.NX, _abi.NU, _abi.CNX
+ENTRY_POINTS = ("hsqp_rollout_defaults", "hsqp_rollout_policy", "hsqp_rollout_policy_device")
+_dp = C.POINTER(C.c_double)
+_ip = C.POINTER(C.c_int32)
+
+
+def test_header_compiles_and_the_library_exports_the_entry_points(tmp_path):
+    src = tmp_path / "r.c"
+    src.write_text('#include <stdio.h>\n#include "hsqp_rollout.h"\n'
+                   'int main(void){ hsqp_rollout_settings s;\n'
+                   ' void (*d)(hsqp_rollout_settings*) = hsqp_rollout_defaults;\n'
+                   ' int (*a)(hsqp_handle*, const hsqp_rollout_settings*, const double*, const double*, double, int, double*, double*, int32_t*, int32_t*,'
+                   ' int32_t*) = hsqp_rollout_policy;\n'
+                   ' int (*b)(hsqp_handle*, const hsqp_rollout_settings*, const double*, const double*, double, int, double*, double*, int32_t*, int32_t*,'
+                   ' int32_t*) = hsqp_rollout_policy_device;\n'
+                   ' s.integrator = HSQP_ROLLOUT_ODE45 + HSQP_ROLLOUT_RK4; s.controller = HSQP_ROLLOUT_FEEDFORWARD + HSQP_ROLLOUT_FEEDBACK;\n'
+                   ' printf("%d %d %d %d\\n", HSQP_ABI_VERSION, a != 0 && b != 0 && d != 0, s.integrator + s.controller,'
+                   ' HSQP_ROLLOUT_OK + HSQP_ROLLOUT_MAX_STEPS + HSQP_ROLLOUT_NONFINITE); return 0; }\n')
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "r.o")])
+    syms = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(LIBDIR, "libhsqp_hip.so")], text=True)
+    names = {line.split()[-1] for line in syms.splitlines() if line.strip()}
+    assert all(n in names for n in ENTRY_POINTS)
+    assert C.sizeof(_abi.RolloutSettings) == 40
+    lib = solver.load_library()
+    st = _abi.RolloutSettings()
+    lib.hsqp_rollout_defaults(C.byref(st))
+    assert (st.integrator, st.controller) == (_abi.ROLLOUT_ODE45, _abi.ROLLOUT_FEEDFORWARD)
+    assert (st.abs_tol, st.rel_tol, st.initial_step, st.max_steps_per_second) == (1e-5, 1e-3, 0.015, 10000.0)
+    # a NULL handle is a bad argument, with or without a device
+    z = np.zeros(NX)
+    i = np.zeros(1, np.int32)
+    for f in (lib.hsqp_rollout_policy, lib.hsqp_rollout_policy_device):
+        assert f(None, C.byref(st), z.ctypes.data_as(_dp), z.ctypes.data_as(_dp), 0.01, 1, None, None, i.ctypes.data_as(_ip), None, None) == _abi.ERR_BAD_ARG
+    assert _abi.ABI_VERSION == 7           # additions only: no revision bump
+
+
+def test_binding_raises_no_device_without_a_gpu(model):
+    if solver.load_library().hsqp_device_count() > 0:
+        pytest.skip("a GPU is visible: the binding is exercised by tests/test_gpu_rollout.py")
+    with pytest.raises(solver.HsqpError) as ei:
+        solver.HipSqpSolver(model, max_nodes=8, max_batch=1).rollout_policy(0.0, model.initial_state, 1.0 / 60.0)
+    assert ei.value.code == _abi.ERR_NO_DEVICE
+
+
+# ---------------------------------------------------------------------------------------------- host build of the kernel source
+@pytest.fixture(scope="module")
+def remu(tmp_path_factory):
+    lib_path = tmp_path_factory.mktemp("ro") / "librollout_emu.so"
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-Wall", "-Wno-unknown-pragmas", "-Werror", "-fPIC", "-shared", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "rollout", "rollout_emu.cpp"), "-o", str(lib_path)])
+    lib = C.CDLL(str(lib_path))
+    lib.ro_create.restype = C.c_void_p
+    lib.ro_create.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    lib.ro_destroy.argtypes = [C.c_void_p]
+    lib.ro_rollout.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), C.c_int, _dp, C.c_double, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
+                               _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
+    lib.ro_flow.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    return lib
+
+
+@pytest.fixture(scope="module")
+def handles(remu, model, cmodel):
+    out = {}
+    for name, m in (("wb", model), ("centroidal", cmodel)):
+        err = C.create_string_buffer(256)
+        h = remu.ro_create(C.byref(m.desc), err, 256)
+        assert h, err.value
+        out[name] = C.c_void_p(h)
+    yield out
+    for h in out.values():
+        remu.ro_destroy(h)
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(_dp)
+
+
+def emu_rollout(remu, h, st, case, s0, x0, duration, n):
+    """The host build over a batch: (x [B][n][58], u [B][n][35], status, steps, rejected)."""
+    B = len(s0)
+    ut = np.ascontiguousarray(np.repeat(case["ut"][None], B, axis=0))
+    dts = None if case["dts"] is None else np.ascontiguousarray(np.repeat(case["dts"][None], B, axis=0))
+    K = uff = None
+    if st["controller"] == R.FEEDBACK:
+        K = np.ascontiguousarray(np.repeat(case["K"][None], B, axis=0))
+        uff = np.ascontiguousarray(np.repeat(case["uff"][None], B, axis=0))
+    s = _abi.RolloutSettings(**st)
+    x, u = np.zeros((B, n, NX)), np.zeros((B, n, NU))
+    status, steps, rej = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    s0, x0 = np.ascontiguousarray(s0, dtype=float), np.ascontiguousarray(x0, dtype=float)
+    remu.ro_rollout(h, C.byref(s), len(case["ut"]), _p(dts), case["dt"], _p(ut), _p(K), _p(uff), 0, len(case["K"]), int(case["cent"]), B, _p(s0), _p(x0),
+                    duration, n, _p(x), _p(u), status.ctypes.data_as(_ip), steps.ctypes.data_as(_ip), rej.ctypes.data_as(_ip))
+    return x, u, status, steps, rej
+
+
+GRIDS = {"uniform": None, "events": [0.01, 0.01, 0.0, 0.01, 0.0, 0.0, 0.01, 0.01, 0.01]}
+
+
+def state_input(model, cent, rng, scale=1.0):
+    """A random (x, u) of either formulation (x: the live entries) from the whole-body model."""
+    return cent_state_input(model, rng) if cent else random_state_input(model, rng, scale)
+
+
+def make_case(m, cent, grid, rng, vary=0.01):
+    """A random resident policy around weight compensation on a grid, with feedback entries for every node (window first = 0).  The entries
+    drift from node to node by `vary` of a random direction: the interpolated controller has kinks at the node stamps, and across a kink
+    the adaptive step sequence (which the two flows reproduce only to rounding) moves the result by far more than rounding."""
+    dts = None if GRIDS[grid] is None else np.array(GRIDS[grid])
+    N = 9
+    nc = CNX if cent else NX
+    (_, u0), (_, u1) = state_input(m, cent, rng), state_input(m, cent, rng)
+    scale = np.r_[np.full(12, 0.2), np.full(NU - 12, 0.5)]
+    ut = np.array([(u0 + vary * k * u1) * scale for k in range(N)])
+    ut[:, 2] += m.total_mass * 9.81 / 2
+    ut[:, 8] += m.total_mass * 9.81 / 2
+    K0, K1 = np.zeros((NU, NX)), np.zeros((NU, NX))
+    K0[:, :nc], K1[:, :nc] = 0.5 * rng.standard_normal((NU, nc)), 0.5 * rng.standard_normal((NU, nc))
+    K = np.array([K0 + vary * k * K1 for k in range(N + 1)])
+    xr = state_input(m, cent, rng)[0][:nc]
+    uff = ut[np.minimum(np.arange(N + 1), N - 1)] - np.einsum("knc,c->kn", K[:, :, :nc], xr)
+    return dict(ut=ut, dt=0.01, dts=dts, K=K, uff=uff, cent=cent)
+
+
+def start_states(m, cent, rng, B):
+    x0 = np.zeros((B, NX))
+    for b in range(B):
+        x = state_input(m, cent, rng, 0.5)[0]
+        x0[b, :len(x)] = x
+    return x0
+
+
+def ref_rollout(flow, case, st, s0, x0, duration, n, logs=None):
+    pol = R.Policy(case["ut"], case["dt"], case["dts"], case["K"], case["uff"], 0, case["cent"])
+    res = []
+    for b in range(len(s0)):
+        log = [] if logs is not None else None
+        res.append(R.rollout(flow, pol, st, s0[b], x0[b], duration, n, log))
+        if logs is not None:
+            logs.append(log)
+    return res
+
+
+def rel(a, b):
+    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
+
+
+def near_threshold(log, tol=1e-9):
+    return any(abs(e - 1.0) <= tol or abs(e - 0.5) <= tol * 0.5 for e in log)
+
+
+def test_flow_maps_match_the_oracle(remu, handles, model, cmodel, oracle, coracle, rng):
+    for name, m, flow in (("wb", model, R.wb_flow(oracle)), ("centroidal", cmodel, R.cent_flow(coracle))):
+        cent = name == "centroidal"
+        for _ in range(3):
+            x, u = state_input(model, cent, rng)
+            xp = np.zeros(NX)
+            xp[:len(x)] = x
+            xd = np.zeros(NX)
+            remu.ro_flow(handles[name], _p(xp), _p(np.ascontiguousarray(u)), _p(xd))
+            want = flow(xp, u)
+            assert rel(xd, want) <= 1e-12, (name, rel(xd, want))
+
+
+CASES = [(f, g, c) for f in ("wb", "centroidal") for g in GRIDS for c in (R.FEEDFORWARD, R.FEEDBACK)]
+
+
+@pytest.mark.parametrize("formulation,grid,controller", CASES)
+def test_rk4_matches_numpy(remu, handles, model, cmodel, oracle, coracle, formulation, grid, controller):
+    cent = formulation == "centroidal"
+    m = cmodel if cent else model
+    rng = np.random.default_rng(hash((formulation, grid, controller)) & 0xFFFF)
+    case = make_case(model, cent, grid, rng)
+    flow = R.cent_flow(coracle) if cent else R.wb_flow(oracle)
+    st = R.settings(R.RK4, controller, initial_step=0.004)
+    s0 = np.array([0.0, 0.0155, 0.013])           # the last two cross the events at 0.02 and 0.03 (two consecutive intervals)
+    x0 = start_states(model, cent, rng, 3)
+    x, u, status, steps, rej = emu_rollout(remu, handles[formulation], st, case, s0, x0, 2.0 ** -5, 2)
+    ref = ref_rollout(flow, case, st, s0, x0, 2.0 ** -5, 2)
+    for b, (xr, ur, sr, nr, rr) in enumerate(ref):
+        assert status[b] == sr == R.OK and rej[b] == rr == 0
+        assert steps[b] == nr, (b, steps[b], nr)
+        assert rel(x[b], xr) <= 1e-12, (b, rel(x[b], xr))
+        assert rel(u[b], ur) <= 1e-11, (b, rel(u[b], ur))
+    if grid == "events":   # the restarts at 0.02 and 0.03 add steps: 4 ms steps over 2 x 15.625 ms take 8 without events
+        assert steps[1] > 8 and steps[2] > 8
+
+
+@pytest.mark.parametrize("formulation,grid,controller", CASES)
+def test_ode45_matches_numpy(remu, handles, model, cmodel, oracle, coracle, formulation, grid, controller):
+    cent = formulation == "centroidal"
+    m = cmodel if cent else model
+    rng = np.random.default_rng(hash(("ode45", formulation, grid, controller)) & 0xFFFF)
+    case = make_case(model, cent, grid, rng)
+    flow = R.cent_flow(coracle) if cent else R.wb_flow(oracle)
+    for tol in (dict(), dict(abs_tol=1e-10, rel_tol=1e-10)):
+        st = R.settings(R.ODE45, controller, **tol)
+        s0 = np.array([0.0, 0.0155])
+        x0 = start_states(model, cent, rng, 2)
+        x, u, status, steps, rej = emu_rollout(remu, handles[formulation], st, case, s0, x0, 1.0 / 60.0, 1)
+        logs = []
+        ref = ref_rollout(flow, case, st, s0, x0, 1.0 / 60.0, 1, logs)
+        for b, (xr, ur, sr, nr, rr) in enumerate(ref):
+            assert status[b] == sr == R.OK
+            if (steps[b], rej[b]) != (nr, rr):
+                assert near_threshold(logs[b]), (b, steps[b], rej[b], nr, rr)   # only a step at a threshold may go either way
+                continue
+            assert rel(x[b], xr) <= 1e-11, (b, rel(x[b], xr))
+            assert rel(u[b], ur) <= 1e-10, (b, rel(u[b], ur))
+        if tol:
+            assert steps.max() > 2 and rej.max() > 0   # the tight tolerances take more than the 0.015 s step and its remainder
+
+
+@pytest.mark.parametrize("integrator", [R.ODE45, R.RK4])
+@pytest.mark.parametrize("grid", sorted(GRIDS))
+def test_chained_calls_equal_one_multi_sample_call(remu, handles, model, integrator, grid):
+    rng = np.random.default_rng(11)
+    case = make_case(model, False, grid, rng)
+    st = R.settings(integrator, R.FEEDBACK, initial_step=0.004 if integrator == R.RK4 else 0.015)
+    s0 = np.array([0.0, 2.0 ** -7])
+    x0 = start_states(model, False, rng, 2)
+    d = 2.0 ** -6
+    x, u, status, steps, _ = emu_rollout(remu, handles["wb"], st, case, s0, x0, 4 * d, 4)
+    assert (status == R.OK).all()
+    xc, total = x0.copy(), np.zeros(2, np.int64)
+    for j in range(4):
+        xj, uj, sj, nj, _ = emu_rollout(remu, handles["wb"], st, case, s0 + j * d, xc, d, 1)
+        assert (sj == R.OK).all()
+        assert np.array_equal(xj[:, 0], x[:, j]) and np.array_equal(uj[:, 0], u[:, j]), j
+        xc = xj[:, 0]
+        total += nj
+    assert np.array_equal(total, steps)
+
+
+@pytest.mark.parametrize("formulation", ["wb", "centroidal"])
+def test_zero_duration_returns_the_start_state(remu, handles, model, cmodel, formulation):
+    cent = formulation == "centroidal"
+    m = cmodel if cent else model
+    rng = np.random.default_rng(5)
+    case = make_case(model, cent, "events", rng)
+    x0 = start_states(model, cent, rng, 2)
+    if cent:
+        x0[:, CNX:] = 7.0                             # the padding is not live
+    s0 = np.array([0.004, 0.02])
+    for controller in (R.FEEDFORWARD, R.FEEDBACK):
+        st = R.settings(R.ODE45, controller)
+        x, u, status, steps, rej = emu_rollout(remu, handles[formulation], st, case, s0, x0, 0.0, 2)
+        nl = CNX if cent else NX
+        assert (status == R.OK).all() and (steps == 0).all() and (rej == 0).all()
+        for j in range(2):
+            assert np.array_equal(x[:, j, :nl], x0[:, :nl])
+            assert (x[:, j, nl:] == 0.0).all()
+        pol = R.Policy(case["ut"], case["dt"], case["dts"], case["K"], case["uff"], 0, cent)
+        for b in range(2):
+            assert rel(u[b, 0], pol.control(s0[b], x0[b], controller)) <= 1e-13
+
+
+def test_step_cap(remu, handles, model):
+    """RK4 with a 1 ms step over 2^-6 s takes 16 steps: a cap of 15 per second (interval shorter than 1 s) stops every instance, 16 does not."""
+    rng = np.random.default_rng(3)
+    case = make_case(model, False, "uniform", rng)
+    x0 = start_states(model, False, rng, 3)
+    s0 = np.array([0.0, 0.01, 0.02])
+    d = 2.0 ** -6
+    st = R.settings(R.RK4, R.FEEDFORWARD, initial_step=0.001, max_steps_per_second=15.0)
+    x, u, status, steps, _ = emu_rollout(remu, handles["wb"], st, case, s0, x0, 2 * d, 2)
+    assert (status == R.MAX_STEPS).all()
+    assert np.isnan(x).all() and np.isnan(u).all()                     # from the first sample on
+    assert (steps == 15).all()
+    st["max_steps_per_second"] = 16.0
+    x, u, status, steps, _ = emu_rollout(remu, handles["wb"], st, case, s0, x0, 2 * d, 2)
+    assert (status == R.OK).all() and (steps == 32).all()
+    assert np.isfinite(x).all() and np.isfinite(u).all()

@@ -111,6 +111,15 @@ class TermWeights(C.Structure):
                [("torso_sqrt_w", C.c_double * 12), ("cent_foot_sqrt_w", C.c_double * 12), ("ext_torque_sqrt_w", (C.c_double * 6) * 2)]
 
 
+class RolloutSettings(C.Structure):   # include/hsqp_rollout.h: hsqp_rollout_settings
+    _fields_ = [("integrator", C.c_int32), ("controller", C.c_int32), ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("initial_step", C.c_double),
+                ("max_steps_per_second", C.c_double)]
+
+
+ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
+ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
+ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2
+
 STEP_COST, STEP_DUAL, STEP_CONSTRAINT, STEP_ZERO, STEP_FULL = 0, 1, 2, 3, 4
 FLAG_LINESEARCH = 1
 FLAG_SERIAL_RICCATI, FLAG_PARALLEL_RICCATI, SCAN_AUTO_BATCH, SCAN_AUTO_MIN_NODES = 2, 4, 2, 48

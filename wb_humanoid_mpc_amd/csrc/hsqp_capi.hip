@@ -18,6 +18,7 @@
 #include "hsqp_policy.h"
 #include "hsqp_feedback.h"
 #include "../../include/hsqp_feedback.h"
+#include "hsqp_rollout.h"
 #include "hsqp_warm.h"
 #include "hsqp_cent.h"
 #include "hsqp_cent_lq.h"
@@ -896,6 +897,52 @@ __global__ __launch_bounds__(FB_THREADS) void k_feedback_eval(const double* __re
   }
 }
 
+// ---- batched policy rollout (include/hsqp_rollout.h, csrc/hsqp_rollout.h), launched by the rollout entry points only.
+//  k_rollout_window: one workgroup — over the instances, the policy entries the call's times [s0, s0 + duration] reach (the feedback
+//                    controller's gain window [out[0], out[1]]) and whether an s0 is not finite (out[2]).
+//  k_rollout:        one workgroup per instance — the whole integration of the instance (all samples, events, step control).
+constexpr int RO_WIN_THREADS = 256;
+__global__ __launch_bounds__(RO_WIN_THREADS) void k_rollout_window(const double* __restrict__ s0, int B, double duration, const double* __restrict__ dts, int N,
+                                                                   double dt, int uniform, int* __restrict__ out) {
+  __shared__ int lo[RO_WIN_THREADS], hi[RO_WIN_THREADS], bad[RO_WIN_THREADS];
+  const int t = threadIdx.x;
+  int l = N, u = 0, f = 0;
+  for (int b = t; b < B; b += RO_WIN_THREADS) {
+    const double s = s0[b];
+    if (!ro_finite(s)) { f = 1; continue; }
+    const double* db = dts + (size_t)b * N;
+    const PolicySegment g0 = uniform ? policy_segment_uniform(N, dt, s) : policy_segment_grid(N, db, s);
+    const PolicySegment g1 = uniform ? policy_segment_uniform(N, dt, s + duration) : policy_segment_grid(N, db, s + duration);
+    l = g0.ku < l ? g0.ku : l;
+    u = g1.ku + 1 > u ? g1.ku + 1 : u;
+  }
+  lo[t] = l; hi[t] = u; bad[t] = f;
+  __syncthreads();
+  if (t == 0) {
+    for (int i = 1; i < RO_WIN_THREADS; ++i) { l = lo[i] < l ? lo[i] : l; u = hi[i] > u ? hi[i] : u; f |= bad[i]; }
+    out[0] = l; out[1] = u; out[2] = f;
+  }
+}
+
+struct RolloutArgs {
+  const double* ut; const double* dts; int N; double dt;   // resident inputs and grid (dts null: uniform)
+  const double* K; const double* uff; int first, count;     // gain window [B][count] (feedback controller)
+  hsqp_rollout_settings st;
+  const double* s0; const double* x0; double duration; int n;
+  double* x; double* u; int32_t* status; int32_t* steps; int32_t* rejected;
+};
+template <class SW>
+__global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restrict__ dm, RolloutArgs a) {
+  RolloutWS<SW>& w = *reinterpret_cast<RolloutWS<SW>*>(hsqp_smem);
+  const int b = blockIdx.x;
+  const RolloutPolicy p{a.ut + (size_t)b * a.N * NU, a.dts ? a.dts + (size_t)b * a.N : nullptr, a.N, a.dt, a.K ? a.K + (size_t)b * a.count * NU * NX : nullptr,
+                        a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count, dm->formulation == HSQP_FORM_CENTROIDAL ? 1 : 0};
+  rollout_instance(Ctx{(int)threadIdx.x, RO_THREADS, nullptr}, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n,
+                   a.x ? a.x + (size_t)b * a.n * NX : nullptr, a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr,
+                   a.rejected ? a.rejected + b : nullptr);
+}
+static_assert(sizeof(RolloutWS<StageWST<false>>) <= 65536 && sizeof(RolloutWS<CentWST<false>>) <= 65536, "the rollout runs without a dynamic-LDS attribute");
+
 // ---- per-instance performance index from per-node {ne, dt*cost, dt*eq^2, dt*dyn^2} + terminal cost
 __device__ inline void perf_reduce_instance(int b, const DevModel* __restrict__ dm, const double* __restrict__ misc, int misc_stride, const double* __restrict__ x,
                                             const double* __restrict__ par, int N, hsqp_perf* __restrict__ out, const LsState* __restrict__ ls) {
@@ -1009,6 +1056,8 @@ struct hsqp_handle {
   bool have_problem = false, have_solution = false;
   bool have_policy = false;       // the QP / Riccati records and the solution are those of the last successful iteration (feedback entry points)
   DevBuf<double> d_fb;            // staging of hsqp_feedback_policy (host destinations)
+  DevBuf<double> d_ro_gain;       // gain window of the rollout's feedback controller: K [B][count][35][58], then uff [B][count][35] (allocated when first used, sized by the window)
+  DevBuf<char> d_ro;              // staging of the rollout (s0, x0, outputs of the host entry point, window, statuses)
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
   // with non-decreasing stamps
@@ -2033,6 +2082,110 @@ int hsqp_evaluate_feedback_policy(hsqp_handle* h, const double* s, const double*
   { const int rc = feedback_ready(h, "hsqp_evaluate_feedback_policy"); if (rc != HSQP_OK) return rc; }
   if (!s || !x_meas) { h->err = "hsqp_evaluate_feedback_policy: null time offsets or measured states"; return HSQP_ERR_BAD_ARG; }
   return run_policy(h, h->B, true, s, nullptr, x_meas, x, u, tau);
+}
+
+// ---- batched policy rollout (include/hsqp_rollout.h, csrc/hsqp_rollout.h)
+void hsqp_rollout_defaults(hsqp_rollout_settings* s) {
+  if (!s) return;
+  s->integrator = HSQP_ROLLOUT_ODE45;
+  s->controller = HSQP_ROLLOUT_FEEDFORWARD;
+  s->abs_tol = 1e-5;
+  s->rel_tol = 1e-3;
+  s->initial_step = 0.015;
+  s->max_steps_per_second = 10000.0;
+}
+
+// dev: every array argument is device memory of the handle's GPU
+static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const double* s0, const double* x0, double duration, int n, double* x, double* u,
+                        int32_t* status, int32_t* steps, int32_t* rejected, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_rollout_policy_device" : "hsqp_rollout_policy";
+  const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  const auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+  if (!st || !s0 || !x0 || !status) return bad("null settings, s0, x0 or status");
+  if (st->integrator != HSQP_ROLLOUT_ODE45 && st->integrator != HSQP_ROLLOUT_RK4) return bad("unknown integrator");
+  if (st->controller != HSQP_ROLLOUT_FEEDFORWARD && st->controller != HSQP_ROLLOUT_FEEDBACK) return bad("unknown controller");
+  if (!positive(st->abs_tol) || !positive(st->rel_tol) || !positive(st->initial_step) || !positive(st->max_steps_per_second))
+    return bad("tolerances, initial_step and max_steps_per_second must be finite and > 0");
+  if (!(duration >= 0.0) || !std::isfinite(duration)) return bad("duration < 0 or not finite");
+  if (n < 1) return bad("n_samples < 1");
+  { const int rc = feedback_ready(h, who); if (rc != HSQP_OK) return rc; }
+  const size_t B = h->B, nn = (size_t)n;
+  const int N = h->N;
+  const bool cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL, feedback = st->controller == HSQP_ROLLOUT_FEEDBACK;
+  // staging: window [3] | status, steps, rejected [B] each | (host entry point) s0 [B], x0 [B][58], x [B][n][58], u [B][n][35]
+  const size_t o_win = 0, o_cnt = o_win + 256, o_s0 = o_cnt + align256(B * 3 * 4), o_x0 = o_s0 + (dev ? 0 : align256(B * 8)),
+               o_x = o_x0 + (dev ? 0 : align256(B * NX * 8)), o_u = o_x + (dev || !x ? 0 : align256(B * nn * NX * 8)),
+               total = o_u + (dev || !u ? 0 : align256(B * nn * NU * 8));
+  DEV_ENSURE(h->d_ro, total, "rollout staging");
+  char* base = h->d_ro.p;
+  int* d_win = reinterpret_cast<int*>(base + o_win);
+  int32_t* d_status = reinterpret_cast<int32_t*>(base + o_cnt);
+  int32_t* d_steps = dev ? steps : (steps ? d_status + B : nullptr);
+  int32_t* d_rej = dev ? rejected : (rejected ? d_status + 2 * B : nullptr);
+  const double* d_s0 = dev ? s0 : reinterpret_cast<const double*>(base + o_s0);
+  const double* d_x0 = dev ? x0 : reinterpret_cast<const double*>(base + o_x0);
+  double* d_x = dev ? x : (x ? reinterpret_cast<double*>(base + o_x) : nullptr);
+  double* d_u = dev ? u : (u ? reinterpret_cast<double*>(base + o_u) : nullptr);
+  StickyError step{h};
+  if (!dev) {
+    step(hipMemcpyAsync(base + o_s0, s0, B * 8, hipMemcpyHostToDevice, h->stream), "upload s0");
+    step(hipMemcpyAsync(base + o_x0, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
+  }
+  const double* dts = h->uniform_grid ? nullptr : (const double*)h->d_dt;
+  HSQP_LAUNCH(k_rollout_window, dim3(1), dim3(RO_WIN_THREADS), 0, h->stream, d_s0, (int)B, duration, (const double*)h->d_dt, N, h->dt, h->uniform_grid ? 1 : 0, d_win);
+  step(hipGetLastError(), "k_rollout_window");
+  int win[3] = {0, 0, 0};
+  step(hipMemcpyAsync(win, d_win, sizeof(win), hipMemcpyDeviceToHost, h->stream), "download window");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  if (win[2]) return bad("non-finite s0");
+  const int first = win[0], count = win[1] - win[0] + 1;
+  if (first < 0 || count < 2 || first + count > N + 1) { h->err = std::string(who) + ": policy window out of range"; return HSQP_ERR_HIP; }
+  double* dK = nullptr;
+  double* duff = nullptr;
+  if (feedback) {
+    const size_t nK = B * count * NU * NX;
+    DEV_ENSURE(h->d_ro_gain, (nK + B * count * NU) * 8, "rollout gain window");
+    dK = h->d_ro_gain.p;
+    duff = dK + nK;
+    HSQP_LAUNCH(k_feedback_gains, dim3(count, B), dim3(FB_THREADS), sizeof(FeedbackWS), h->stream, (const double*)h->d_qp, (const double*)h->d_ric,
+                (const double*)h->d_xnew, (const double*)h->d_unew, (const double*)h->d_dt, N, first, count, cent ? 1 : 0, dK, duff);
+    step(hipGetLastError(), "k_feedback_gains");
+  }
+  const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, d_status, d_steps, d_rej};
+  if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
+  else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
+  step(hipGetLastError(), "k_rollout");
+  std::vector<int32_t> hs(B);
+  step(hipMemcpyAsync(hs.data(), d_status, B * 4, hipMemcpyDeviceToHost, h->stream), "download status");
+  if (dev) step(hipMemcpyAsync(status, d_status, B * 4, hipMemcpyDeviceToDevice, h->stream), "copy status");
+  else {
+    if (x) step(hipMemcpyAsync(x, d_x, B * nn * NX * 8, hipMemcpyDeviceToHost, h->stream), "download x");
+    if (u) step(hipMemcpyAsync(u, d_u, B * nn * NU * 8, hipMemcpyDeviceToHost, h->stream), "download u");
+    if (steps) step(hipMemcpyAsync(steps, d_steps, B * 4, hipMemcpyDeviceToHost, h->stream), "download steps");
+    if (rejected) step(hipMemcpyAsync(rejected, d_rej, B * 4, hipMemcpyDeviceToHost, h->stream), "download rejected");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  if (!dev) memcpy(status, hs.data(), B * 4);
+  int nonfinite = -1, capped = -1;
+  for (size_t b = 0; b < B; ++b) {
+    if (hs[b] == HSQP_ROLLOUT_NONFINITE && nonfinite < 0) nonfinite = (int)b;
+    if (hs[b] == HSQP_ROLLOUT_MAX_STEPS && capped < 0) capped = (int)b;
+  }
+  if (nonfinite >= 0) { h->err = std::string(who) + ": instance " + std::to_string(nonfinite) + " produced a non-finite value"; return HSQP_ERR_NUMERIC; }
+  if (capped >= 0) { h->err = std::string(who) + ": instance " + std::to_string(capped) + " hit the step cap"; return HSQP_ERR_NOT_CONVERGED; }
+  return HSQP_OK;
+}
+
+int hsqp_rollout_policy(hsqp_handle* h, const hsqp_rollout_settings* st, const double* s0, const double* x0, double duration, int n_samples, double* x,
+                        double* u, int32_t* status, int32_t* steps, int32_t* rejected) {
+  return rollout_impl(h, st, s0, x0, duration, n_samples, x, u, status, steps, rejected, false);
+}
+int hsqp_rollout_policy_device(hsqp_handle* h, const hsqp_rollout_settings* st, const double* d_s0, const double* d_x0, double duration, int n_samples,
+                               double* d_x, double* d_u, int32_t* d_status, int32_t* d_steps, int32_t* d_rejected) {
+  return rollout_impl(h, st, d_s0, d_x0, duration, n_samples, d_x, d_u, d_status, d_steps, d_rejected, true);
 }
 
 int hsqp_last_kernel_ms(hsqp_handle* h, double out_ms[5]) {

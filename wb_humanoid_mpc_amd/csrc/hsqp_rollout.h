@@ -1,0 +1,310 @@
+// Batched policy rollout (include/hsqp_rollout.h; upstream ocs2 MRT_BASE::rolloutPolicy: a TimeTriggeredRollout of the flow map under the
+// current controller).  One workgroup integrates one instance over all its sample intervals: the adaptive loop, the restarts at samples and
+// events and the step control run inside, every decision uniform across the workgroup (each thread runs the same scalar control on values
+// read from LDS after a barrier; the error norm is a workgroup reduction).
+//   flow maps:   whole-body  xdot = [x[29..57], a_b, u[12..34]]  (stage_topology + stage_eval<false>, hsqp_model.h, as policy_node fills it);
+//                centroidal  xdot = [12 dense rows of cent_lane_flow<double> (CK_NONE), u[12..34]]  (hsqp_cent_lq.h)
+//   controllers: feed-forward  u(s) = the input hsqp_evaluate_policy interpolates (policy_segment_*, hsqp_feedback.h);
+//                feedback      u(s, x) = uff(s) + K(s) x blended on the same segment in the order of k_feedback_eval (hsqp_capi.hip), from a
+//                              window of policy entries [first, first + count) formed beforehand by k_feedback_gains
+//   integrators: Dormand–Prince 5(4) with FSAL and odeint's step control (ODE45), classical RK4 with a fixed step; the step-control
+//                rules and the step cap are restated from memory of boost odeint / ocs2 (include/hsqp_rollout.h: the assumptions).
+// The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp).
+#pragma once
+#include "hsqp_policy.h"
+#include "hsqp_cent_lq.h"
+#include "hsqp_feedback.h"
+#include "../../include/hsqp_rollout.h"
+
+namespace hsqp {
+
+constexpr int RO_THREADS = 128;                  // threads of the rollout workgroup (the stage evaluations' width: k_policy_torques)
+constexpr int RO_MAX_REJECTS = 500;              // consecutive rejected ODE45 steps that end an instance (odeint's failed-step checker)
+
+// The resident policy of ONE instance
+struct RolloutPolicy {
+  const double* ut;       // [N][NU] optimal inputs (feed-forward controller)
+  const double* dts;      // [N] interval lengths (0: event) of a non-uniform grid, or null: uniform grid of spacing dt (no events)
+  int N;
+  double dt;
+  const double* K;        // [count][NU][NX] gain entries first .. first + count - 1 (feedback controller)
+  const double* uff;      // [count][NU]
+  int first, count;
+  int cent;               // centroidal handle: 35 live states
+};
+
+template <class SW>
+struct RolloutWS {
+  SW sw;                  // stage workspace of the flow evaluation (StageWST<false> / CentWST<false>)
+  double k[7][NX];        // stage derivatives (k[0]: at the start of the step)
+  double x[NX];           // state at the start of the step
+  double xs[NX];          // stage state
+  double xn[NX];          // state at the end of the step
+  double u[NU];           // controller input of the evaluation
+  double red[RO_THREADS]; // per-thread partials of the workgroup reductions (error norm, finiteness)
+};
+
+HSQP_HD bool ro_finite(double v) { return v - v == 0.0; }
+
+// ---- flow maps: xdot [NX] of (x, u) through the workspace.  Entries of the centroidal padding are zero.
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws) { stage_topology(ctx, dm, ws); }
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, CentWST<false>& ws) { cent_ws_topology(ctx, dm, ws); }
+
+HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, const double* x, const double* u, double* xdot) {
+  WG_FOR(ctx, i, NV + NV + NJ + 12) {
+    if (i < NV) ws.q[i] = x[i];
+    else if (i < 2 * NV) ws.v[i - NV] = x[i];
+    else if (i < 2 * NV + NJ) ws.qddj[i - 2 * NV] = u[12 + i - 2 * NV];
+    else ws.W[i - 2 * NV - NJ] = u[i - 2 * NV - NJ];
+  }
+  WG_SYNC(ctx);
+  stage_eval<false>(ctx, dm, ws);
+  WG_FOR(ctx, i, NX) {
+    xdot[i] = i < NV ? x[NV + i] : (i < NV + 6 ? ws.ab[i - NV] : u[12 + (i - NV - 6)]);
+  }
+  WG_SYNC(ctx);
+}
+
+HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, CentWST<false>& ws, const double* x, const double* u, double* xdot) {
+  WG_FOR(ctx, i, CNX + NU) { if (i < CNX) ws.x[i] = x[i]; else ws.u[i - CNX] = u[i - CNX]; }
+  WG_SYNC(ctx);
+  cent_stage_values(ctx, dm, ws, 0, 0.0);
+  WG_FOR(ctx, it, 1) {
+    CentBase<double> base;
+    double xd[12];
+    cent_lane_flow<double>(dm, ws, CentCol{CK_NONE, 0}, xd, base);
+    for (int r = 0; r < 12; ++r) xdot[r] = xd[r];
+  }
+  WG_FOR(ctx, i, NX - 12) xdot[12 + i] = i < CNX - 12 ? u[12 + i] : 0.0;
+  WG_SYNC(ctx);
+}
+
+// ---- controller input u [NU] at s seconds after the first node and the state x
+HSQP_HD void rollout_control(const Ctx& ctx, const RolloutPolicy& p, int controller, double s, const double* x, double* u) {
+  const PolicySegment g = p.dts ? policy_segment_grid(p.N, p.dts, s) : policy_segment_uniform(p.N, p.dt, s);
+  if (controller == HSQP_ROLLOUT_FEEDFORWARD) {
+    const int ku = g.ku;
+    const double au = g.au;
+    WG_FOR(ctx, c, NU) u[c] = p.N >= 2 ? (1.0 - au) * p.ut[(size_t)ku * NU + c] + au * p.ut[(size_t)(ku + 1) * NU + c] : p.ut[c];
+  } else {
+    // entries ku, ku + 1 of the policy inside the window (the window covers every time of the call; the clamp only keeps reads in bounds)
+    int e = g.ku - p.first;
+    e = e < 0 ? 0 : (e > p.count - 2 ? p.count - 2 : e);
+    const double* K0 = p.K + (size_t)e * NU * NX;
+    const double* K1 = K0 + NU * NX;
+    const double* u0 = p.uff + (size_t)e * NU;
+    const double* u1 = u0 + NU;
+    const double a = g.au;
+    const int nc = p.cent ? CNX : NX;
+    WG_FOR(ctx, r, NU) {
+      double kx = 0.0;
+      for (int c = 0; c < nc; ++c) kx += ((1.0 - a) * K0[(size_t)r * NX + c] + a * K1[(size_t)r * NX + c]) * x[c];
+      u[r] = ((1.0 - a) * u0[r] + a * u1[r]) + kx;
+    }
+  }
+  WG_SYNC(ctx);
+}
+
+// one evaluation of the closed loop: k = f(x, u(s, x)) (a non-finite input reaches k: its joint part is copied, the wrenches enter a_b)
+template <class SW>
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, int controller, double s, const double* x,
+                          double* k) {
+  rollout_control(ctx, p, controller, s, x, w.u);
+  rollout_flow(ctx, dm, w.sw, x, w.u, k);
+}
+
+// whether any of the first n entries of rows r0 .. r1 - 1 of v (row stride NX) is not finite: a workgroup reduction, uniform
+template <class SW>
+HSQP_HD bool rollout_nonfinite(const Ctx& ctx, RolloutWS<SW>& w, const double* v, int r0, int r1, int n) {
+  double f = 0.0;
+  WG_FOR(ctx, i, n) for (int r = r0; r < r1; ++r) if (!ro_finite(v[(size_t)r * NX + i])) f = 1.0;
+  w.red[ctx.tid] = f;
+  WG_SYNC(ctx);
+  bool any = false;
+  for (int t = 0; t < ctx.nthreads; ++t) any = any || w.red[t] != 0.0;
+  WG_SYNC(ctx);
+  return any;
+}
+
+// Dormand–Prince 5(4) tableau: c, a (row s: the ns = s coefficients of stage s), the 5th-order weights b (= row 6 of a), b - b* (error)
+struct Dopri {
+  static constexpr double c2 = 1.0 / 5.0, c3 = 3.0 / 10.0, c4 = 4.0 / 5.0, c5 = 8.0 / 9.0;
+  static constexpr double a21 = 1.0 / 5.0;
+  static constexpr double a31 = 3.0 / 40.0, a32 = 9.0 / 40.0;
+  static constexpr double a41 = 44.0 / 45.0, a42 = -56.0 / 15.0, a43 = 32.0 / 9.0;
+  static constexpr double a51 = 19372.0 / 6561.0, a52 = -25360.0 / 2187.0, a53 = 64448.0 / 6561.0, a54 = -212.0 / 729.0;
+  static constexpr double a61 = 9017.0 / 3168.0, a62 = -355.0 / 33.0, a63 = 46732.0 / 5247.0, a64 = 49.0 / 176.0, a65 = -5103.0 / 18656.0;
+  static constexpr double b1 = 35.0 / 384.0, b3 = 500.0 / 1113.0, b4 = 125.0 / 192.0, b5 = -2187.0 / 6784.0, b6 = 11.0 / 84.0;
+  static constexpr double e1 = 35.0 / 384.0 - 5179.0 / 57600.0, e3 = 500.0 / 1113.0 - 7571.0 / 16695.0, e4 = 125.0 / 192.0 - 393.0 / 640.0,
+                          e5 = -2187.0 / 6784.0 + 92097.0 / 339200.0, e6 = 11.0 / 84.0 - 187.0 / 2100.0, e7 = -1.0 / 40.0;
+};
+
+// Row s of the tableau of either integrator: the coefficient of k[j] in the state of stage s (ODE45: s = 1 .. 6, row 6 = the 5th-order
+// weights; RK4: s = 1 .. 3), and the stage's time as a fraction of the step (c)
+HSQP_HD double rollout_a(bool ode45, int s, int j) {
+  if (!ode45) return j == s - 1 ? (s == 3 ? 1.0 : 0.5) : 0.0;
+  switch (s) {
+    case 1: return Dopri::a21;
+    case 2: return j == 0 ? Dopri::a31 : Dopri::a32;
+    case 3: return j == 0 ? Dopri::a41 : (j == 1 ? Dopri::a42 : Dopri::a43);
+    case 4: return j == 0 ? Dopri::a51 : (j == 1 ? Dopri::a52 : (j == 2 ? Dopri::a53 : Dopri::a54));
+    case 5: return j == 0 ? Dopri::a61 : (j == 1 ? Dopri::a62 : (j == 2 ? Dopri::a63 : (j == 3 ? Dopri::a64 : Dopri::a65)));
+    default: return j == 0 ? Dopri::b1 : (j == 1 ? 0.0 : (j == 2 ? Dopri::b3 : (j == 3 ? Dopri::b4 : (j == 4 ? Dopri::b5 : Dopri::b6))));
+  }
+}
+HSQP_HD double rollout_c(bool ode45, int s) {
+  if (!ode45) return s == 0 ? 0.0 : (s == 3 ? 1.0 : 0.5);
+  return s == 0 ? 0.0 : (s == 1 ? Dopri::c2 : (s == 2 ? Dopri::c3 : (s == 3 ? Dopri::c4 : (s == 4 ? Dopri::c5 : 1.0))));
+}
+
+// out = x + h sum_{j < s} a_sj k[j] over the nl live entries (the accumulation runs in j order)
+template <class SW>
+HSQP_HD void rollout_combine(const Ctx& ctx, RolloutWS<SW>& w, int nl, bool ode45, int s, double h, double* out) {
+  WG_FOR(ctx, i, nl) {
+    double acc = 0.0;
+    for (int j = 0; j < s; ++j) acc += rollout_a(ode45, s, j) * w.k[j][i];
+    out[i] = w.x[i] + h * acc;
+  }
+  WG_SYNC(ctx);
+}
+
+// The stage evaluations of one step of length h from (t, w.x) ending at tn: k[first_stage .. last_stage] (ODE45: 1 .. 6, k[0] is the FSAL
+// derivative, the stage-6 state — the 5th-order solution — goes to w.xn; RK4: 0 .. 3).  One call site of the flow evaluation per step.
+template <class SW>
+HSQP_HD void rollout_stages(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, int controller, bool ode45, int nl, double t,
+                            double h, double tn) {
+  for (int s = ode45 ? 1 : 0; s < (ode45 ? 7 : 4); ++s) {
+    const double c = rollout_c(ode45, s);
+    double* xe = s == 6 ? w.xn : w.xs;
+    if (s > 0) rollout_combine(ctx, w, nl, ode45, s, h, xe);
+    rollout_eval(ctx, dm, w, p, controller, c == 1.0 ? tn : t + c * h, s > 0 ? xe : w.x, w.k[s]);
+  }
+}
+
+// err = max_i |h sum e_j k_j| / (abs_tol + rel_tol (|x_i| + h |k1_i|)) over the live entries (NaN propagates); uniform across the workgroup
+template <class SW>
+HSQP_HD double rollout_error(const Ctx& ctx, RolloutWS<SW>& w, int nl, double h, double abs_tol, double rel_tol) {
+  double m = 0.0;
+  WG_FOR(ctx, i, nl) {
+    const double e = h * (Dopri::e1 * w.k[0][i] + Dopri::e3 * w.k[2][i] + Dopri::e4 * w.k[3][i] + Dopri::e5 * w.k[4][i] + Dopri::e6 * w.k[5][i] +
+                          Dopri::e7 * w.k[6][i]);
+    const double r = fabs(e) / (abs_tol + rel_tol * (fabs(w.x[i]) + h * fabs(w.k[0][i])));
+    if (!(r <= m)) m = r;
+  }
+  w.red[ctx.tid] = m;
+  WG_SYNC(ctx);
+  double err = 0.0;
+  for (int t = 0; t < ctx.nthreads; ++t) { const double v = w.red[t]; if (!(v <= err)) err = v; }
+  WG_SYNC(ctx);
+  return err;
+}
+
+// Integrates w.x from ta to tb (no event inside) and returns HSQP_ROLLOUT_*.  acc: accepted steps of the sample interval so far (cap: its
+// limit), nacc / nrej: the instance's accepted / rejected steps.
+template <class SW>
+HSQP_HD int rollout_segment(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, const hsqp_rollout_settings& st, double ta,
+                            double tb, double cap, int& acc, int& nacc, int& nrej) {
+  const int nl = p.cent ? CNX : NX;
+  const bool ode45 = st.integrator == HSQP_ROLLOUT_ODE45;
+  double h = st.initial_step < tb - ta ? st.initial_step : tb - ta;
+  double t = ta;
+  int fails = 0;
+  if (ode45) {   // FSAL: the derivative at the start of the segment, then the last stage of every accepted step
+    rollout_eval(ctx, dm, w, p, st.controller, t, w.x, w.k[0]);
+    if (rollout_nonfinite(ctx, w, &w.k[0][0], 0, 1, nl)) return HSQP_ROLLOUT_NONFINITE;
+  }
+  while (t < tb) {
+    if ((double)acc >= cap) return HSQP_ROLLOUT_MAX_STEPS;
+    if (ode45) {
+      const bool last = tb - t <= h;
+      if (last) h = tb - t;
+      const double tn = last ? tb : t + h;
+      rollout_stages(ctx, dm, w, p, st.controller, true, nl, t, h, tn);
+      if (rollout_nonfinite(ctx, w, &w.k[0][0], 1, 7, nl)) return HSQP_ROLLOUT_NONFINITE;
+      const double err = rollout_error(ctx, w, nl, h, st.abs_tol, st.rel_tol);
+      if (!(err <= 1.0)) {
+        if (err != err) return HSQP_ROLLOUT_NONFINITE;
+        const double f = 0.9 * pow(err, -1.0 / 3.0);
+        h *= f > 0.2 ? f : 0.2;
+        ++nrej;
+        if (++fails > RO_MAX_REJECTS) return HSQP_ROLLOUT_MAX_STEPS;
+        continue;
+      }
+      fails = 0;
+      WG_FOR(ctx, i, nl) { w.x[i] = w.xn[i]; w.k[0][i] = w.k[6][i]; }
+      WG_SYNC(ctx);
+      t = tn;
+      ++acc; ++nacc;
+      if (err < 0.5) {
+        const double e = err > 1.0 / 3125.0 ? err : 1.0 / 3125.0;   // max(err, 5^-5)
+        h *= 0.9 * pow(e, -1.0 / 5.0);
+      }
+    } else {
+      const bool last = tb - t <= h;
+      const double hs = last ? tb - t : h, tn = last ? tb : t + hs;
+      rollout_stages(ctx, dm, w, p, st.controller, false, nl, t, hs, tn);
+      if (rollout_nonfinite(ctx, w, &w.k[0][0], 0, 4, nl)) return HSQP_ROLLOUT_NONFINITE;
+      WG_FOR(ctx, i, nl) w.x[i] = w.x[i] + hs / 6.0 * (w.k[0][i] + 2.0 * w.k[1][i] + 2.0 * w.k[2][i] + w.k[3][i]);
+      WG_SYNC(ctx);
+      t = tn;
+      ++acc; ++nacc;
+    }
+  }
+  return HSQP_ROLLOUT_OK;
+}
+
+// the first event stamp of the grid strictly inside (t, tb), else tb (stamps summed in the order of policy_segment_grid)
+HSQP_HD double rollout_next_event(const RolloutPolicy& p, double t, double tb) {
+  if (!p.dts) return tb;
+  double tk = 0.0;
+  for (int k = 0; k < p.N; ++k) {
+    if (p.dts[k] == 0.0 && tk > t && tk < tb) return tk;
+    tk += p.dts[k];
+  }
+  return tb;
+}
+
+// sample j of n: s0 + duration (j + 1) / n, the last one s0 + duration exactly
+HSQP_HD double rollout_sample_time(double s0, double duration, int j, int n) { return j + 1 == n ? s0 + duration : s0 + duration * (double)(j + 1) / (double)n; }
+
+// One instance: x0 at s0, n samples over duration.  xo [n][NX], uo [n][NU] (may be null); the counters are written by item 0.
+template <class SW>
+HSQP_HD void rollout_instance(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, const hsqp_rollout_settings& st, double s0,
+                              const double* x0, double duration, int n, double* xo, double* uo, int32_t* status, int32_t* steps, int32_t* rejected) {
+  const int nl = p.cent ? CNX : NX;
+  rollout_topology(ctx, dm, w.sw);
+  WG_FOR(ctx, i, NX) w.x[i] = i < nl ? x0[i] : 0.0;
+  WG_SYNC(ctx);
+  int stat = HSQP_ROLLOUT_OK, nacc = 0, nrej = 0;
+  double ta = s0;
+  for (int j = 0; j < n; ++j) {
+    const double tb = rollout_sample_time(s0, duration, j, n);
+    if (stat == HSQP_ROLLOUT_OK) {
+      const double len = tb - ta;
+      const double cap = st.max_steps_per_second * (len > 1.0 ? len : 1.0);
+      int acc = 0;
+      double t = ta;
+      while (stat == HSQP_ROLLOUT_OK && t < tb) {
+        const double te = rollout_next_event(p, t, tb);
+        stat = rollout_segment(ctx, dm, w, p, st, t, te, cap, acc, nacc, nrej);
+        t = te;
+      }
+      if (stat == HSQP_ROLLOUT_OK) {
+        rollout_control(ctx, p, st.controller, tb, w.x, w.u);
+        if (rollout_nonfinite(ctx, w, w.u, 0, 1, NU)) stat = HSQP_ROLLOUT_NONFINITE;
+      }
+    }
+    const bool ok = stat == HSQP_ROLLOUT_OK;
+    const double nan = __builtin_nan("");
+    if (xo) WG_FOR(ctx, i, NX) xo[(size_t)j * NX + i] = ok ? (i < nl ? w.x[i] : 0.0) : nan;
+    if (uo) WG_FOR(ctx, r, NU) uo[(size_t)j * NU + r] = ok ? w.u[r] : nan;
+    ta = tb;
+  }
+  WG_FOR(ctx, i, 1) {
+    *status = stat;
+    if (steps) *steps = nacc;
+    if (rejected) *rejected = nrej;
+  }
+}
+
+}  // namespace hsqp

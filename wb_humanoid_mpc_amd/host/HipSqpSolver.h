@@ -15,6 +15,7 @@
 
 #include "../../include/hsqp.h"
 #include "../../include/hsqp_feedback.h"
+#include "../../include/hsqp_rollout.h"
 
 namespace hsqp_host {
 
@@ -138,6 +139,20 @@ class HipSqpSolver {
     state.assign(B * HSQP_NX, 0.0); input.assign(B * HSQP_NU, 0.0); jointTorques.assign(B * HSQP_NJ, 0.0);
     const int rc = hsqp_evaluate_feedback_policy(h_, secondsAfterStart.data(), measuredState.data(), state.data(), input.data(), jointTorques.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_evaluate_feedback_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** MRT_BASE::rolloutPolicy for every instance of the last run (include/hsqp_rollout.h): instance b from x0[b] (one HSQP_NX row per
+   *  instance) at secondsAfterStart[b], under the resident policy with the integrator / controller of `st`; x [batch][nSamples][HSQP_NX],
+   *  u [batch][nSamples][HSQP_NU] at the nSamples times secondsAfterStart[b] + duration (j + 1) / nSamples, status [batch].  A failed
+   *  instance (step cap, non-finite value) throws like every other failure; the outputs are complete for the others. */
+  void rolloutPolicy(const hsqp_rollout_settings& st, const std::vector<double>& secondsAfterStart, const std::vector<double>& x0, double duration, int nSamples,
+                     std::vector<double>& x, std::vector<double>& u, std::vector<int32_t>& status) {
+    const size_t B = (size_t)solution_.batch;
+    if (secondsAfterStart.size() != B || x0.size() != B * HSQP_NX || nSamples < 1)
+      throw std::runtime_error("[HipSqpSolver] rolloutPolicy: one time and one start state per instance, and nSamples >= 1 expected");
+    x.assign(B * nSamples * HSQP_NX, 0.0); u.assign(B * nSamples * HSQP_NU, 0.0); status.assign(B, 0);
+    const int rc = hsqp_rollout_policy(h_, &st, secondsAfterStart.data(), x0.data(), duration, nSamples, x.data(), u.data(), status.data(), nullptr, nullptr);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_rollout_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
   const PrimalSolution& getPrimalSolution() const { return solution_; }

@@ -51,6 +51,10 @@ struct HipSqpAdaptorConfig {
   // WeightCompInitializer (the device builds that one: state kept, weight-compensating input of the node's contact flags).  The trajectories
   // are still downloaded (getPrimalSolution).  The runImpl overload with an external PrimalSolution takes the host path for that call.
   bool deviceWarmStart = false;
+  // rolloutPolicy's integrator (include/hsqp_rollout.h): the task.info rollout block by default; the controller field is ignored — the rollout
+  // follows sqp::Settings::useFeedbackPolicy like the PrimalSolution's controller.  INTEGRATION.md: filling it from interface.rolloutSettings().
+  hsqp_rollout_settings rollout = rolloutDefaults();
+  static hsqp_rollout_settings rolloutDefaults() { hsqp_rollout_settings s; hsqp_rollout_defaults(&s); return s; }
 };
 
 struct HipSqpBenchmarks {         // SqpSolver::getBenchmarks() of the fork (SqpBenchmarksPublisher.cpp:44-57), accumulated seconds
@@ -172,6 +176,21 @@ class HipSqpSolverAdaptor final : public SolverBase {
     impl_.evaluatePolicy({time - primal_.timeTrajectory_.front()}, x, u, tau);
     state = vector_t(cfg_.stateDim); input = vector_t(HSQP_NU); jointTorques = vector_t(HSQP_NJ);
     std::copy_n(x.data(), cfg_.stateDim, state.data()); std::copy_n(u.data(), HSQP_NU, input.data()); std::copy_n(tau.data(), HSQP_NJ, jointTorques.data());
+  }
+  /** MRT_BASE::rolloutPolicy (the reference's dummy-simulation loop after mrt.initRollout): the plant moved from currentState at
+   *  currentTime over timeStep under the controller of the last solution (FeedforwardController, or LinearController with useFeedbackPolicy),
+   *  on the device with cfg_.rollout's integrator: mpcState = the state at currentTime + timeStep, mpcInput = the controller's input there.
+   *  (The mode is the caller's mode schedule's: it is not part of the device result.) */
+  void rolloutPolicy(scalar_t currentTime, const vector_t& currentState, scalar_t timeStep, vector_t& mpcState, vector_t& mpcInput) {
+    if (primal_.timeTrajectory_.empty()) throw std::runtime_error("[HipSqpSolverAdaptor] rolloutPolicy: no solution");
+    hsqp_rollout_settings st = cfg_.rollout;
+    st.controller = settings_.useFeedbackPolicy ? HSQP_ROLLOUT_FEEDBACK : HSQP_ROLLOUT_FEEDFORWARD;
+    std::vector<double> x0(HSQP_NX, 0.0), x, u;
+    std::vector<int32_t> status;
+    std::copy_n(currentState.data(), cfg_.stateDim, x0.data());
+    impl_.rolloutPolicy(st, {currentTime - primal_.timeTrajectory_.front()}, x0, timeStep, 1, x, u, status);
+    mpcState = vector_t(cfg_.stateDim); mpcInput = vector_t(HSQP_NU);
+    std::copy_n(x.data(), cfg_.stateDim, mpcState.data()); std::copy_n(u.data(), HSQP_NU, mpcInput.data());
   }
 
  private:

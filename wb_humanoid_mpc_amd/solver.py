@@ -90,6 +90,12 @@ def load_library():
     lib.hsqp_feedback_policy.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
     lib.hsqp_feedback_policy_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
     lib.hsqp_evaluate_feedback_policy.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
+    # include/hsqp_rollout.h
+    _ip = C.POINTER(C.c_int32)
+    lib.hsqp_rollout_defaults.argtypes = [C.POINTER(_abi.RolloutSettings)]
+    lib.hsqp_rollout_defaults.restype = None
+    lib.hsqp_rollout_policy.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
+    lib.hsqp_rollout_policy_device.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -399,6 +405,61 @@ class HipSqpSolver:
         self._check(self.lib.hsqp_evaluate_feedback_policy(self.h, s.ctypes.data_as(_dp), x_meas.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
                                                            u.ctypes.data_as(_dp), tau.ctypes.data_as(_dp)))
         return x, u, tau
+
+    # ---- batched policy rollout (include/hsqp_rollout.h; ocs2 MRT_BASE::rolloutPolicy)
+    _INTEGRATORS = {"ode45": _abi.ROLLOUT_ODE45, "rk4": _abi.ROLLOUT_RK4}
+    _CONTROLLERS = {"feedforward": _abi.ROLLOUT_FEEDFORWARD, "feedback": _abi.ROLLOUT_FEEDBACK}
+
+    def rollout_settings(self, integrator="ode45", controller="feedforward", **tolerances):
+        """hsqp_rollout_settings: hsqp_rollout_defaults (the task.info rollout block) with the named fields replaced (abs_tol, rel_tol,
+        initial_step, max_steps_per_second)."""
+        st = _abi.RolloutSettings()
+        self.lib.hsqp_rollout_defaults(C.byref(st))
+        st.integrator = self._INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
+        st.controller = self._CONTROLLERS[controller] if isinstance(controller, str) else int(controller)
+        for k, v in tolerances.items():
+            if k not in ("abs_tol", "rel_tol", "initial_step", "max_steps_per_second"):
+                raise TypeError(f"unknown rollout setting {k!r}")
+            setattr(st, k, float(v))
+        return st
+
+    def rollout_policy(self, s0, x0, duration, n_samples=1, integrator="ode45", controller="feedforward", **tolerances):
+        """Every instance from x0[b] at s0[b] under the resident policy: dict(x[B, n, 58], u[B, n, 35], status[B], steps[B], rejected[B]).
+        A failed instance (step cap: HSQP_ERR_NOT_CONVERGED, non-finite: HSQP_ERR_NUMERIC) raises HsqpError with the complete result of the
+        call as its `result` attribute."""
+        B = self._shape[0] if self._shape else 1      # (no problem uploaded: the library reports it)
+        st = self.rollout_settings(integrator, controller, **tolerances)
+        s0 = _c(np.broadcast_to(s0, (B,)))
+        x0 = _c(np.broadcast_to(x0, (B, _abi.NX)))
+        n = max(int(n_samples), 1)
+        out = dict(x=np.zeros((B, n, _abi.NX)), u=np.zeros((B, n, _abi.NU)), status=np.zeros(B, np.int32), steps=np.zeros(B, np.int32),
+                   rejected=np.zeros(B, np.int32))
+        ip = C.POINTER(C.c_int32)
+        rc = self.lib.hsqp_rollout_policy(self.h, C.byref(st), s0.ctypes.data_as(_dp), x0.ctypes.data_as(_dp), C.c_double(duration), int(n_samples),
+                                          out["x"].ctypes.data_as(_dp), out["u"].ctypes.data_as(_dp), out["status"].ctypes.data_as(ip),
+                                          out["steps"].ctypes.data_as(ip), out["rejected"].ctypes.data_as(ip))
+        self._check_rollout(rc, out)
+        return out
+
+    def rollout_policy_device(self, s0_ptr, x0_ptr, duration, n_samples=1, x_ptr=0, u_ptr=0, status_ptr=0, steps_ptr=0, rejected_ptr=0,
+                              integrator="ode45", controller="feedforward", **tolerances):
+        """hsqp_rollout_policy_device: the same with every array in device memory (addresses; 0 = not wanted for x, u, steps, rejected).
+        Returns the library's return code after raising for everything but a failed instance (HSQP_ERR_NOT_CONVERGED / HSQP_ERR_NUMERIC)."""
+        st = self.rollout_settings(integrator, controller, **tolerances)
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        icast = lambda a: C.cast(C.c_void_p(int(a)), C.POINTER(C.c_int32)) if a else None  # noqa: E731
+        rc = self.lib.hsqp_rollout_policy_device(self.h, C.byref(st), cast(s0_ptr), cast(x0_ptr), C.c_double(duration), int(n_samples), cast(x_ptr),
+                                                 cast(u_ptr), icast(status_ptr), icast(steps_ptr), icast(rejected_ptr))
+        if rc not in (0, _abi.ERR_NOT_CONVERGED, _abi.ERR_NUMERIC):
+            self._check(rc)
+        return rc
+
+    def _check_rollout(self, rc, result):
+        if rc != 0:
+            err = HsqpError(rc, self.lib.hsqp_last_error(self.h).decode())
+            if rc in (_abi.ERR_NOT_CONVERGED, _abi.ERR_NUMERIC):
+                err.result = result
+            raise err
 
     def joint_torques(self, x, u):
         x, u = _c(np.atleast_2d(x)), _c(np.atleast_2d(u))
