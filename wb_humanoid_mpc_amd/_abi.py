@@ -116,6 +116,17 @@ class RolloutSettings(C.Structure):   # include/hsqp_rollout.h: hsqp_rollout_set
                 ("max_steps_per_second", C.c_double)]
 
 
+class LoopSettings(C.Structure):   # include/hsqp_loop.h: hsqp_loop_settings
+    _fields_ = [("period", C.c_double), ("filter_alpha", C.c_double), ("n_nodes", C.c_int32), ("iterations", C.c_int32), ("dt", C.c_double),
+                ("iterate_flags", C.c_int32), ("arm_swing", C.c_int32), ("rollout", RolloutSettings), ("swing", SwingConfig),
+                ("terrain_height", C.c_double)]
+
+
+CMD_N, CMD_KNOTS = 4, 3   # HSQP_CMD_N, HSQP_CMD_KNOTS
+# entry points of include/hsqp_loop.h (tests/test_loop.py checks that the library exports each of them and the binding declares it)
+LOOP_ENTRY_POINTS = ("hsqp_set_default_joint_state", "hsqp_command_targets", "hsqp_command_targets_device", "hsqp_loop_defaults", "hsqp_loop_start",
+                     "hsqp_loop_command", "hsqp_loop_command_device", "hsqp_loop_run", "hsqp_loop_run_device", "hsqp_loop_state", "hsqp_loop_state_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

@@ -19,6 +19,8 @@
 #include "hsqp_feedback.h"
 #include "../../include/hsqp_feedback.h"
 #include "hsqp_rollout.h"
+#include "hsqp_loop.h"
+#include "../../include/hsqp_loop.h"
 #include "hsqp_warm.h"
 #include "hsqp_cent.h"
 #include "hsqp_cent_lq.h"
@@ -782,6 +784,21 @@ __global__ __launch_bounds__(64) void k_params(const DevModel* __restrict__ dm, 
   if (!ok) atomicExch(bad, 1);
 }
 
+// ---- velocity-command targets (hsqp_loop.h): one thread per instance-knot; a workgroup holds whole instances (CMDT_THREADS is a multiple of three), so
+// the barrier between the read of the filter state and its update in place covers the three items that read it
+constexpr int CMDT_THREADS = 192;
+static_assert(CMDT_THREADS % CMD_KNOTS == 0 && CMDT_THREADS % 64 == 0, "whole instances and whole waves per workgroup");
+__global__ __launch_bounds__(CMDT_THREADS) void k_command_targets(const DevModel* __restrict__ dm, double alpha, const double* __restrict__ v_cmd, double* v_filt,
+                                                                  const double* __restrict__ x0, double t0, double horizon, int B, double* __restrict__ tt,
+                                                                  double* __restrict__ ts) {
+  const int id = blockIdx.x * CMDT_THREADS + threadIdx.x;
+  const bool live = id < B * CMD_KNOTS;
+  CommandItem it{};
+  if (live) it = command_item_load(alpha, v_cmd, v_filt, id);
+  __syncthreads();
+  if (live) command_item_store(it, dm->default_joint_state, x0, t0, horizon, id, v_filt, tt, ts);
+}
+
 // ---- receding-horizon warm start (hsqp_warm.h) behind k_params: one wave per node of the new grid, WARM_WAVES nodes per workgroup
 // (blockIdx.x), one instance per blockIdx.y; the instance's previous stamps are staged in LDS once per workgroup (SHIFT)
 constexpr int WARM_WAVES = 4;
@@ -1016,6 +1033,9 @@ struct hsqp_handle {
   DevBuf<double> d_dt;            // [B][N] length of every interval (uniform grids: filled with dt)
   std::vector<double> h_dt;       // host copy (debug reads), empty for device-resident uploads
   bool uniform_grid = true, has_events = false;
+  bool grid_resident = false;     // d_dt / h_dt hold the uniform grid (h_dt.size() / grid_N instances, grid_N intervals of grid_dt): set_grid
+  int grid_N = 0;
+  double grid_dt = 0.0;
   DevBuf<double> d_vf;            // [B][N+1][VF_SIZE] value function of the last Riccati sweep (allocated when a KKT check is first asked for)
   DevBuf<double> d_vf2;           // scan path: value functions of the refinement pass (the KKT check then reads these)
   double* h_gate = nullptr;       // pinned host copy of the gate block [kkt | |g|_inf | scan flags]
@@ -1064,6 +1084,17 @@ struct hsqp_handle {
   DevBuf<double> d_stamps[2];
   int stamps_cur = 0;
   bool have_stamps = false;
+  // the resident closed loop (include/hsqp_loop.h): settings, where it stands, and its buffers carved from d_loop
+  struct Loop {
+    bool started = false, have_cycle = false;   // have_cycle: a cycle has completed since hsqp_loop_start (the next one shifts)
+    hsqp_loop_settings st;
+    int B = 0, E = 0;
+    double t = 0.0;
+    int* ne = nullptr; int* seq = nullptr; int* bad = nullptr; int32_t* ro_status = nullptr;
+    double* ev = nullptr; double* tt = nullptr; double* ts = nullptr; double* s0 = nullptr;
+    double* v_cmd = nullptr; double* v_filt = nullptr; double* x = nullptr; double* xs = nullptr; double* us = nullptr;
+  } loop;
+  DevBuf<char> d_loop, d_loop_log;   // the loop's resident arrays; staging of hsqp_loop_run's host logs and of hsqp_command_targets' host arrays
   double kernel_ms[5] = {0, 0, 0, 0, 0};
   int last_iterations = 0;
   struct IterLog { std::vector<hsqp_perf> perf; std::vector<double> alpha; std::vector<int> type; };
@@ -1378,12 +1409,17 @@ static int set_grid(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   const size_t B = p->batch, N = p->n_nodes;
   h->has_events = false;
   if (!p->dt_nodes) {
-    h->h_dt.assign(B * N, p->dt);
+    // (a receding-horizon caller uploads the same uniform grid every cycle: the resident copy is kept)
+    const bool resident = h->grid_resident && h->uniform_grid && h->h_dt.size() == B * N && h->grid_N == p->n_nodes && h->grid_dt == p->dt;
     h->uniform_grid = true;
+    if (resident) return HSQP_OK;
+    h->grid_resident = false;
+    h->h_dt.assign(B * N, p->dt);
     HCHECK(hipMemcpyAsync(h->d_dt, h->h_dt.data(), B * N * 8, hipMemcpyHostToDevice, h->stream));
+    h->grid_resident = true; h->grid_N = p->n_nodes; h->grid_dt = p->dt;
     return HSQP_OK;
   }
-  h->uniform_grid = false;
+  h->uniform_grid = false; h->grid_resident = false;
   if (device_src) {
     h->h_dt.resize(B * N);
     HCHECK(hipMemcpyAsync(h->d_dt, p->dt_nodes, B * N * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -1432,6 +1468,7 @@ static void commit_problem(hsqp_handle* h, const hsqp_problem* p, bool have_stam
 static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   if (!h) return HSQP_ERR_BAD_ARG;
   h->have_policy = false;
+  h->loop.started = false;
   if (!p || !p->x_init || !p->x_traj || !p->u_traj || !p->node_params) { h->err = "null problem pointer"; return HSQP_ERR_BAD_ARG; }
   if (!fits_handle(h, p)) return HSQP_ERR_BAD_ARG;
   if (!device_src && !padding_is_zero(h, p)) return HSQP_ERR_BAD_ARG;   // device-resident inputs: the caller guarantees the zero padding
@@ -1464,9 +1501,68 @@ static int check_status(hsqp_handle* h, const std::vector<int>& status) {
   return HSQP_OK;
 }
 
+// HSQP_WARM_SHIFT's preconditions, checked before anything is copied: a rejected call leaves the resident solution as it was
+static int warm_shift_ready(hsqp_handle* h, int batch, bool sorted) {
+  if (!h->have_solution || !h->have_stamps) {
+    h->err = "warm_start SHIFT: no resident solution of a problem uploaded through hsqp_upload_reference";
+    return HSQP_ERR_BAD_ARG;
+  }
+  if (h->B != batch) { h->err = "warm_start SHIFT: the batch differs from the resident solution's"; return HSQP_ERR_BAD_ARG; }
+  if (!sorted) { h->err = "warm_start SHIFT: node_times must not decrease"; return HSQP_ERR_BAD_ARG; }
+  std::vector<int> status(h->B);
+  HCHECK(hipMemcpy(status.data(), h->d_status, status.size() * sizeof(int), hipMemcpyDeviceToHost));
+  return check_status(h, status);
+}
+
+// the compact reference of a problem, every array resident on the device (hsqp_upload_reference: its staging area; the loop: its own buffers)
+struct RefDev {
+  int E, K;                        // max_events, n_knots
+  const int* ne; const int* seq;   // [B], [B][E + 1]
+  const double* ev;                // [B][E]
+  const double* tt; const double* ts; const double* nt;   // [B][K], [B][K][58], [B][N + 1] or null
+  int* bad;                        // one int, zeroed on the stream before the call
+  double t0, dt;
+  hsqp_swing_config swing; double terrain_height; int arm_swing, warm, N_prev;
+  bool sorted;
+};
+
+// The device side of hsqp_upload_reference, behind the copies `step` has queued on the stream (x_init in d_xinit, the grid in d_dt, the CALLER warm start
+// in d_x / d_u): the node-parameter table, the grid's raw stamps, the device-built warm start; then the problem is the resident one.
+static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& r, StickyError& step) {
+  const size_t B = p->batch, N = p->n_nodes;
+  if (step.rc == HSQP_OK) {
+    const int total = (int)(B * (N + 1));
+    HSQP_LAUNCH(k_params, dim3((total + 63) / 64), dim3(64), 0, h->stream, h->d_dm, r.swing, r.terrain_height, r.arm_swing, r.E, r.ne, r.ev, r.seq,
+                       r.K, r.tt, r.ts, r.t0, r.dt, r.nt, (int)N, (int)B, h->d_par, r.bad);
+    if (h->hdm.formulation == HSQP_FORM_CENTROIDAL)   // torso task-space reference of every row
+      HSQP_LAUNCH(k_params_cent_torso, dim3(total), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_par);
+    step(hipGetLastError(), "k_params");
+  }
+  if (step.rc == HSQP_OK) {   // the grid's raw stamps (every mode) and the device-built warm start (SHIFT / COLD), after k_params wrote the contact flags
+    WarmArgs w{};
+    w.mode = r.warm; w.B = (int)B; w.N = (int)N; w.N_prev = r.warm == HSQP_WARM_SHIFT ? r.N_prev : 0; w.cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
+    w.t0 = r.t0; w.dt = r.dt; w.total_mass = h->hdm.total_mass;
+    w.node_times = r.nt; w.dts = h->d_dt; w.par = h->d_par; w.x_init = h->d_xinit;
+    w.x_prev = h->d_xnew; w.u_prev = h->d_unew; w.stamps_prev = h->d_stamps[h->stamps_cur];
+    w.x = h->d_x; w.u = h->d_u; w.stamps = h->d_stamps[1 - h->stamps_cur];
+    const size_t lds = r.warm == HSQP_WARM_SHIFT ? (size_t)(r.N_prev + 1) * 8 : 0;
+    HSQP_LAUNCH(k_warm_start, dim3((unsigned)((N + 1 + WARM_WAVES - 1) / WARM_WAVES), (unsigned)B), dim3(64 * WARM_WAVES), lds, h->stream, w);
+    step(hipGetLastError(), "k_warm_start");
+  }
+  int bad = 0;
+  step(hipMemcpyAsync(&bad, r.bad, 4, hipMemcpyDeviceToHost, h->stream), "download status");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  if (bad) { h->err = "a swing phase has no lift-off / touch-down inside the mode schedule"; return HSQP_ERR_BAD_ARG; }
+  h->stamps_cur = 1 - h->stamps_cur;
+  commit_problem(h, p, r.sorted);
+  return HSQP_OK;
+}
+
 int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r) {
   if (!h) return HSQP_ERR_BAD_ARG;
   h->have_policy = false;
+  h->loop.started = false;
   if (!p || !r || !p->x_init || !r->n_events || !r->event_times || !r->mode_sequence || !r->target_times || !r->target_states) {
     h->err = "null problem / reference pointer";
     return HSQP_ERR_BAD_ARG;
@@ -1497,17 +1593,7 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
     sorted = i % (p->n_nodes + 1) == 0 || r->node_times[i] >= r->node_times[i - 1];
   HCHECK(hipSetDevice(h->device));
   const int N_prev = h->N;
-  if (warm == HSQP_WARM_SHIFT) {   // preconditions, checked before anything is copied: a rejected call leaves the resident solution as it was
-    if (!h->have_solution || !h->have_stamps) {
-      h->err = "warm_start SHIFT: no resident solution of a problem uploaded through hsqp_upload_reference";
-      return HSQP_ERR_BAD_ARG;
-    }
-    if (h->B != p->batch) { h->err = "warm_start SHIFT: the batch differs from the resident solution's"; return HSQP_ERR_BAD_ARG; }
-    if (!sorted) { h->err = "warm_start SHIFT: node_times must not decrease"; return HSQP_ERR_BAD_ARG; }
-    std::vector<int> status(h->B);
-    HCHECK(hipMemcpy(status.data(), h->d_status, status.size() * sizeof(int), hipMemcpyDeviceToHost));
-    if (check_status(h, status) != HSQP_OK) return HSQP_ERR_NUMERIC;
-  }
+  if (warm == HSQP_WARM_SHIFT) { const int rc = warm_shift_ready(h, p->batch, sorted); if (rc != HSQP_OK) return rc; }
   const size_t B = p->batch, N = p->n_nodes, E = r->max_events, K = r->n_knots;
   // staging area for the compact reference (a few KB per instance)
   const size_t o_ne = 0, o_seq = o_ne + align256(B * 4), o_bad = o_seq + align256(B * (E + 1) * 4), o_ev = o_bad + 256,
@@ -1537,33 +1623,8 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
     step(hipMemcpyAsync(h->d_x, p->x_traj, B * (N + 1) * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
     step(hipMemcpyAsync(h->d_u, p->u_traj, B * N * NU * 8, hipMemcpyHostToDevice, h->stream), "upload u");
   }
-  if (step.rc == HSQP_OK) {
-    const int total = (int)(B * (N + 1));
-    HSQP_LAUNCH(k_params, dim3((total + 63) / 64), dim3(64), 0, h->stream, h->d_dm, r->swing, r->terrain_height, r->arm_swing, (int)E, d_ne, d_ev, d_seq,
-                       (int)K, d_tt, d_ts, r->t0, r->dt, (const double*)d_nt, (int)N, (int)B, h->d_par, d_bad);
-    if (h->hdm.formulation == HSQP_FORM_CENTROIDAL)   // torso task-space reference of every row
-      HSQP_LAUNCH(k_params_cent_torso, dim3(total), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_par);
-    step(hipGetLastError(), "k_params");
-  }
-  if (step.rc == HSQP_OK) {   // the grid's raw stamps (every mode) and the device-built warm start (SHIFT / COLD), after k_params wrote the contact flags
-    WarmArgs w{};
-    w.mode = warm; w.B = (int)B; w.N = (int)N; w.N_prev = warm == HSQP_WARM_SHIFT ? N_prev : 0; w.cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
-    w.t0 = r->t0; w.dt = r->dt; w.total_mass = h->hdm.total_mass;
-    w.node_times = d_nt; w.dts = h->d_dt; w.par = h->d_par; w.x_init = h->d_xinit;
-    w.x_prev = h->d_xnew; w.u_prev = h->d_unew; w.stamps_prev = h->d_stamps[h->stamps_cur];
-    w.x = h->d_x; w.u = h->d_u; w.stamps = h->d_stamps[1 - h->stamps_cur];
-    const size_t lds = warm == HSQP_WARM_SHIFT ? (size_t)(N_prev + 1) * 8 : 0;
-    HSQP_LAUNCH(k_warm_start, dim3((unsigned)((N + 1 + WARM_WAVES - 1) / WARM_WAVES), (unsigned)B), dim3(64 * WARM_WAVES), lds, h->stream, w);
-    step(hipGetLastError(), "k_warm_start");
-  }
-  int bad = 0;
-  step(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream), "download status");
-  step(hipStreamSynchronize(h->stream), "sync");
-  if (step.rc != HSQP_OK) return step.rc;
-  if (bad) { h->err = "a swing phase has no lift-off / touch-down inside the mode schedule"; return HSQP_ERR_BAD_ARG; }
-  h->stamps_cur = 1 - h->stamps_cur;
-  commit_problem(h, p, sorted);
-  return HSQP_OK;
+  const RefDev rd{(int)E, (int)K, d_ne, d_seq, d_ev, d_tt, d_ts, d_nt, d_bad, r->t0, r->dt, r->swing, r->terrain_height, r->arm_swing, warm, N_prev, sorted};
+  return reference_build(h, p, rd, step);
 }
 
 // The backward sweep of an iteration: serial recursion, or — one or two instances on a long horizon, or on request — the associative scan over the
@@ -1907,6 +1968,8 @@ int hsqp_update_term_weights(hsqp_handle* h, const hsqp_term_weights* w) {
   if (!e.empty()) { h->err = "hsqp_update_term_weights: " + e; return HSQP_ERR_BAD_ARG; }
   HCHECK(hipSetDevice(h->device));
   HCHECK(hipStreamSynchronize(h->stream));   // no kernel of an earlier call may still be reading the image
+  dm.has_default_joint_state = h->hdm.has_default_joint_state;   // (not part of hsqp_model_desc: hsqp_set_default_joint_state)
+  memcpy(dm.default_joint_state, h->hdm.default_joint_state, sizeof(dm.default_joint_state));
   h->md = m; h->hdm = dm;
   HCHECK(hipMemcpy(h->d_dm, &h->hdm, sizeof(DevModel), hipMemcpyHostToDevice));
   return HSQP_OK;
@@ -2095,18 +2158,24 @@ void hsqp_rollout_defaults(hsqp_rollout_settings* s) {
   s->max_steps_per_second = 10000.0;
 }
 
+// what hsqp_rollout_policy refuses in its settings (null: nothing)
+static const char* rollout_settings_error(const hsqp_rollout_settings& st) {
+  const auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+  if (st.integrator != HSQP_ROLLOUT_ODE45 && st.integrator != HSQP_ROLLOUT_RK4) return "unknown integrator";
+  if (st.controller != HSQP_ROLLOUT_FEEDFORWARD && st.controller != HSQP_ROLLOUT_FEEDBACK) return "unknown controller";
+  if (!positive(st.abs_tol) || !positive(st.rel_tol) || !positive(st.initial_step) || !positive(st.max_steps_per_second))
+    return "tolerances, initial_step and max_steps_per_second must be finite and > 0";
+  return nullptr;
+}
+
 // dev: every array argument is device memory of the handle's GPU
 static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const double* s0, const double* x0, double duration, int n, double* x, double* u,
                         int32_t* status, int32_t* steps, int32_t* rejected, bool dev) {
   if (!h) return HSQP_ERR_BAD_ARG;
   const char* who = dev ? "hsqp_rollout_policy_device" : "hsqp_rollout_policy";
   const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
-  const auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
   if (!st || !s0 || !x0 || !status) return bad("null settings, s0, x0 or status");
-  if (st->integrator != HSQP_ROLLOUT_ODE45 && st->integrator != HSQP_ROLLOUT_RK4) return bad("unknown integrator");
-  if (st->controller != HSQP_ROLLOUT_FEEDFORWARD && st->controller != HSQP_ROLLOUT_FEEDBACK) return bad("unknown controller");
-  if (!positive(st->abs_tol) || !positive(st->rel_tol) || !positive(st->initial_step) || !positive(st->max_steps_per_second))
-    return bad("tolerances, initial_step and max_steps_per_second must be finite and > 0");
+  if (const char* what = rollout_settings_error(*st)) return bad(what);
   if (!(duration >= 0.0) || !std::isfinite(duration)) return bad("duration < 0 or not finite");
   if (n < 1) return bad("n_samples < 1");
   { const int rc = feedback_ready(h, who); if (rc != HSQP_OK) return rc; }
@@ -2187,6 +2256,258 @@ int hsqp_rollout_policy_device(hsqp_handle* h, const hsqp_rollout_settings* st, 
                                double* d_x, double* d_u, int32_t* d_status, int32_t* d_steps, int32_t* d_rejected) {
   return rollout_impl(h, st, d_s0, d_x0, duration, n_samples, d_x, d_u, d_status, d_steps, d_rejected, true);
 }
+
+// ---- velocity-command targets and the resident closed loop (include/hsqp_loop.h, csrc/hsqp_loop.h)
+static int loop_bad(hsqp_handle* h, const char* who, const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; }
+// whole-body handle with a default joint state
+static int loop_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) return loop_bad(h, who, "whole-body handles only (the centroidal generator needs the base velocity from the centroidal momentum)");
+  if (!h->hdm.has_default_joint_state) return loop_bad(h, who, "no default joint state: call hsqp_set_default_joint_state first");
+  return HSQP_OK;
+}
+static bool all_finite(const double* v, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false; return true; }
+
+int hsqp_set_default_joint_state(hsqp_handle* h, const double* q) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (!q || !all_finite(q, NJ)) return loop_bad(h, "hsqp_set_default_joint_state", "null or non-finite joint state");
+  HCHECK(hipSetDevice(h->device));
+  memcpy(h->hdm.default_joint_state, q, NJ * 8);
+  h->hdm.has_default_joint_state = 1;
+  HCHECK(hipMemcpy(h->d_dm, &h->hdm, sizeof(DevModel), hipMemcpyHostToDevice));
+  return HSQP_OK;
+}
+
+// queues k_command_targets on the handle's stream (device arrays)
+static void launch_command_targets(hsqp_handle* h, int B, const double* d_v_cmd, double* d_v_filt, double alpha, const double* d_x0, double t0, double horizon,
+                                   double* d_tt, double* d_ts) {
+  HSQP_LAUNCH(k_command_targets, dim3((B * CMD_KNOTS + CMDT_THREADS - 1) / CMDT_THREADS), dim3(CMDT_THREADS), 0, h->stream, h->d_dm, alpha, d_v_cmd, d_v_filt, d_x0,
+              t0, horizon, B, d_tt, d_ts);
+}
+
+static int command_targets_impl(hsqp_handle* h, int batch, const double* v_cmd, double* v_filt, double alpha, const double* x0, double t0, double horizon,
+                                double* tt, double* ts, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_command_targets_device" : "hsqp_command_targets";
+  { const int rc = loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (!v_cmd || !v_filt || !x0 || !tt || !ts) return loop_bad(h, who, "null array");
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (!(alpha >= 0.0 && alpha < 1.0)) return loop_bad(h, who, "filter_alpha outside [0, 1)");
+  if (!std::isfinite(t0) || !std::isfinite(horizon) || !(horizon > 0.0)) return loop_bad(h, who, "t0 not finite, or horizon not finite and > 0");
+  const size_t B = batch;
+  if (!dev && !all_finite(v_cmd, B * CMD_N)) return loop_bad(h, who, "non-finite command");
+  HCHECK(hipSetDevice(h->device));
+  StickyError step{h};
+  if (dev) {
+    launch_command_targets(h, batch, v_cmd, v_filt, alpha, x0, t0, horizon, tt, ts);
+    step(hipGetLastError(), "k_command_targets");
+  } else {
+    const size_t o_c = 0, o_f = o_c + align256(B * CMD_N * 8), o_x = o_f + align256(B * CMD_N * 8), o_tt = o_x + align256(B * NX * 8),
+                 o_ts = o_tt + align256(B * CMD_KNOTS * 8), total = o_ts + align256(B * CMD_KNOTS * NX * 8);
+    DEV_ENSURE(h->d_loop_log, total, "command-target staging");
+    char* base = h->d_loop_log.p;
+    double* d_f = reinterpret_cast<double*>(base + o_f);
+    step(hipMemcpyAsync(base + o_c, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
+    step(hipMemcpyAsync(d_f, v_filt, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_filt");
+    step(hipMemcpyAsync(base + o_x, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
+    if (step.rc == HSQP_OK) {
+      launch_command_targets(h, batch, reinterpret_cast<const double*>(base + o_c), d_f, alpha, reinterpret_cast<const double*>(base + o_x), t0, horizon,
+                             reinterpret_cast<double*>(base + o_tt), reinterpret_cast<double*>(base + o_ts));
+      step(hipGetLastError(), "k_command_targets");
+    }
+    step(hipMemcpyAsync(v_filt, d_f, B * CMD_N * 8, hipMemcpyDeviceToHost, h->stream), "download v_filt");
+    step(hipMemcpyAsync(tt, base + o_tt, B * CMD_KNOTS * 8, hipMemcpyDeviceToHost, h->stream), "download target_times");
+    step(hipMemcpyAsync(ts, base + o_ts, B * CMD_KNOTS * NX * 8, hipMemcpyDeviceToHost, h->stream), "download target_states");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+
+int hsqp_command_targets(hsqp_handle* h, int batch, const double* v_cmd, double* v_filt, double filter_alpha, const double* x0, double t0, double horizon,
+                         double* target_times, double* target_states) {
+  return command_targets_impl(h, batch, v_cmd, v_filt, filter_alpha, x0, t0, horizon, target_times, target_states, false);
+}
+int hsqp_command_targets_device(hsqp_handle* h, int batch, const double* d_v_cmd, double* d_v_filt, double filter_alpha, const double* d_x0, double t0,
+                                double horizon, double* d_target_times, double* d_target_states) {
+  return command_targets_impl(h, batch, d_v_cmd, d_v_filt, filter_alpha, d_x0, t0, horizon, d_target_times, d_target_states, true);
+}
+
+void hsqp_loop_defaults(const hsqp_handle* h, hsqp_loop_settings* s) {
+  if (!s) return;
+  memset(s, 0, sizeof(*s));
+  s->period = 1.0 / 60.0;     // task.info mpcDesiredFrequency 60
+  s->filter_alpha = 0.8;      // WBMpcTargetTrajectoriesCalculator.cpp:88
+  s->n_nodes = h ? std::min(100, h->st.max_nodes) : 100;
+  s->dt = 0.035;              // task.info sqp dt
+  s->iterations = 1;          // task.info sqpIteration 1
+  s->iterate_flags = HSQP_ITER_TAKE_STEP | HSQP_ITER_LINESEARCH;
+  s->arm_swing = 1;
+  hsqp_rollout_defaults(&s->rollout);
+  s->swing = hsqp_swing_config{0.05, -0.0, 0.08, -0.001, 0.4, 0.005, -0.15, 0.3};   // task.info swing_trajectory_config
+  s->terrain_height = 0.0;
+}
+
+int hsqp_loop_start(hsqp_handle* h, const hsqp_loop_settings* st, int batch, double t0, const double* x0, const double* v_cmd, int max_events,
+                    const int32_t* n_events, const double* event_times, const int32_t* mode_sequence) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_start";
+  h->loop.started = false;
+  { const int rc = loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (!st || !x0 || !v_cmd || !n_events || !event_times || !mode_sequence) return loop_bad(h, who, "null settings or array");
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (st->n_nodes < 1 || st->n_nodes > h->st.max_nodes) return loop_bad(h, who, "n_nodes outside [1, max_nodes]");
+  const auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+  if (!positive(st->period) || !positive(st->dt)) return loop_bad(h, who, "period and dt must be finite and > 0");
+  if (!(st->filter_alpha >= 0.0 && st->filter_alpha < 1.0)) return loop_bad(h, who, "filter_alpha outside [0, 1)");
+  if (st->iterations < 1) return loop_bad(h, who, "iterations < 1");
+  if (st->iterate_flags & ~(HSQP_ITER_TAKE_STEP | HSQP_ITER_KKT | HSQP_ITER_LINESEARCH))
+    return loop_bad(h, who, "iterate_flags: HSQP_ITER_TAKE_STEP, HSQP_ITER_KKT, HSQP_ITER_LINESEARCH only (HSQP_ITER_UNTIL_CONVERGED reads B-sized records back per iteration)");
+  if (const char* what = rollout_settings_error(st->rollout)) return loop_bad(h, who, what);
+  if (!std::isfinite(t0)) return loop_bad(h, who, "t0 not finite");
+  if (max_events < 1) return loop_bad(h, who, "max_events < 1");
+  const size_t B = batch, E = max_events;
+  for (size_t b = 0; b < B; ++b)
+    if (n_events[b] < 1 || n_events[b] > max_events) return loop_bad(h, who, "n_events outside [1, max_events]");
+  if (!all_finite(v_cmd, B * CMD_N)) return loop_bad(h, who, "non-finite command");
+  HCHECK(hipSetDevice(h->device));
+  // the loop's resident arrays, carved from one buffer
+  size_t o = 0;
+  const auto carve = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+  const size_t o_ne = carve(B * 4), o_seq = carve(B * (E + 1) * 4), o_bad = carve(4), o_rs = carve(B * 4), o_ev = carve(B * E * 8), o_tt = carve(B * CMD_KNOTS * 8),
+               o_ts = carve(B * CMD_KNOTS * NX * 8), o_s0 = carve(B * 8), o_vc = carve(B * CMD_N * 8), o_vf = carve(2 * B * CMD_N * 8), o_x = carve(B * NX * 8),
+               o_xs = carve(B * NX * 8), o_us = carve(B * NU * 8);
+  DEV_ENSURE(h->d_loop, o, "loop buffers");
+  char* base = h->d_loop.p;
+  hsqp_handle::Loop& L = h->loop;
+  L.ne = reinterpret_cast<int*>(base + o_ne); L.seq = reinterpret_cast<int*>(base + o_seq); L.bad = reinterpret_cast<int*>(base + o_bad);
+  L.ro_status = reinterpret_cast<int32_t*>(base + o_rs); L.ev = reinterpret_cast<double*>(base + o_ev); L.tt = reinterpret_cast<double*>(base + o_tt);
+  L.ts = reinterpret_cast<double*>(base + o_ts); L.s0 = reinterpret_cast<double*>(base + o_s0); L.v_cmd = reinterpret_cast<double*>(base + o_vc);
+  L.v_filt = reinterpret_cast<double*>(base + o_vf); L.x = reinterpret_cast<double*>(base + o_x); L.xs = reinterpret_cast<double*>(base + o_xs);
+  L.us = reinterpret_cast<double*>(base + o_us);
+  StickyError step{h};
+  step(hipMemcpyAsync(L.ne, n_events, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
+  step(hipMemcpyAsync(L.seq, mode_sequence, B * (E + 1) * 4, hipMemcpyHostToDevice, h->stream), "upload mode_sequence");
+  step(hipMemcpyAsync(L.ev, event_times, B * E * 8, hipMemcpyHostToDevice, h->stream), "upload event_times");
+  step(hipMemcpyAsync(L.v_cmd, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
+  step(hipMemcpyAsync(L.v_filt, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_filt");
+  step(hipMemcpyAsync(L.x, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
+  step(hipMemsetAsync(L.s0, 0, B * 8, h->stream), "memset s0");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  L.st = *st; L.B = batch; L.E = max_events; L.t = t0;
+  L.have_cycle = false;
+  L.started = true;
+  return HSQP_OK;
+}
+
+static int loop_started(hsqp_handle* h, const char* who) {
+  if (!h->loop.started) return loop_bad(h, who, "no loop started (hsqp_loop_start; every hsqp_upload* / hsqp_solve call ends a loop)");
+  return HSQP_OK;
+}
+
+static int loop_command_impl(hsqp_handle* h, const double* v_cmd, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_loop_command_device" : "hsqp_loop_command";
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  if (!v_cmd) return loop_bad(h, who, "null commands");
+  const size_t n = (size_t)h->loop.B * CMD_N;
+  if (!dev && !all_finite(v_cmd, n)) return loop_bad(h, who, "non-finite command");
+  HCHECK(hipSetDevice(h->device));
+  HCHECK(hipMemcpyAsync(h->loop.v_cmd, v_cmd, n * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_loop_command(hsqp_handle* h, const double* v_cmd) { return loop_command_impl(h, v_cmd, false); }
+int hsqp_loop_command_device(hsqp_handle* h, const double* d_v_cmd) { return loop_command_impl(h, d_v_cmd, true); }
+
+// One cycle from the resident buffers (include/hsqp_loop.h, steps 1 to 5).  d_xlog / d_ulog: this cycle's log rows (device) or null.  On a failure the
+// loop's own state (t, x, v_filt) is that of the last completed cycle: the filter state is advanced on a copy and committed with the state.
+static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
+  hsqp_handle::Loop& L = h->loop;
+  const hsqp_loop_settings& st = L.st;
+  const size_t B = L.B;
+  const int warm = L.have_cycle ? HSQP_WARM_SHIFT : HSQP_WARM_COLD;
+  hsqp_problem p{};
+  p.batch = L.B; p.n_nodes = st.n_nodes; p.dt = st.dt; p.x_init = L.x;
+  // step 2's checks come first, as in hsqp_upload_reference: a rejected cycle leaves the resident solution as it was
+  h->have_policy = false;
+  const int N_prev = h->N;
+  if (warm == HSQP_WARM_SHIFT) { const int rc = warm_shift_ready(h, L.B, true); if (rc != HSQP_OK) return rc; }
+  StickyError step{h};
+  // 1. the targets; the filter state advances in the second half of its buffer
+  double* vf_next = L.v_filt + B * CMD_N;
+  step(hipMemcpyAsync(vf_next, L.v_filt, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream), "copy v_filt");
+  launch_command_targets(h, L.B, L.v_cmd, vf_next, st.filter_alpha, L.x, L.t, st.n_nodes * st.dt, L.tt, L.ts);
+  step(hipGetLastError(), "k_command_targets");
+  // 2. hsqp_upload_reference's work on the resident arrays
+  h->have_problem = false; h->have_solution = false; h->have_stamps = false;
+  { const int rc = set_grid(h, &p, false); if (rc != HSQP_OK) return rc; }
+  step(hipMemsetAsync(L.bad, 0, 4, h->stream), "memset");
+  step(hipMemcpyAsync(h->d_xinit, L.x, B * NX * 8, hipMemcpyDeviceToDevice, h->stream), "copy x_init");
+  const RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, nullptr, L.bad, L.t, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
+  { const int rc = reference_build(h, &p, rd, step); if (rc != HSQP_OK) return rc; }
+  // 3. the iteration
+  { const int rc = hsqp_iterate_device(h, st.iterations, st.iterate_flags); if (rc != HSQP_OK) return rc; }
+  // 4. the plant under the policy over one period
+  { const int rc = rollout_impl(h, &st.rollout, L.s0, L.x, st.period, 1, L.xs, L.us, L.ro_status, nullptr, nullptr, true); if (rc != HSQP_OK) return rc; }
+  // 5. the rolled-out state is the next measured state
+  HCHECK(hipMemcpyAsync(L.x, L.xs, B * NX * 8, hipMemcpyDeviceToDevice, h->stream));
+  HCHECK(hipMemcpyAsync(L.v_filt, vf_next, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream));
+  if (d_xlog) HCHECK(hipMemcpyAsync(d_xlog, L.xs, B * NX * 8, hipMemcpyDeviceToDevice, h->stream));
+  if (d_ulog) HCHECK(hipMemcpyAsync(d_ulog, L.us, B * NU * 8, hipMemcpyDeviceToDevice, h->stream));
+  L.t += st.period;
+  L.have_cycle = true;
+  return HSQP_OK;
+}
+
+static int loop_run_impl(hsqp_handle* h, int n_cycles, double* x_log, double* u_log, int* cycles_done, bool dev) {
+  if (cycles_done) *cycles_done = 0;
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_loop_run_device" : "hsqp_loop_run";
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  if (n_cycles < 1) return loop_bad(h, who, "n_cycles < 1");
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = h->loop.B, nx = B * NX, nu = B * NU, n = n_cycles;
+  double* d_xl = x_log;
+  double* d_ul = u_log;
+  if (!dev && (x_log || u_log)) {
+    DEV_ENSURE(h->d_loop_log, ((x_log ? n * nx : 0) + (u_log ? n * nu : 0)) * 8, "loop log staging");
+    d_xl = x_log ? reinterpret_cast<double*>(h->d_loop_log.p) : nullptr;
+    d_ul = u_log ? reinterpret_cast<double*>(h->d_loop_log.p) + (x_log ? n * nx : 0) : nullptr;
+  }
+  int rc = HSQP_OK, done = 0;
+  for (; done < n_cycles && rc == HSQP_OK; done += rc == HSQP_OK)
+    rc = loop_cycle(h, d_xl ? d_xl + done * nx : nullptr, d_ul ? d_ul + done * nu : nullptr);
+  if (cycles_done) *cycles_done = done;
+  // the rows of the completed cycles, once (a failed cycle's error text stays in h->err)
+  const std::string err = h->err;
+  StickyError step{h};
+  if (!dev && done > 0) {
+    if (x_log) step(hipMemcpyAsync(x_log, d_xl, done * nx * 8, hipMemcpyDeviceToHost, h->stream), "download x_log");
+    if (u_log) step(hipMemcpyAsync(u_log, d_ul, done * nu * 8, hipMemcpyDeviceToHost, h->stream), "download u_log");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (rc != HSQP_OK) { h->err = err; return rc; }
+  return step.rc;
+}
+int hsqp_loop_run(hsqp_handle* h, int n_cycles, double* x_log, double* u_log, int* cycles_done) { return loop_run_impl(h, n_cycles, x_log, u_log, cycles_done, false); }
+int hsqp_loop_run_device(hsqp_handle* h, int n_cycles, double* d_x_log, double* d_u_log, int* cycles_done) {
+  return loop_run_impl(h, n_cycles, d_x_log, d_u_log, cycles_done, true);
+}
+
+static int loop_state_impl(hsqp_handle* h, double* t, double* x, double* v_filt, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  { const int rc = loop_started(h, dev ? "hsqp_loop_state_device" : "hsqp_loop_state"); if (rc != HSQP_OK) return rc; }
+  HCHECK(hipSetDevice(h->device));
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t B = h->loop.B;
+  if (t) *t = h->loop.t;
+  if (x) HCHECK(hipMemcpyAsync(x, h->loop.x, B * NX * 8, kind, h->stream));
+  if (v_filt) HCHECK(hipMemcpyAsync(v_filt, h->loop.v_filt, B * CMD_N * 8, kind, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_loop_state(hsqp_handle* h, double* t, double* x, double* v_filt) { return loop_state_impl(h, t, x, v_filt, false); }
+int hsqp_loop_state_device(hsqp_handle* h, double* t, double* d_x, double* d_v_filt) { return loop_state_impl(h, t, d_x, d_v_filt, true); }
 
 int hsqp_last_kernel_ms(hsqp_handle* h, double out_ms[5]) {
   if (!h || !out_ms) return HSQP_ERR_BAD_ARG;

@@ -180,6 +180,9 @@ struct DevModel {
   unsigned char limb_merge[NANC][QV_LIMBS];
   int limb_foot_step[QV_LIMBS];   // the step of the limb's path on which its foot body sits (-1: the limb carries no foot)
   int ql_ok;
+  // velocity-command targets (hsqp_loop.h): reference.info defaultJointState.  Not part of hsqp_model_desc: hsqp_set_default_joint_state (include/hsqp_loop.h)
+  int has_default_joint_state;
+  double default_joint_state[NJ];
 };
 
 // ------------------------------------------------------------------------------------------------

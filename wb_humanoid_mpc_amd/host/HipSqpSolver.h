@@ -16,6 +16,7 @@
 #include "../../include/hsqp.h"
 #include "../../include/hsqp_feedback.h"
 #include "../../include/hsqp_rollout.h"
+#include "../../include/hsqp_loop.h"
 
 namespace hsqp_host {
 
@@ -155,6 +156,55 @@ class HipSqpSolver {
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_rollout_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
+  /** ---- the closed loop resident on the device (include/hsqp_loop.h): what ProceduralMpcMotionManager::preSolverRun's target generation, MPC_BASE::run
+   *  and the dummy simulation's rolloutPolicy do per cycle, for `batch` instances with their own velocity commands.
+   *  setDefaultJointState: reference.info defaultJointState (HSQP_NJ values), once, before the first startLoop. */
+  void setDefaultJointState(const std::vector<double>& q) {
+    if (q.size() != HSQP_NJ) throw std::runtime_error("[HipSqpSolver] setDefaultJointState: HSQP_NJ values expected");
+    const int rc = hsqp_set_default_joint_state(h_, q.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_set_default_joint_state failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** hsqp_loop_defaults for this handle. */
+  hsqp_loop_settings loopDefaults() const { hsqp_loop_settings st; hsqp_loop_defaults(h_, &st); return st; }
+  /** x0 [batch][HSQP_NX], velocityCommands [batch][4] (vx, vy, height, yaw rate), the instances' mode schedules as hsqp_reference takes them
+   *  (nEvents [batch], eventTimes [batch][maxEvents], modeSequence [batch][maxEvents + 1]); uploaded once. */
+  void startLoop(const hsqp_loop_settings& st, double t0, const std::vector<double>& x0, const std::vector<double>& velocityCommands, int maxEvents,
+                 const std::vector<int32_t>& nEvents, const std::vector<double>& eventTimes, const std::vector<int32_t>& modeSequence) {
+    const size_t B = nEvents.size();
+    loopBatch_ = 0;
+    if (B == 0 || maxEvents < 1 || x0.size() != B * HSQP_NX || velocityCommands.size() != B * HSQP_CMD_N || eventTimes.size() != B * (size_t)maxEvents ||
+        modeSequence.size() != B * (size_t)(maxEvents + 1))
+      throw std::runtime_error("[HipSqpSolver] startLoop: inconsistent array sizes");
+    const int rc = hsqp_loop_start(h_, &st, (int)B, t0, x0.data(), velocityCommands.data(), maxEvents, nEvents.data(), eventTimes.data(), modeSequence.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_start failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    loopBatch_ = B;
+    shiftable_ = false;   // (the loop owns the resident problem until the next run* call ends it)
+  }
+  /** New commands [batch][4]; in effect from the next cycle. */
+  void setLoopCommand(const std::vector<double>& velocityCommands) {
+    if (velocityCommands.size() != loopBatch_ * HSQP_CMD_N) throw std::runtime_error("[HipSqpSolver] setLoopCommand: four values per instance of the started loop expected");
+    const int rc = hsqp_loop_command(h_, velocityCommands.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_command failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** nCycles cycles; xLog [done][batch][HSQP_NX], uLog [done][batch][HSQP_NU]: state and input at the end of every completed cycle.  A cycle that
+   *  fails throws after the logs of the completed ones are in place; returns the cycles done. */
+  int runLoop(int nCycles, std::vector<double>& xLog, std::vector<double>& uLog) {
+    const size_t n = nCycles > 0 ? (size_t)nCycles : 0;
+    xLog.assign(n * loopBatch_ * HSQP_NX, 0.0); uLog.assign(n * loopBatch_ * HSQP_NU, 0.0);
+    int done = 0;
+    const int rc = hsqp_loop_run(h_, nCycles, xLog.data(), uLog.data(), &done);
+    xLog.resize((size_t)done * loopBatch_ * HSQP_NX); uLog.resize((size_t)done * loopBatch_ * HSQP_NU);
+    if (rc != HSQP_OK)
+      throw std::runtime_error("[HipSqpSolver] hsqp_loop_run failed after " + std::to_string(done) + " cycles (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return done;
+  }
+  /** Where the loop stands: its time, the measured states [batch][HSQP_NX] and the command filters' states [batch][4]. */
+  void loopState(double& t, std::vector<double>& x, std::vector<double>& filteredCommands) {
+    x.assign(loopBatch_ * HSQP_NX, 0.0); filteredCommands.assign(loopBatch_ * HSQP_CMD_N, 0.0);
+    const int rc = hsqp_loop_state(h_, &t, x.data(), filteredCommands.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_state failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
   const PrimalSolution& getPrimalSolution() const { return solution_; }
   const std::vector<hsqp_perf>& getPerformanceIndeces() const { return perf_; }
   const std::vector<hsqp_perf>& getPerformanceIndecesBeforeStep() const { return perfBefore_; }
@@ -223,6 +273,7 @@ class HipSqpSolver {
   Benchmarks bench_;
   int iterations_ = 0;
   bool reportKkt_ = false;
+  size_t loopBatch_ = 0;     // instances of the started loop (startLoop)
   bool shiftable_ = false;   // the handle holds the solution of a runWithReference / runRecedingHorizon: the next runRecedingHorizon shifts it
 };
 

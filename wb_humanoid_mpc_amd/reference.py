@@ -194,11 +194,20 @@ class TargetTrajectories:
         return a * self.states[i] + (1.0 - a) * self.states[i + 1]
 
 
-def velocity_command_targets(model, v_cmd, t0, x0, horizon):
-    """commandedVelocityToTargetTrajectories with the command filter at steady state
-    (the reference's first-call transient of the function-local static filter —
-    TargetTrajectoriesCalculatorBase.cpp:117-119 — is deliberately not reproduced)."""
+def velocity_command_targets(model, v_cmd, t0, x0, horizon, filter_alpha=0.0, v_filt=None):
+    """commandedVelocityToTargetTrajectories.  Default: the command filter at steady state (the reference's first-call transient of the
+    function-local static filter — TargetTrajectoriesCalculatorBase.cpp:117-119 — is deliberately not reproduced).  With filter_alpha > 0
+    the knots are formed from alpha v_filt + (1 - alpha) v_cmd (filterAndTransformVelCommandToLocal, 0.8 in the reference); v_filt is the
+    caller's filter state ([4], updated IN PLACE when it is a numpy array; None: the command).  The device form is hsqp_command_targets."""
     nj = model.nj
+    if filter_alpha != 0.0:
+        cmd = np.asarray(v_cmd, dtype=float)
+        new = filter_alpha * (cmd if v_filt is None else np.asarray(v_filt, dtype=float)) + (1.0 - filter_alpha) * cmd
+        if isinstance(v_filt, np.ndarray):
+            v_filt[:] = new
+        v_cmd = tuple(float(v) for v in new)
+    elif isinstance(v_filt, np.ndarray):
+        v_filt[:] = v_cmd
     vx, vy, height, wz = v_cmd
     pose = np.array(x0[:6], dtype=float)
     pose[4] = pose[5] = 0.0

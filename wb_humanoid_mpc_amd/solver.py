@@ -96,6 +96,20 @@ def load_library():
     lib.hsqp_rollout_defaults.restype = None
     lib.hsqp_rollout_policy.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
     lib.hsqp_rollout_policy_device.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
+    # include/hsqp_loop.h
+    _ls = C.POINTER(_abi.LoopSettings)
+    lib.hsqp_set_default_joint_state.argtypes = [C.c_void_p, _dp]
+    lib.hsqp_command_targets.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp, C.c_double, C.c_double, _dp, _dp]
+    lib.hsqp_command_targets_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp, C.c_double, C.c_double, _dp, _dp]
+    lib.hsqp_loop_defaults.argtypes = [C.c_void_p, _ls]
+    lib.hsqp_loop_defaults.restype = None
+    lib.hsqp_loop_start.argtypes = [C.c_void_p, _ls, C.c_int, C.c_double, _dp, _dp, C.c_int, _ip, _dp, _ip]
+    lib.hsqp_loop_command.argtypes = [C.c_void_p, _dp]
+    lib.hsqp_loop_command_device.argtypes = [C.c_void_p, _dp]
+    lib.hsqp_loop_run.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
+    lib.hsqp_loop_run_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
+    lib.hsqp_loop_state.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    lib.hsqp_loop_state_device.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -125,6 +139,9 @@ class HipSqpSolver:
         self.max_nodes, self.max_batch = max_nodes, max_batch
         self._shape = None
         self._sol = None
+        self._loop_batch = 0
+        if not model.centroidal:   # the velocity-command generator's joint targets (reference.info defaultJointState) are not part of hsqp_model_desc
+            self._check(self.lib.hsqp_set_default_joint_state(h, _c(model.default_joint_state).ctypes.data_as(_dp)))
 
     def close(self):
         if getattr(self, "h", None):
@@ -460,6 +477,106 @@ class HipSqpSolver:
             if rc in (_abi.ERR_NOT_CONVERGED, _abi.ERR_NUMERIC):
                 err.result = result
             raise err
+
+    # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
+    def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
+        """hsqp_command_targets: (target_times[B, 3], target_states[B, 3, 58], v_filt[B, 4]) of B instances from their commands
+        (vx, vy, height, yaw rate) and measured states; v_filt: the filter state before the call (None: the commands, a converged filter).
+        The arithmetic of reference.velocity_command_targets."""
+        x0 = _c(np.atleast_2d(x0))
+        B = x0.shape[0]
+        v_cmd = _c(np.broadcast_to(v_cmd, (B, _abi.CMD_N)))
+        vf = v_cmd.copy() if v_filt is None else _c(np.broadcast_to(v_filt, (B, _abi.CMD_N))).copy()
+        tt, ts = np.zeros((B, _abi.CMD_KNOTS)), np.zeros((B, _abi.CMD_KNOTS, _abi.NX))
+        self._check(self.lib.hsqp_command_targets(self.h, B, v_cmd.ctypes.data_as(_dp), vf.ctypes.data_as(_dp), C.c_double(filter_alpha), x0.ctypes.data_as(_dp),
+                                                  C.c_double(t0), C.c_double(horizon), tt.ctypes.data_as(_dp), ts.ctypes.data_as(_dp)))
+        return tt, ts, vf
+
+    def command_targets_device(self, batch, v_cmd_ptr, v_filt_ptr, x0_ptr, t0, horizon, target_times_ptr, target_states_ptr, filter_alpha=0.0):
+        """hsqp_command_targets_device: the same with every array in device memory (addresses); v_filt is updated in place."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp)  # noqa: E731
+        self._check(self.lib.hsqp_command_targets_device(self.h, int(batch), cast(v_cmd_ptr), cast(v_filt_ptr), C.c_double(filter_alpha), cast(x0_ptr),
+                                                         C.c_double(t0), C.c_double(horizon), cast(target_times_ptr), cast(target_states_ptr)))
+
+    def loop_settings(self, n_nodes, dt, period=None, filter_alpha=None, iterations=1, take_step=True, kkt=False, linesearch=True, swing=None,
+                      terrain_height=0.0, arm_swing=True, integrator="ode45", controller="feedforward", **tolerances):
+        """hsqp_loop_settings: hsqp_loop_defaults (period 1 / 60 s, filter_alpha 0.8) with the grid, the iteration flags of iterate(), the
+        rollout settings of rollout_settings() and the model's swing configuration."""
+        from .reference import swing_config
+        st = _abi.LoopSettings()
+        self.lib.hsqp_loop_defaults(self.h, C.byref(st))
+        st.n_nodes, st.dt, st.iterations = int(n_nodes), float(dt), int(iterations)
+        if period is not None:
+            st.period = float(period)
+        if filter_alpha is not None:
+            st.filter_alpha = float(filter_alpha)
+        st.iterate_flags = (1 if take_step else 0) | (2 if kkt else 0) | (4 if linesearch else 0)
+        st.rollout = self.rollout_settings(integrator, controller, **tolerances)
+        st.swing = swing_config(self.model) if swing is None else swing
+        st.terrain_height, st.arm_swing = float(terrain_height), 1 if arm_swing else 0
+        return st
+
+    def loop_start(self, settings, t0, x0, v_cmd, n_events, event_times, mode_sequence):
+        """hsqp_loop_start: B = len(x0) instances, their commands [B][4] and mode schedules (reference.pack_reference's first three arrays),
+        uploaded once."""
+        x0 = _c(np.atleast_2d(x0))
+        B = x0.shape[0]
+        v_cmd = _c(np.broadcast_to(v_cmd, (B, _abi.CMD_N)))
+        n_events = np.ascontiguousarray(n_events, dtype=np.int32)
+        mode_sequence = np.ascontiguousarray(mode_sequence, dtype=np.int32)
+        event_times = _c(event_times)
+        if x0.shape != (B, _abi.NX) or n_events.shape != (B,) or event_times.ndim != 2 or event_times.shape[0] != B or \
+                mode_sequence.shape != (B, event_times.shape[1] + 1):
+            raise ValueError("inconsistent loop array shapes")
+        ip = C.POINTER(C.c_int32)
+        self._loop_batch = 0
+        self._check(self.lib.hsqp_loop_start(self.h, C.byref(settings), B, C.c_double(t0), x0.ctypes.data_as(_dp), v_cmd.ctypes.data_as(_dp), event_times.shape[1],
+                                             n_events.ctypes.data_as(ip), event_times.ctypes.data_as(_dp), mode_sequence.ctypes.data_as(ip)))
+        self._loop_batch = B
+        self._shape = (B, int(settings.n_nodes))
+
+    def loop_command(self, v_cmd):
+        """hsqp_loop_command: new commands [B][4], in effect from the next cycle."""
+        v_cmd = _c(np.broadcast_to(v_cmd, (self._loop_batch, _abi.CMD_N)) if self._loop_batch else v_cmd)   # (no loop: the library reports it)
+        self._check(self.lib.hsqp_loop_command(self.h, v_cmd.ctypes.data_as(_dp)))
+
+    def loop_command_device(self, v_cmd_ptr):
+        self._check(self.lib.hsqp_loop_command_device(self.h, C.cast(C.c_void_p(int(v_cmd_ptr)), _dp)))
+
+    def loop_run(self, n_cycles, log=True):
+        """hsqp_loop_run: dict(x[n, B, 58], u[n, B, 35], cycles_done) (x, u: the rows of the completed cycles; None without log).  A cycle
+        that fails raises HsqpError with that dict as its `result` attribute."""
+        B, n = max(self._loop_batch, 1), max(int(n_cycles), 1)
+        x = np.zeros((n, B, _abi.NX)) if log else None
+        u = np.zeros((n, B, _abi.NU)) if log else None
+        done = C.c_int(0)
+        rc = self.lib.hsqp_loop_run(self.h, int(n_cycles), x.ctypes.data_as(_dp) if log else None, u.ctypes.data_as(_dp) if log else None, C.byref(done))
+        out = dict(x=x[:done.value] if log else None, u=u[:done.value] if log else None, cycles_done=done.value)
+        if rc != 0:
+            err = HsqpError(rc, self.lib.hsqp_last_error(self.h).decode())
+            err.result = out
+            raise err
+        return out
+
+    def loop_run_device(self, n_cycles, x_log_ptr=0, u_log_ptr=0):
+        """hsqp_loop_run_device: logs in device memory (addresses; 0 = not wanted).  Returns the cycles done."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        done = C.c_int(0)
+        self._check(self.lib.hsqp_loop_run_device(self.h, int(n_cycles), cast(x_log_ptr), cast(u_log_ptr), C.byref(done)))
+        return done.value
+
+    def loop_state(self):
+        """hsqp_loop_state: (t, x[B, 58], v_filt[B, 4]) where the loop stands."""
+        B = max(self._loop_batch, 1)
+        t, x, vf = C.c_double(0.0), np.zeros((B, _abi.NX)), np.zeros((B, _abi.CMD_N))
+        self._check(self.lib.hsqp_loop_state(self.h, C.byref(t), x.ctypes.data_as(_dp), vf.ctypes.data_as(_dp)))
+        return t.value, x, vf
+
+    def loop_state_device(self, x_ptr=0, v_filt_ptr=0):
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        t = C.c_double(0.0)
+        self._check(self.lib.hsqp_loop_state_device(self.h, C.byref(t), cast(x_ptr), cast(v_filt_ptr)))
+        return t.value
 
     def joint_torques(self, x, u):
         x, u = _c(np.atleast_2d(x)), _c(np.atleast_2d(u))
