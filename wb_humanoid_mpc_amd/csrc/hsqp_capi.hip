@@ -115,17 +115,18 @@ __global__ __launch_bounds__(64) void k_params_cent_torso(const DevModel* __rest
   cent_params_torso(ctx, *dm, w, par + (size_t)blockIdx.x * NP);
 }
 
-// ---- projection: one workgroup per (instance, node)
-__global__ __launch_bounds__(PROJ_THREADS, PROJ_WPE) void k_project(const double* __restrict__ rec, const double* __restrict__ dts, double* __restrict__ qp, long long* prof, int cent, int joint_rows, int chain) {
+// ---- projection: one workgroup per (instance, node); n0: the first node of the launch's node range (hsqp_iterate_device)
+__global__ __launch_bounds__(PROJ_THREADS, PROJ_WPE) void k_project(const double* __restrict__ rec, const double* __restrict__ dts, double* __restrict__ qp, long long* prof, int cent, int joint_rows, int chain, int n0) {
   ProjWS& w = *reinterpret_cast<ProjWS*>(hsqp_smem);
-  const Ctx ctx{(int)threadIdx.x, PROJ_THREADS, blockIdx.x == 0 ? prof : nullptr};
+  const int node = n0 + blockIdx.x;
+  const Ctx ctx{(int)threadIdx.x, PROJ_THREADS, node == 0 ? prof : nullptr};
   PH_TICK(ctx, 126);  // re-arm the phase clock (bucket 126 is a sink)
-  project_node(ctx, w, rec + (size_t)blockIdx.x * REC_SIZE, dts[blockIdx.x], qp + (size_t)blockIdx.x * QP_SIZE, cent != 0, joint_rows != 0, chain != 0);
+  project_node(ctx, w, rec + (size_t)node * REC_SIZE, dts[node], qp + (size_t)node * QP_SIZE, cent != 0, joint_rows != 0, chain != 0);
 }
 
 // ---- event intervals (jump_node_qp, hsqp_project.h): one workgroup per node; only launched when the grid has such intervals
-__global__ __launch_bounds__(256) void k_jump(const double* __restrict__ dts, const double* __restrict__ rec, double* __restrict__ qp) {
-  const int node = blockIdx.x;
+__global__ __launch_bounds__(256) void k_jump(const double* __restrict__ dts, const double* __restrict__ rec, double* __restrict__ qp, int n0) {
+  const int node = n0 + blockIdx.x;
   if (dts[node] != 0.0) return;
   const Ctx ctx{(int)threadIdx.x, 256, nullptr};
   jump_node_qp(ctx, rec + (size_t)node * REC_SIZE, qp + (size_t)node * QP_SIZE);
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(QV_THREADS * QV_WAVES) __attribute__((amdgpu_waves_
 
 // ---- whole-body LQ approximation on limb lanes (hsqp_lql.h), kernel 1 of 3: the rigid-body model and its Jacobian at the four RK4 stages.  A wave
 //      evaluates QL_NODES nodes, one lane per limb; writes REC_GS (transposed) and REC_AS of the node's record.
-constexpr int LQ_SPLIT_DEFAULT = 2;   // node ranges of the limb-lane LQ kernels on streams of their own (hsqp_iterate_device)
+constexpr int LQ_SPLIT_DEFAULT = 2;   // node ranges of the limb-lane LQ kernels and of k_project behind them, on streams of their own (hsqp_iterate_device)
 constexpr int QL_WAVES = 2;           // waves per workgroup: they share the body constants
 constexpr int QL_WPE = 1, QR_WPE = 1;   // waves per SIMD the register budget of k_lq_limb / k_lq_rows is cut for (1: 512 registers per lane)
 struct QlWS {
@@ -1020,7 +1021,7 @@ struct hsqp_handle {
   hipEvent_t ev[6] = {};
   static constexpr int LQ_SPLIT_MAX = 8;
   int lq_round_blocks = 512;                   // workgroups of k_lq_limb / k_lq_rows the chip holds at once (4 waves per CU, QL_WAVES per workgroup)
-  int lq_split = 1;                            // node ranges of the limb-lane LQ kernels, each on its own stream (HSQP_LQ_SPLIT in the environment at hsqp_create)
+  int lq_split = 1;                            // node ranges of the limb-lane LQ kernels and of k_project behind them, each on its own stream (HSQP_LQ_SPLIT in the environment at hsqp_create)
   hipStream_t aux[LQ_SPLIT_MAX - 1] = {};
   hipEvent_t ev_fork = nullptr, ev_join[LQ_SPLIT_MAX - 1] = {};
   DevBuf<DevModel> d_dm;
@@ -1684,44 +1685,61 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     // (until_converged: any iteration may turn out to be the last one, so each is bracketed by the timing events and its times are summed)
     const bool last = it == n_iterations - 1 || until_converged;
     if (last) HCHECK(hipEventRecord(h->ev[0], h->stream));
-    if (cent) {
-      HSQP_LAUNCH(k_lq_cent2, dim3(nodes), dim3(CLQ_THREADS), sizeof(CentWST<true>), h->stream, h->d_dm, h->d_x, h->d_u, h->d_par, h->d_dt, N, h->d_rec);
-    }
-    else if (h->lq_limb) {   // limb lanes for the model and the node terms (16 nodes per wave), then the RK4 chain, a lane per column (hsqp_lql.h)
-      // Two of the three kernels run one wave per SIMD (limb, rows), so a launch of config 4 is 1.56 rounds of the chip's 1024 SIMDs and the
-      // last round of each leaves 44 % of them idle.  With lq_split = 2 the nodes are cut into two ranges, each going through its three
-      // kernels on a stream of its own: a range's next kernel fills the SIMDs the other range's previous kernel leaves (measured, 256 x 100:
-      // the three kernels 1.07 -> 0.97 ms; the bound of the arrangement, every SIMD busy throughout, is 0.92; three and more ranges lose
-      // again: 1.02 / 1.10 / 1.38 ms at 3 / 4 / 8).  Only when a launch is more than one round.
-      const dim3 qblock(QL_THREADS * QL_WAVES);
-      constexpr int QG = QL_NODES * QL_WAVES;
-      const int S = h->lq_split > 1 && (nodes + QG - 1) / QG > h->lq_round_blocks ? h->lq_split : 1;
-      if (S > 1) {
-        HCHECK(hipEventRecord(h->ev_fork, h->stream));
-        for (int s = 1; s < S; ++s) HCHECK(hipStreamWaitEvent(h->aux[s - 1], h->ev_fork, 0));
-      }
-      for (int s = 0; s < S; ++s) {
-        const int n0 = (int)(((long long)nodes * s / S) / QG * QG), n1 = s == S - 1 ? nodes : (int)(((long long)nodes * (s + 1) / S) / QG * QG);
-        hipStream_t st = s == 0 ? h->stream : h->aux[s - 1];
-        const dim3 qgrid((n1 - n0 + QG - 1) / QG);
-        HSQP_LAUNCH(k_lq_limb, qgrid, qblock, 0, st, h->d_dm, h->d_x, h->d_u, h->d_dt, N, n1, h->d_rec, h->d_prof + 384, n0);
-        HSQP_LAUNCH(k_lq_rows, qgrid, qblock, 0, st, h->d_dm, h->d_x, h->d_u, h->d_par, h->d_dt, N, n1, h->d_rec, h->d_prof + 384, n0, h->chain_fused ? 1 : 0);
-        if (!h->chain_fused) HSQP_LAUNCH(k_lq_chain, dim3(n1 - n0), dim3(LQC_THREADS), 0, st, h->d_x, h->d_u, h->d_dt, N, h->d_rec, n0, 1);   // (fused: the columns' chain runs in k_project, the defect on the lanes of k_lq_rows)
-        if (s > 0) { HCHECK(hipEventRecord(h->ev_join[s - 1], st)); HCHECK(hipStreamWaitEvent(h->stream, h->ev_join[s - 1], 0)); }
-      }
-    } else
-      HSQP_LAUNCH(k_lq<true>, dim3(nodes), dim3(LQ_THREADS), sizeof(LqWS), h->stream, h->d_dm, h->d_x, h->d_u, h->d_par, h->d_dt, N,
-                         h->d_rec, (double*)nullptr, h->d_prof, (const LsState*)nullptr);
-    if (last) HCHECK(hipEventRecord(h->ev[1], h->stream));
     const Sweep sweep = choose_sweep(h, B, N);
     const int segP = sweep.kind == Sweep::SEGMENTED ? sweep.P : 0;
     const bool scan = sweep.kind != Sweep::SERIAL;   // a KKT-gated sweep with the serial recursion as fallback
     // The joint rows of A~ / B~ (46 of 58: scaled copies of rows of [Px | Pu]) are written only for those who read A~ / B~ as dense blocks: the
     // parallel-in-time and two-level sweeps, the KKT report, the centroidal stage.  The whole-body serial sweep works on the factors.
     const bool joint_rows = cent || !h->ric_fact || scan || want_kkt;
-    HSQP_LAUNCH(k_project, dim3(nodes), dim3(PROJ_THREADS), sizeof(ProjWS), h->stream, h->d_rec, h->d_dt, h->d_qp, h->d_prof + 128, cent ? 1 : 0, joint_rows ? 1 : 0, (!cent && h->lq_limb && h->chain_fused) ? 1 : 0);
+    const int proj_chain = (!cent && h->lq_limb && h->chain_fused) ? 1 : 0;
+    // node ranges of the pipelined stages (S > 1: limb-lane form, a launch of more than one round of the chip): range s is the nodes
+    // range_begin(s) .. range_begin(s + 1) - 1, cut at the 32-node workgroups of the limb-lane LQ kernels
+    constexpr int QG = QL_NODES * QL_WAVES;
+    const int S = !cent && h->lq_limb && h->lq_split > 1 && (nodes + QG - 1) / QG > h->lq_round_blocks ? h->lq_split : 1;
+    auto range_begin = [&](int s) { return s >= S ? nodes : (int)(((long long)nodes * s / S) / QG * QG); };
+    auto range_stream = [&](int s) { return s == 0 ? h->stream : h->aux[s - 1]; };
+    if (cent) {
+      HSQP_LAUNCH(k_lq_cent2, dim3(nodes), dim3(CLQ_THREADS), sizeof(CentWST<true>), h->stream, h->d_dm, h->d_x, h->d_u, h->d_par, h->d_dt, N, h->d_rec);
+    }
+    else if (h->lq_limb) {   // limb lanes for the model and the node terms (16 nodes per wave), then the RK4 chain, a lane per column (hsqp_lql.h)
+      // Two of the three kernels run one wave per SIMD (limb, rows), so a launch of config 4 is 1.56 rounds of the chip's 1024 SIMDs and the
+      // last round of each leaves 44 % of them idle.  With lq_split = 2 the nodes are cut into two ranges, each going through its LQ
+      // kernels AND its k_project (and k_jump) on a stream of its own: a range's next kernel fills the SIMDs the other range's previous
+      // kernel leaves, and the projection of the range that is through first starts on the CUs the other range's last k_lq_rows round
+      // leaves free (a k_project workgroup is 49.5 KB of LDS and four waves of 120 VGPR: it fits wherever no LQ workgroup sits).
+      // project_node and jump_node_qp see their own node's record and QP block only, so a range boundary may lie inside an instance.
+      // The ranges join behind k_project: the backward sweep waits for all of the QP record.  (Measured, 256 x 100, the LQ kernels
+      // alone: 1.07 -> 0.97 ms at two ranges; three and more lose again: 1.02 / 1.10 / 1.38 ms at 3 / 4 / 8.  DESIGN.md section 4 has
+      // the drawing.)  Only when a launch is more than one round; S == 1 is one launch per kernel on h->stream.
+      // kernel_ms: ev[1] is recorded behind range 0's k_lq_rows and ev[2] behind the join, so with S > 1 what the other ranges' LQ
+      // kernels run past ev[1] lands in the project bucket; the buckets stay contiguous and sum to the total.
+      const dim3 qblock(QL_THREADS * QL_WAVES);
+      if (S > 1) {
+        HCHECK(hipEventRecord(h->ev_fork, h->stream));
+        for (int s = 1; s < S; ++s) HCHECK(hipStreamWaitEvent(h->aux[s - 1], h->ev_fork, 0));
+      }
+      for (int s = 0; s < S; ++s) {
+        const int n0 = range_begin(s), n1 = range_begin(s + 1);
+        hipStream_t st = range_stream(s);
+        const dim3 qgrid((n1 - n0 + QG - 1) / QG);
+        HSQP_LAUNCH(k_lq_limb, qgrid, qblock, 0, st, h->d_dm, h->d_x, h->d_u, h->d_dt, N, n1, h->d_rec, h->d_prof + 384, n0);
+        HSQP_LAUNCH(k_lq_rows, qgrid, qblock, 0, st, h->d_dm, h->d_x, h->d_u, h->d_par, h->d_dt, N, n1, h->d_rec, h->d_prof + 384, n0, h->chain_fused ? 1 : 0);
+        if (!h->chain_fused) HSQP_LAUNCH(k_lq_chain, dim3(n1 - n0), dim3(LQC_THREADS), 0, st, h->d_x, h->d_u, h->d_dt, N, h->d_rec, n0, 1);   // (fused: the columns' chain runs in k_project, the defect on the lanes of k_lq_rows)
+        if (s == 0 && last) HCHECK(hipEventRecord(h->ev[1], h->stream));
+        HSQP_LAUNCH(k_project, dim3(n1 - n0), dim3(PROJ_THREADS), sizeof(ProjWS), st, h->d_rec, h->d_dt, h->d_qp, h->d_prof + 128, 0, joint_rows ? 1 : 0, proj_chain, n0);
+        if (h->has_events) HSQP_LAUNCH(k_jump, dim3(n1 - n0), dim3(256), 0, st, h->d_dt, h->d_rec, h->d_qp, n0);
+        if (s > 0) HCHECK(hipEventRecord(h->ev_join[s - 1], st));
+      }
+      for (int s = 1; s < S; ++s) HCHECK(hipStreamWaitEvent(h->stream, h->ev_join[s - 1], 0));
+    } else
+      HSQP_LAUNCH(k_lq<true>, dim3(nodes), dim3(LQ_THREADS), sizeof(LqWS), h->stream, h->d_dm, h->d_x, h->d_u, h->d_par, h->d_dt, N,
+                         h->d_rec, (double*)nullptr, h->d_prof, (const LsState*)nullptr);
+    if (cent || !h->lq_limb) {
+      if (last) HCHECK(hipEventRecord(h->ev[1], h->stream));
+      HSQP_LAUNCH(k_project, dim3(nodes), dim3(PROJ_THREADS), sizeof(ProjWS), h->stream, h->d_rec, h->d_dt, h->d_qp, h->d_prof + 128, cent ? 1 : 0, joint_rows ? 1 : 0, proj_chain, 0);
+      if (h->has_events) HSQP_LAUNCH(k_jump, dim3(nodes), dim3(256), 0, h->stream, h->d_dt, h->d_rec, h->d_qp, 0);
+    }
     h->qp_joint_rows = joint_rows;
-    if (h->has_events) HSQP_LAUNCH(k_jump, dim3(nodes), dim3(256), 0, h->stream, h->d_dt, h->d_rec, h->d_qp);
     if (last) HCHECK(hipEventRecord(h->ev[2], h->stream));
     if (want_kkt) DEV_ENSURE(h->d_vf, vf_bytes(h), "value functions");
     const int Bm = h->st.max_batch;
@@ -1750,6 +1768,9 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
                            h->d_par, h->d_dt, N, 1.0, h->d_ut, h->d_du, h->d_xnew, h->d_unew, h->d_stepinfo, h->d_misc, h->d_prof + 384, ut_given,
                            fj_given ? (const double*)h->d_fj : (const double*)nullptr);
       else {   // the step (HBM-bound); whole-body: then the value pass on quads of lanes (centroidal: launch_perf)
+        // (k_step and k_value_quad are NOT taken through the node ranges: measured at 256 x 100 with two ranges, the value pass of the
+        // high range on an aux stream beside the step of the low range, the bucket went from 0.193 to 0.228 ms — two 45 us halves of
+        // k_step and two cross-stream waits cost more than the overlap returns.  DESIGN.md section 8)
         HSQP_LAUNCH(k_step, dim3(nodes), dim3(64), 0, h->stream, h->d_qp, h->d_ric, h->d_dx, h->d_x, h->d_u, N, 1.0, h->d_ut, h->d_du,
                            h->d_xnew, h->d_unew, h->d_stepinfo, ut_given, fj_given ? (const double*)h->d_fj : (const double*)nullptr);
         if (!cent) launch_value_pass(h, nullptr);
