@@ -41,6 +41,7 @@ constexpr int LQV_THREADS = 64, LQV_WPE = 2;   // value-only pass (19.2 KB works
 constexpr size_t VALUE_QUAD_MIN_NODES = 2048;   // handles sized below this keep the phase form of the whole-body value pass (hsqp_create)
 constexpr size_t LQ_LIMB_MIN_NODES = 2048;      // handles sized below this keep the phase form of the whole-body LQ kernel (hsqp_create)
 constexpr int PROJ_THREADS = 256, PROJ_WPE = 3;   // 49.5 KB workspace: three workgroups of four waves per CU
+static_assert(PROJ_THREADS == 256 && PROJ_THREADS - hsqp::GRAM_BP >= 192, "gram_rows (hsqp_project.h): four waves carry the fifteen tiles, the border pairs sit on the last lanes of wave 3");
 static_assert(PROJ_THREADS >= 256 && PROJ_THREADS % 64 == 0, "project_node hoists its staging loads assuming >= 256 threads; the Gram tiles are dealt to waves 0..3");
 // Every kernel hands its workgroup size to the device functions as the CONSTANT it is launched with (Ctx::nthreads), not as blockDim.x: the item loops
 // (WG_FOR) then have constant strides and trip counts, and the paths written for other workgroup shapes (the host build's) are not compiled into the

@@ -204,6 +204,7 @@ __device__ inline double readlane_f64(double v, int lane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 typedef double hsqp_d4 __attribute__((ext_vector_type(4)));
+typedef double hsqp_d2 __attribute__((ext_vector_type(2)));   // 16-byte aligned: one ds_read_b128 / ds_write_b128
 typedef const double __attribute__((address_space(1))) * hsqp_gcptr;
 typedef double __attribute__((address_space(1))) * hsqp_gptr;
 typedef const double __attribute__((address_space(3))) * hsqp_lcptr;

@@ -39,7 +39,7 @@ constexpr int LDTM = 82;                       // leading dimension of Tm = [Px 
 // The 64 residual row slots are projected in passes of NRP rows (24 + 24 + 16) through one small LDS block; the projected
 // Gauss-Newton Hessian J~^T J~ is accumulated ACROSS the passes in registers (the matrix-core accumulators of the 15 tiles on /
 // above the diagonal of its leading 80 x 80 block, dealt to the four waves; the last projected input and the gradient column
-// as per-thread sums), and the 35 input-weight rows sqrt(d_u) [Px | Pu | Pe] are accumulated straight from Tm.  Nothing of the
+// as vector-pipe sums of 41 threads, a pair of rows each: GRAM_BP below), and the 35 input-weight rows sqrt(d_u) [Px | Pu | Pe] are accumulated straight from Tm.  Nothing of the
 // Hessian makes a round trip through memory between the passes, and the workspace is 49.5 KB: three workgroups per CU.
 constexpr int NRP = 24;
 static_assert(NRP % 4 == 0 && NRS == 2 * NRP + 16, "pass sizes");
@@ -104,17 +104,27 @@ HSQP_HD void jump_node_qp(const Ctx& ctx, const double* rec, double* qp) {
 
 // ---- Gram accumulation across the passes: H (+)= X^T diag(s) X over the rows of X (columns 0..81 of Jt or Tm; column 81 carries
 // rho', so the same sums also give the gradient J~^T rho').  Device: each wave owns the accumulators of up to four 16 x 16 tiles on /
-// above the diagonal of the leading 80 x 80 block; threads 0..161 own one element each of column 80 (the last projected input) and
-// of the gradient column.  Host build: a plain upper-triangular array.
+// above the diagonal of the leading 80 x 80 block; the last GRAM_BP = 41 threads own a pair of rows each of column 80 (the last projected
+// input) and of the gradient column.  Host build: a plain upper-triangular array.
 struct GramAcc {
 #if defined(__HIP_DEVICE_COMPILE__)
   hsqp_d4 acc[4];
   int xr[4], yc[4], nt;
-  double vs;
+  double bs[4];                  // border sums (a, 80), (a, 81), (a + 1, 80), (a + 1, 81) of the thread's pair of rows a = ba, a + 1
+  int ba;                        // -1: the thread carries no border sums
 #else
   std::vector<double> h;         // [NTW][NTW + 1]: h[a][c] for a <= c <= 80, h[a][81] = gradient
 #endif
 };
+
+// The border of the tile grid (82 = 5 x 16 + 2: column 80, the last projected input, and the gradient column 81) is summed on the vector pipe.  A thread owns a PAIR
+// of adjacent rows a, a + 1 of BOTH border columns: per row of X one 16-byte read of X[r][a .. a + 1], one (wave-uniform address) of X[r][80 .. 81], four independent
+// multiply-adds.  Every sum still runs over the rows in their order, one multiply-add per row: bit for bit what one thread per element gave (162 threads on 2.5 waves,
+// two 8-byte reads per multiply-add, ONE dependent chain per thread) at a third of its LDS reads.  The 41 pairs sit on the last threads of wave 3, which carries three
+// of the fifteen tiles (the others four).
+constexpr int GRAM_BP = (NTW + 1) / 2;
+static_assert(2 * GRAM_BP == NTW + 1 && GRAM_BP <= 64, "column pairs on one wave (the LAST wave of the workgroup: hsqp_capi.hip asserts PROJ_THREADS against it)");
+static_assert(LDTM % 2 == 0 && offsetof(ProjWS, Tm) % 16 == 0 && offsetof(ProjWS, ps.Jt) % 16 == 0, "16-byte reads of column pairs");
 
 HSQP_HD void gram_init(const Ctx& ctx, GramAcc& g) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -131,7 +141,9 @@ HSQP_HD void gram_init(const Ctx& ctx, GramAcc& g) {
     g.acc[t] = hsqp_d4{0.0, 0.0, 0.0, 0.0};
     if (id < NGT * (NGT + 1) / 2) g.nt = t + 1;
   }
-  g.vs = 0.0;
+  const int bp = ctx.nthreads - 1 - ctx.tid;
+  g.ba = bp < GRAM_BP ? 2 * bp : -1;
+  g.bs[0] = g.bs[1] = g.bs[2] = g.bs[3] = 0.0;
 #else
   (void)ctx;
   g.h.assign((size_t)NTW * (NTW + 1), 0.0);
@@ -160,18 +172,19 @@ HSQP_HD void gram_rows(const Ctx& ctx, GramAcc& g, const double* X, int ldx, con
       }
     }
   }
-  // (the 162 per-thread sums sit on the LAST threads of the workgroup: wave 3 carries three of the fifteen tiles, the others four)
-  const int vt = ctx.nthreads - 1 - ctx.tid;
-  if (vt < 2 * NTW) {
-    const int a = vt < NTW ? vt : vt - NTW, cb = vt < NTW ? NTW - 1 : NTW;
-    double s = g.vs;
+  if (g.ba >= 0) {
+    const double* xa = X + g.ba;
 #pragma unroll 4
     for (int r = 0; r < NR; ++r) {
-      double xb = X[r * ldx + cb];
-      if (WEIGHT) xb = du[r] * xb + (cb == NTW ? gdu[r] : 0.0);
-      s += X[r * ldx + a] * xb;
+      const hsqp_d2 a = *reinterpret_cast<const hsqp_d2*>(xa + r * ldx);
+      const hsqp_d2 b = *reinterpret_cast<const hsqp_d2*>(X + r * ldx + NTW - 1);
+      double b0 = b[0], b1 = b[1];
+      if (WEIGHT) { b0 = du[r] * b0 + 0.0; b1 = du[r] * b1 + gdu[r]; }   // (+ 0.0: the sign of a zero as before)
+      g.bs[0] += a[0] * b0;
+      g.bs[1] += a[0] * b1;
+      g.bs[2] += a[1] * b0;
+      g.bs[3] += a[1] * b1;
     }
-    g.vs = s;
   }
 #else
   (void)ctx;
@@ -222,9 +235,11 @@ HSQP_HD void gram_store(const Ctx& ctx, const GramAcc& g, const ProjWS& w, int n
       }
     }
   }
-  const int vt = ctx.nthreads - 1 - ctx.tid;
-  if (vt < NTW) put(vt, NTW - 1, g.vs);
-  else if (vt < 2 * NTW) put_grad(vt - NTW, g.vs);
+  if (g.ba >= 0) {
+    put(g.ba, NTW - 1, g.bs[0]);
+    put_grad(g.ba, g.bs[1]);
+    if (g.ba + 1 < NTW) { put(g.ba + 1, NTW - 1, g.bs[2]); put_grad(g.ba + 1, g.bs[3]); }   // (the last pair's second row is the gradient column itself)
+  }
 #else
   (void)ctx;
   for (int a = 0; a < NTW; ++a) {
