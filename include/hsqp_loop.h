@@ -50,8 +50,9 @@
  * hsqp_rollout_policy refuses, n_events outside [1, max_events], n_cycles < 1, a non-finite command (host arrays) or t0.  Start states are
  * not checked: a non-finite one surfaces the way it does in the underlying calls (HSQP_ERR_NUMERIC from the solution's status).
  *
- * Out of scope: the gait auto-transition of preSolverRun (transitionToFasterGait / ...Slower...: host logic — re-start the loop with the new
- * schedule), the motion manager's own BreakFrequencyAlphaFilter in front of the generator, event grids (hsqp_reference::node_times), the
+ * The gait auto-transition of preSolverRun (transitionToFasterGait / ...Slower...) and the re-tiling of the schedule in every cycle are in
+ * include/hsqp_gait.h: hsqp_loop_start_gait starts this loop with a per-instance gait schedule and ladder resident on the device.
+ * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, event grids (hsqp_reference::node_times), the
  * centroidal formulation, several GPUs.
  *
  * ABI: additions only — no public struct and no entry point of hsqp.h, hsqp_feedback.h or hsqp_rollout.h changes, HSQP_ABI_VERSION stays.

@@ -7,7 +7,11 @@ reports one hsqp_loop_run(cycles) call per cycle (`run_ms_per_cycle`), which is 
 Prints one JSON line with the fields of tools/closed_loop_cycle.py (no rollout share and no step counts: the loop does not stop between the
 iteration and the rollout, and its rollout keeps no step counters).
     python tools/device_loop_cycle.py [--cycles 30] [--warmup 3] [--batch 256] [--nodes 100] [--controller feedforward|feedback]
-                                      [--commands same|spread]
+                                      [--commands same|spread] [--gait ladder|walk]
+--gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
+and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
+command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
+reports the rungs at the end; walk: --commands from the start (feet lift about one second in: choose --warmup 120 to time walking cycles).
 --commands same: every instance is commanded (0.3, 0, 0.7925, 0), the other tool's command; spread: vx from 0 to 0.6 m/s and yaw rates from
 -0.2 to 0.2 rad/s across the batch.
 """
@@ -22,7 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from wb_humanoid_mpc_amd import load_model  # noqa: E402
-from wb_humanoid_mpc_amd.reference import pack_reference, tile_gait, velocity_command_targets  # noqa: E402
+from wb_humanoid_mpc_amd.reference import gait_settings, pack_reference, tile_gait, velocity_command_targets  # noqa: E402
 from wb_humanoid_mpc_amd.solver import HipSqpSolver  # noqa: E402
 
 
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--controller", default="feedforward", choices=("feedforward", "feedback"))
     ap.add_argument("--commands", default="same", choices=("same", "spread"))
     ap.add_argument("--filter-alpha", type=float, default=0.8)
+    ap.add_argument("--gait", default=None, choices=("ladder", "walk"))
     args = ap.parse_args()
     m = load_model()
     B, N, dt = args.batch, args.nodes, m.sqp["dt"]
@@ -55,9 +60,23 @@ def main():
     st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True,
                          controller=args.controller)
     cycle_ms, heights = [], []
+    changes = {}
+    if args.gait == "ladder":
+        zero = np.tile((0.0, 0.0, 0.7925, 0.0), (B, 1))
+        go, k = zero.copy(), np.arange(B) % 4
+        go[(k == 1) | (k == 2), 0] = 0.2
+        go[k == 3, 3] = 0.3
+        stop = go.copy()
+        stop[k == 2, 0] = 0.0
+        cmd, changes = zero, {10: go, 40: stop}
     try:
-        s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
+        if args.gait:
+            s.loop_start(st, 0.0, x_init, cmd, gait=gait_settings(m))
+        else:
+            s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
         for c in range(args.warmup + args.cycles):
+            if c in changes:
+                s.loop_command(changes[c])
             t_a = time.perf_counter()
             r = s.loop_run(1)
             t_b = time.perf_counter()
@@ -68,13 +87,14 @@ def main():
         r = s.loop_run(args.cycles, log=False)
         run_ms = 1e3 * (time.perf_counter() - t_a) / args.cycles
         t_end, x_end, v_filt = s.loop_state()
+        rungs = np.bincount(s.gait_state()["rung"], minlength=7).tolist() if args.gait else None
         heights.append(x_end[:, 2].copy())
     finally:
         s.close()
     heights = np.concatenate(heights)
     q = np.percentile(cycle_ms, [25, 75])
     print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
-                      "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha,
+                      "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),
                       "run_ms_per_cycle": round(float(run_ms), 3), "t_end": round(float(t_end), 6),

@@ -127,6 +127,26 @@ CMD_N, CMD_KNOTS = 4, 3   # HSQP_CMD_N, HSQP_CMD_KNOTS
 LOOP_ENTRY_POINTS = ("hsqp_set_default_joint_state", "hsqp_command_targets", "hsqp_command_targets_device", "hsqp_loop_defaults", "hsqp_loop_start",
                      "hsqp_loop_command", "hsqp_loop_command_device", "hsqp_loop_run", "hsqp_loop_run_device", "hsqp_loop_state", "hsqp_loop_state_device")
 
+# include/hsqp_gait.h
+GAIT_MAX_RUNGS, GAIT_MAX_PHASES, GAIT_MAX_EVENTS, GAIT_NAME_LEN = 16, 6, 256, 16
+GAIT_OK, GAIT_OVERFLOW, GAIT_BAD_TILING = 0, 1, 2
+
+
+class GaitRung(C.Structure):   # hsqp_gait_rung
+    _fields_ = [("min_lin_vel_cmd", C.c_double), ("max_lin_vel_cmd", C.c_double), ("min_ang_vel_cmd", C.c_double), ("max_ang_vel_cmd", C.c_double),
+                ("lin_vel_error_thresh", C.c_double), ("ang_vel_error_thresh", C.c_double), ("n_phases", C.c_int32), ("reserved", C.c_int32),
+                ("switching_times", C.c_double * (GAIT_MAX_PHASES + 1)), ("modes", C.c_int32 * GAIT_MAX_PHASES), ("name", C.c_char * GAIT_NAME_LEN)]
+
+
+class GaitSettings(C.Structure):   # hsqp_gait_settings
+    _fields_ = [("n_rungs", C.c_int32), ("max_events", C.c_int32), ("phase_transition_stance_time", C.c_double), ("min_change_interval", C.c_double),
+                ("rungs", GaitRung * GAIT_MAX_RUNGS)]
+
+
+# entry points of include/hsqp_gait.h (tests/test_gait.py checks that the library exports each of them and the binding declares it)
+GAIT_ENTRY_POINTS = ("hsqp_gait_ladder_defaults", "hsqp_gait_reset", "hsqp_gait_update", "hsqp_gait_update_device", "hsqp_gait_state", "hsqp_gait_state_device",
+                     "hsqp_loop_start_gait")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

@@ -21,6 +21,7 @@
 #include "hsqp_rollout.h"
 #include "hsqp_loop.h"
 #include "../../include/hsqp_loop.h"
+#include "hsqp_gait.h"
 #include "hsqp_warm.h"
 #include "hsqp_cent.h"
 #include "hsqp_cent_lq.h"
@@ -801,6 +802,18 @@ __global__ __launch_bounds__(CMDT_THREADS) void k_command_targets(const DevModel
   if (live) command_item_store(it, dm->default_joint_state, x0, t0, horizon, id, v_filt, tt, ts);
 }
 
+// ---- gait schedule and ladder (hsqp_gait.h): one wave per instance, the work row of its schedule in LDS; reads the live state `in`, writes the shadow
+// state `out` and one status word per instance (the host swaps the two after it has read the words)
+__global__ __launch_bounds__(64) void k_gait_update(const hsqp_gait_settings* __restrict__ gs, GaitState in, GaitState out, double t, double horizon,
+                                                    const double* __restrict__ v_filt, const double* __restrict__ x, int* __restrict__ n_out,
+                                                    double* __restrict__ ev_out, int* __restrict__ seq_out, int* __restrict__ status) {
+  __shared__ GaitWork w;
+  const int b = blockIdx.x, E = gs->max_events;
+  const int st = gait_update_instance(Ctx{(int)threadIdx.x, 64, nullptr}, *gs, w, in, out, b, t, horizon, v_filt + (size_t)b * CMD_N, x + (size_t)b * NX, n_out + b,
+                                      ev_out + (size_t)b * E, seq_out + (size_t)b * (E + 1));
+  if (threadIdx.x == 0) status[b] = st;
+}
+
 // ---- receding-horizon warm start (hsqp_warm.h) behind k_params: one wave per node of the new grid, WARM_WAVES nodes per workgroup
 // (blockIdx.x), one instance per blockIdx.y; the instance's previous stamps are staged in LDS once per workgroup (SHIFT)
 constexpr int WARM_WAVES = 4;
@@ -1095,7 +1108,19 @@ struct hsqp_handle {
     int* ne = nullptr; int* seq = nullptr; int* bad = nullptr; int32_t* ro_status = nullptr;
     double* ev = nullptr; double* tt = nullptr; double* ts = nullptr; double* s0 = nullptr;
     double* v_cmd = nullptr; double* v_filt = nullptr; double* x = nullptr; double* xs = nullptr; double* us = nullptr;
+    bool gait = false;                          // started through hsqp_loop_start_gait: ne / seq / ev are written by k_gait_update in every cycle
   } loop;
+  // the resident gait state (include/hsqp_gait.h): two copies carved from d_gait, s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
+  struct Gait {
+    bool ready = false;
+    hsqp_gait_settings st;
+    int B = 0, cur = 0;
+    hsqp_gait_settings* d_st = nullptr;
+    GaitState s[2] = {};
+    int* status = nullptr; int* ne = nullptr; int* seq = nullptr;
+    double* ev = nullptr; double* v = nullptr; double* x = nullptr;
+  } gait;
+  DevBuf<char> d_gait;
   DevBuf<char> d_loop, d_loop_log;   // the loop's resident arrays; staging of hsqp_loop_run's host logs and of hsqp_command_targets' host arrays
   double kernel_ms[5] = {0, 0, 0, 0, 0};
   int last_iterations = 0;
@@ -2368,13 +2393,15 @@ void hsqp_loop_defaults(const hsqp_handle* h, hsqp_loop_settings* s) {
   s->terrain_height = 0.0;
 }
 
-int hsqp_loop_start(hsqp_handle* h, const hsqp_loop_settings* st, int batch, double t0, const double* x0, const double* v_cmd, int max_events,
-                    const int32_t* n_events, const double* event_times, const int32_t* mode_sequence) {
+static int gait_reset_impl(hsqp_handle* h, const char* who, const hsqp_gait_settings* gs, int batch, double t0);
+
+// hsqp_loop_start (schedules uploaded once) and hsqp_loop_start_gait (gait != null: the resident gait state owns the schedule, max_events is its capacity)
+static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_settings* st, const hsqp_gait_settings* gait, int batch, double t0, const double* x0,
+                           const double* v_cmd, int max_events, const int32_t* n_events, const double* event_times, const int32_t* mode_sequence) {
   if (!h) return HSQP_ERR_BAD_ARG;
-  const char* who = "hsqp_loop_start";
   h->loop.started = false;
   { const int rc = loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
-  if (!st || !x0 || !v_cmd || !n_events || !event_times || !mode_sequence) return loop_bad(h, who, "null settings or array");
+  if (!st || !x0 || !v_cmd || (!gait && (!n_events || !event_times || !mode_sequence))) return loop_bad(h, who, "null settings or array");
   if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
   if (st->n_nodes < 1 || st->n_nodes > h->st.max_nodes) return loop_bad(h, who, "n_nodes outside [1, max_nodes]");
   const auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
@@ -2387,10 +2414,12 @@ int hsqp_loop_start(hsqp_handle* h, const hsqp_loop_settings* st, int batch, dou
   if (!std::isfinite(t0)) return loop_bad(h, who, "t0 not finite");
   if (max_events < 1) return loop_bad(h, who, "max_events < 1");
   const size_t B = batch, E = max_events;
-  for (size_t b = 0; b < B; ++b)
-    if (n_events[b] < 1 || n_events[b] > max_events) return loop_bad(h, who, "n_events outside [1, max_events]");
+  if (!gait)
+    for (size_t b = 0; b < B; ++b)
+      if (n_events[b] < 1 || n_events[b] > max_events) return loop_bad(h, who, "n_events outside [1, max_events]");
   if (!all_finite(v_cmd, B * CMD_N)) return loop_bad(h, who, "non-finite command");
   HCHECK(hipSetDevice(h->device));
+  if (gait) { const int rc = gait_reset_impl(h, who, gait, batch, t0); if (rc != HSQP_OK) return rc; }
   // the loop's resident arrays, carved from one buffer
   size_t o = 0;
   const auto carve = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
@@ -2406,9 +2435,11 @@ int hsqp_loop_start(hsqp_handle* h, const hsqp_loop_settings* st, int batch, dou
   L.v_filt = reinterpret_cast<double*>(base + o_vf); L.x = reinterpret_cast<double*>(base + o_x); L.xs = reinterpret_cast<double*>(base + o_xs);
   L.us = reinterpret_cast<double*>(base + o_us);
   StickyError step{h};
-  step(hipMemcpyAsync(L.ne, n_events, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
-  step(hipMemcpyAsync(L.seq, mode_sequence, B * (E + 1) * 4, hipMemcpyHostToDevice, h->stream), "upload mode_sequence");
-  step(hipMemcpyAsync(L.ev, event_times, B * E * 8, hipMemcpyHostToDevice, h->stream), "upload event_times");
+  if (!gait) {
+    step(hipMemcpyAsync(L.ne, n_events, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
+    step(hipMemcpyAsync(L.seq, mode_sequence, B * (E + 1) * 4, hipMemcpyHostToDevice, h->stream), "upload mode_sequence");
+    step(hipMemcpyAsync(L.ev, event_times, B * E * 8, hipMemcpyHostToDevice, h->stream), "upload event_times");
+  }
   step(hipMemcpyAsync(L.v_cmd, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
   step(hipMemcpyAsync(L.v_filt, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_filt");
   step(hipMemcpyAsync(L.x, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
@@ -2417,8 +2448,14 @@ int hsqp_loop_start(hsqp_handle* h, const hsqp_loop_settings* st, int batch, dou
   if (step.rc != HSQP_OK) return step.rc;
   L.st = *st; L.B = batch; L.E = max_events; L.t = t0;
   L.have_cycle = false;
+  L.gait = gait != nullptr;
   L.started = true;
   return HSQP_OK;
+}
+
+int hsqp_loop_start(hsqp_handle* h, const hsqp_loop_settings* st, int batch, double t0, const double* x0, const double* v_cmd, int max_events,
+                    const int32_t* n_events, const double* event_times, const int32_t* mode_sequence) {
+  return loop_start_impl(h, "hsqp_loop_start", st, nullptr, batch, t0, x0, v_cmd, max_events, n_events, event_times, mode_sequence);
 }
 
 static int loop_started(hsqp_handle* h, const char* who) {
@@ -2441,6 +2478,199 @@ static int loop_command_impl(hsqp_handle* h, const double* v_cmd, bool dev) {
 int hsqp_loop_command(hsqp_handle* h, const double* v_cmd) { return loop_command_impl(h, v_cmd, false); }
 int hsqp_loop_command_device(hsqp_handle* h, const double* d_v_cmd) { return loop_command_impl(h, d_v_cmd, true); }
 
+// ---- per-instance gait schedule and ladder (include/hsqp_gait.h, csrc/hsqp_gait.h)
+static const char* gait_settings_error(const hsqp_gait_settings& g, std::string& text) {
+  if (g.n_rungs < 1 || g.n_rungs > HSQP_GAIT_MAX_RUNGS) return "n_rungs outside [1, HSQP_GAIT_MAX_RUNGS]";
+  if (g.max_events < 2 || g.max_events > HSQP_GAIT_MAX_EVENTS) return "max_events outside [2, HSQP_GAIT_MAX_EVENTS]";
+  if (!std::isfinite(g.phase_transition_stance_time) || g.phase_transition_stance_time < 0.0) return "phase_transition_stance_time not finite and >= 0";
+  if (!std::isfinite(g.min_change_interval) || g.min_change_interval < 0.0) return "min_change_interval not finite and >= 0";
+  for (int r = 0; r < g.n_rungs; ++r) {
+    const hsqp_gait_rung& c = g.rungs[r];
+    const std::string name(c.name, strnlen(c.name, HSQP_GAIT_NAME_LEN));
+    const std::string where = "rung " + std::to_string(r) + " (" + name + "): ";
+    const double th[6] = {c.min_lin_vel_cmd, c.max_lin_vel_cmd, c.min_ang_vel_cmd, c.max_ang_vel_cmd, c.lin_vel_error_thresh, c.ang_vel_error_thresh};
+    for (double v : th) if (!std::isfinite(v)) { text = where + "non-finite threshold"; return text.c_str(); }
+    if (c.n_phases < 1 || c.n_phases > HSQP_GAIT_MAX_PHASES) { text = where + "n_phases outside [1, HSQP_GAIT_MAX_PHASES]"; return text.c_str(); }
+    for (int i = 0; i < c.n_phases; ++i)
+      if (c.modes[i] < HSQP_MODE_FLY || c.modes[i] > HSQP_MODE_STANCE) { text = where + "mode outside 0 .. 3"; return text.c_str(); }
+    for (int i = 0; i <= c.n_phases; ++i) if (!std::isfinite(c.switching_times[i])) { text = where + "non-finite switching time"; return text.c_str(); }
+    for (int i = 0; i < c.n_phases; ++i)
+      if (!(c.switching_times[i + 1] > c.switching_times[i])) {
+        text = where + "switching times not strictly increasing (" + std::to_string(c.switching_times[i]) + " is followed by " + std::to_string(c.switching_times[i + 1]) +
+               "; gait.info's skip is such a template)";
+        return text.c_str();
+      }
+  }
+  return nullptr;
+}
+
+void hsqp_gait_ladder_defaults(hsqp_gait_settings* s) {
+  if (!s) return;
+  memset(s, 0, sizeof(*s));
+  // ProceduralMpcMotionManager.h:110-118
+  static const struct { const char* name; double v[6]; } rows[7] = {
+      {"stance", {-0.1, 0.1, -0.1, 0.1, 10.0, 10.0}},   {"slow_walk", {0.05, 0.3, 0.05, 0.2, 0.05, 0.05}}, {"walk", {0.25, 0.5, 0.15, 0.35, 0.05, 0.05}},
+      {"slower_trot", {0.45, 0.7, 0.3, 0.55, 0.1, 0.1}}, {"slow_trot", {0.65, 0.9, 0.5, 0.7, 0.2, 0.2}},   {"trot", {0.8, 1.3, 0.65, 10.0, 0.2, 0.2}},
+      {"run", {1.2, 10.0, 0.65, 10.0, 0.2, 0.2}}};
+  s->n_rungs = 7;
+  s->max_events = 128;
+  s->phase_transition_stance_time = 0.0;   // task.info phaseTransitionStanceTime
+  s->min_change_interval = 0.2;            // ProceduralMpcMotionManager.cpp:134
+  for (int r = 0; r < 7; ++r) {
+    hsqp_gait_rung& c = s->rungs[r];
+    c.min_lin_vel_cmd = rows[r].v[0]; c.max_lin_vel_cmd = rows[r].v[1]; c.min_ang_vel_cmd = rows[r].v[2]; c.max_ang_vel_cmd = rows[r].v[3];
+    c.lin_vel_error_thresh = rows[r].v[4]; c.ang_vel_error_thresh = rows[r].v[5];
+    strncpy(c.name, rows[r].name, HSQP_GAIT_NAME_LEN - 1);
+  }
+}
+
+static int gait_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) return loop_bad(h, who, "whole-body handles only (the ladder reads the base velocity from the whole-body state)");
+  return HSQP_OK;
+}
+
+// the initial state of `batch` instances at t0, in both copies' place (the live one is copy 0)
+static int gait_reset_impl(hsqp_handle* h, const char* who, const hsqp_gait_settings* gs, int batch, double t0) {
+  h->gait.ready = false;
+  { const int rc = gait_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (!gs) return loop_bad(h, who, "null gait settings");
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (!std::isfinite(t0)) return loop_bad(h, who, "t0 not finite");
+  { std::string text; if (const char* what = gait_settings_error(*gs, text)) return loop_bad(h, who, what); }
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = batch, E = gs->max_events;
+  size_t o = 0;
+  const auto carve = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+  const size_t o_st = carve(sizeof(hsqp_gait_settings)), o_status = carve(B * 4), o_ne = carve(B * 4), o_seq = carve(B * (E + 1) * 4), o_ev = carve(B * E * 8),
+               o_v = carve(B * CMD_N * 8), o_x = carve(B * NX * 8);
+  size_t o_s[2][5];
+  for (int c = 0; c < 2; ++c) { o_s[c][0] = carve(B * 4); o_s[c][1] = carve(B * E * 8); o_s[c][2] = carve(B * (E + 1) * 4); o_s[c][3] = carve(B * GAIT_SCAL * 4); o_s[c][4] = carve(B * 8); }
+  DEV_ENSURE(h->d_gait, o, "gait state");
+  char* base = h->d_gait.p;
+  hsqp_handle::Gait& G = h->gait;
+  G.d_st = reinterpret_cast<hsqp_gait_settings*>(base + o_st); G.status = reinterpret_cast<int*>(base + o_status); G.ne = reinterpret_cast<int*>(base + o_ne);
+  G.seq = reinterpret_cast<int*>(base + o_seq); G.ev = reinterpret_cast<double*>(base + o_ev); G.v = reinterpret_cast<double*>(base + o_v);
+  G.x = reinterpret_cast<double*>(base + o_x);
+  for (int c = 0; c < 2; ++c)
+    G.s[c] = GaitState{reinterpret_cast<int*>(base + o_s[c][0]), reinterpret_cast<double*>(base + o_s[c][1]), reinterpret_cast<int*>(base + o_s[c][2]),
+                       reinterpret_cast<int*>(base + o_s[c][3]), reinterpret_cast<double*>(base + o_s[c][4])};
+  // reference.info initialModeSchedule {[0.5], [STANCE, STANCE]} offset by t0; rung 0, its template, both gait commands rung 0
+  std::vector<int> n(B, 1), seq(B * (E + 1), HSQP_MODE_STANCE), scal(B * GAIT_SCAL, 0);
+  std::vector<double> ev(B * E, t0 + 0.5), tc(B, t0);
+  StickyError step{h};
+  step(hipMemcpyAsync(G.d_st, gs, sizeof(*gs), hipMemcpyHostToDevice, h->stream), "upload gait settings");
+  step(hipMemcpyAsync(G.s[0].n, n.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload gait n_events");
+  step(hipMemcpyAsync(G.s[0].ev, ev.data(), B * E * 8, hipMemcpyHostToDevice, h->stream), "upload gait event_times");
+  step(hipMemcpyAsync(G.s[0].seq, seq.data(), B * (E + 1) * 4, hipMemcpyHostToDevice, h->stream), "upload gait mode_sequence");
+  step(hipMemcpyAsync(G.s[0].scal, scal.data(), B * GAIT_SCAL * 4, hipMemcpyHostToDevice, h->stream), "upload gait rungs");
+  step(hipMemcpyAsync(G.s[0].t_change, tc.data(), B * 8, hipMemcpyHostToDevice, h->stream), "upload gait change times");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  G.st = *gs; G.B = batch; G.cur = 0;
+  G.ready = true;
+  return HSQP_OK;
+}
+
+int hsqp_gait_reset(hsqp_handle* h, const hsqp_gait_settings* settings, int batch, double t0) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (h->loop.started && h->loop.gait) h->loop.started = false;
+  return gait_reset_impl(h, "hsqp_gait_reset", settings, batch, t0);
+}
+
+// queues k_gait_update on the handle's stream (device arrays), reads the B status words; the copies are NOT swapped here
+static int gait_launch_and_check(hsqp_handle* h, const char* who, int batch, double t, double horizon, const double* d_v, const double* d_x, int* d_ne, double* d_ev,
+                                 int* d_seq) {
+  hsqp_handle::Gait& G = h->gait;
+  StickyError step{h};
+  HSQP_LAUNCH(k_gait_update, dim3(batch), dim3(64), 0, h->stream, G.d_st, G.s[G.cur], G.s[G.cur ^ 1], t, horizon, d_v, d_x, d_ne, d_ev, d_seq, G.status);
+  step(hipGetLastError(), "k_gait_update");
+  std::vector<int> status(batch);
+  step(hipMemcpyAsync(status.data(), G.status, (size_t)batch * 4, hipMemcpyDeviceToHost, h->stream), "download gait status");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  for (int b = 0; b < batch; ++b)
+    if (status[b] != HSQP_GAIT_OK) {
+      h->err = std::string(who) + ": gait update of instance " + std::to_string(b) +
+               (status[b] == HSQP_GAIT_OVERFLOW ? ": the schedule would exceed max_events" : ": the template tiling would not start behind the last event of the schedule") +
+               " (the gait state is unchanged)";
+      return HSQP_ERR_BAD_ARG;
+    }
+  return HSQP_OK;
+}
+
+static int gait_update_impl(hsqp_handle* h, int batch, double t, double horizon, const double* v, const double* x, int32_t* ne, double* ev, int32_t* seq, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_gait_update_device" : "hsqp_gait_update";
+  { const int rc = gait_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Gait& G = h->gait;
+  if (!G.ready) return loop_bad(h, who, "no gait state (hsqp_gait_reset)");
+  if (h->loop.started && h->loop.gait) h->loop.started = false;   // the state is the caller's again
+  if (batch != G.B) return loop_bad(h, who, "the batch differs from the one of hsqp_gait_reset");
+  if (!v || !x || !ne || !ev || !seq) return loop_bad(h, who, "null array");
+  if (!std::isfinite(t) || !std::isfinite(horizon) || !(horizon > 0.0)) return loop_bad(h, who, "t not finite, or horizon not finite and > 0");
+  const size_t B = batch, E = G.st.max_events;
+  HCHECK(hipSetDevice(h->device));
+  int rc;
+  if (dev) {
+    rc = gait_launch_and_check(h, who, batch, t, horizon, v, x, ne, ev, seq);
+  } else {
+    StickyError step{h};
+    step(hipMemcpyAsync(G.v, v, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_filt");
+    step(hipMemcpyAsync(G.x, x, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
+    if (step.rc != HSQP_OK) return step.rc;
+    rc = gait_launch_and_check(h, who, batch, t, horizon, G.v, G.x, G.ne, G.ev, G.seq);
+    const std::string err = h->err;
+    step(hipMemcpyAsync(ne, G.ne, B * 4, hipMemcpyDeviceToHost, h->stream), "download n_events");
+    step(hipMemcpyAsync(ev, G.ev, B * E * 8, hipMemcpyDeviceToHost, h->stream), "download event_times");
+    step(hipMemcpyAsync(seq, G.seq, B * (E + 1) * 4, hipMemcpyDeviceToHost, h->stream), "download mode_sequence");
+    step(hipStreamSynchronize(h->stream), "sync");
+    if (rc != HSQP_OK) h->err = err; else rc = step.rc;
+  }
+  if (rc == HSQP_OK) G.cur ^= 1;
+  return rc;
+}
+
+int hsqp_gait_update(hsqp_handle* h, int batch, double t, double horizon, const double* v_filt, const double* x, int32_t* n_events, double* event_times,
+                     int32_t* mode_sequence) {
+  return gait_update_impl(h, batch, t, horizon, v_filt, x, n_events, event_times, mode_sequence, false);
+}
+int hsqp_gait_update_device(hsqp_handle* h, int batch, double t, double horizon, const double* d_v_filt, const double* d_x, int32_t* d_n_events,
+                            double* d_event_times, int32_t* d_mode_sequence) {
+  return gait_update_impl(h, batch, t, horizon, d_v_filt, d_x, d_n_events, d_event_times, d_mode_sequence, true);
+}
+
+static int gait_state_impl(hsqp_handle* h, int32_t* rung, double* t_change, int32_t* ne, double* ev, int32_t* seq, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_gait_state_device" : "hsqp_gait_state";
+  { const int rc = gait_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Gait& G = h->gait;
+  if (!G.ready) return loop_bad(h, who, "no gait state (hsqp_gait_reset)");
+  HCHECK(hipSetDevice(h->device));
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t B = G.B, E = G.st.max_events;
+  const GaitState& s = G.s[G.cur];
+  if (rung) HCHECK(hipMemcpy2DAsync(rung, 4, s.scal, GAIT_SCAL * 4, 4, B, kind, h->stream));   // column 0 of the [B][GAIT_SCAL] scalars
+  if (t_change) HCHECK(hipMemcpyAsync(t_change, s.t_change, B * 8, kind, h->stream));
+  if (ne) HCHECK(hipMemcpyAsync(ne, s.n, B * 4, kind, h->stream));
+  if (ev) HCHECK(hipMemcpyAsync(ev, s.ev, B * E * 8, kind, h->stream));
+  if (seq) HCHECK(hipMemcpyAsync(seq, s.seq, B * (E + 1) * 4, kind, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_gait_state(hsqp_handle* h, int32_t* rung, double* last_change_time, int32_t* n_events, double* event_times, int32_t* mode_sequence) {
+  return gait_state_impl(h, rung, last_change_time, n_events, event_times, mode_sequence, false);
+}
+int hsqp_gait_state_device(hsqp_handle* h, int32_t* d_rung, double* d_last_change_time, int32_t* d_n_events, double* d_event_times, int32_t* d_mode_sequence) {
+  return gait_state_impl(h, d_rung, d_last_change_time, d_n_events, d_event_times, d_mode_sequence, true);
+}
+
+int hsqp_loop_start_gait(hsqp_handle* h, const hsqp_loop_settings* settings, const hsqp_gait_settings* gait, int batch, double t0, const double* x0,
+                         const double* v_cmd) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (!gait) { h->loop.started = false; return loop_bad(h, "hsqp_loop_start_gait", "null gait settings"); }
+  return loop_start_impl(h, "hsqp_loop_start_gait", settings, gait, batch, t0, x0, v_cmd, gait->max_events, nullptr, nullptr, nullptr);
+}
+
 // One cycle from the resident buffers (include/hsqp_loop.h, steps 1 to 5).  d_xlog / d_ulog: this cycle's log rows (device) or null.  On a failure the
 // loop's own state (t, x, v_filt) is that of the last completed cycle: the filter state is advanced on a copy and committed with the state.
 static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
@@ -2460,6 +2690,12 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   step(hipMemcpyAsync(vf_next, L.v_filt, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream), "copy v_filt");
   launch_command_targets(h, L.B, L.v_cmd, vf_next, st.filter_alpha, L.x, L.t, st.n_nodes * st.dt, L.tt, L.ts);
   step(hipGetLastError(), "k_command_targets");
+  // the gait update between steps 1 and 2 (include/hsqp_gait.h): this cycle's schedule into ne / ev / seq; the shadow state becomes the live one with step 5
+  if (L.gait) {
+    if (step.rc != HSQP_OK) return step.rc;
+    const int rc = gait_launch_and_check(h, "hsqp_loop_run", L.B, L.t, st.n_nodes * st.dt, vf_next, L.x, L.ne, L.ev, L.seq);
+    if (rc != HSQP_OK) return rc;
+  }
   // 2. hsqp_upload_reference's work on the resident arrays
   h->have_problem = false; h->have_solution = false; h->have_stamps = false;
   { const int rc = set_grid(h, &p, false); if (rc != HSQP_OK) return rc; }
@@ -2476,6 +2712,7 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   HCHECK(hipMemcpyAsync(L.v_filt, vf_next, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream));
   if (d_xlog) HCHECK(hipMemcpyAsync(d_xlog, L.xs, B * NX * 8, hipMemcpyDeviceToDevice, h->stream));
   if (d_ulog) HCHECK(hipMemcpyAsync(d_ulog, L.us, B * NU * 8, hipMemcpyDeviceToDevice, h->stream));
+  if (L.gait) h->gait.cur ^= 1;
   L.t += st.period;
   L.have_cycle = true;
   return HSQP_OK;

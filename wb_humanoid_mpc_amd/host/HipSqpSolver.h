@@ -17,6 +17,7 @@
 #include "../../include/hsqp_feedback.h"
 #include "../../include/hsqp_rollout.h"
 #include "../../include/hsqp_loop.h"
+#include "../../include/hsqp_gait.h"
 
 namespace hsqp_host {
 
@@ -179,6 +180,18 @@ class HipSqpSolver {
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_start failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     loopBatch_ = B;
     shiftable_ = false;   // (the loop owns the resident problem until the next run* call ends it)
+  }
+  /** startLoop with the per-instance gait schedule and ladder resident on the device (include/hsqp_gait.h) in place of uploaded schedules: every
+   *  instance starts in stance at rung 0 and climbs / descends the ladder of `gait` from its filtered command and measured base velocity.  The
+   *  caller fills `gait` (hsqp_gait_ladder_defaults for thresholds and names, the templates of gait.info under the rungs). */
+  void startLoopGait(const hsqp_loop_settings& st, const hsqp_gait_settings& gait, double t0, const std::vector<double>& x0, const std::vector<double>& velocityCommands) {
+    const size_t B = velocityCommands.size() / HSQP_CMD_N;
+    loopBatch_ = 0;
+    if (B == 0 || x0.size() != B * HSQP_NX || velocityCommands.size() != B * HSQP_CMD_N) throw std::runtime_error("[HipSqpSolver] startLoopGait: inconsistent array sizes");
+    const int rc = hsqp_loop_start_gait(h_, &st, &gait, (int)B, t0, x0.data(), velocityCommands.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_start_gait failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    loopBatch_ = B;
+    shiftable_ = false;
   }
   /** New commands [batch][4]; in effect from the next cycle. */
   void setLoopCommand(const std::vector<double>& velocityCommands) {

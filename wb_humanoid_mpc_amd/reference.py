@@ -709,3 +709,192 @@ def linear_controller_input(times, uff, K, t, x):
     j = min(i + 1, n - 1)
     Ks = alpha * K[i] + (1.0 - alpha) * K[j]
     return alpha * uff[i] + (1.0 - alpha) * uff[j] + Ks @ x
+
+
+# ---- per-instance gait schedule and gait ladder (include/hsqp_gait.h): csrc/hsqp_gait.h restated for the tests, line by line from
+#      GaitSchedule.cpp:53-145, GaitScheduleUpdater.cpp:45-69 and ProceduralMpcMotionManager.cpp:86-159.  Python floats are IEEE doubles and
+#      nothing here is fused, so the mirror, the host build of the kernel source and the device agree bit for bit.
+GAIT_OK, GAIT_OVERFLOW, GAIT_BAD_TILING = 0, 1, 2
+# ProceduralMpcMotionManager.h:110-118: gaitCommand, minLinVelCmd, maxLinVelCmd, minAngVelCmd, maxAngVelCmd, linVelErrorThresh, angVelErrorThresh
+GAIT_LADDER = (("stance", -0.1, 0.1, -0.1, 0.1, 10.0, 10.0),      # "Large threshold allows switching away from stance purely command based"
+               ("slow_walk", 0.05, 0.3, 0.05, 0.2, 0.05, 0.05),
+               ("walk", 0.25, 0.5, 0.15, 0.35, 0.05, 0.05),
+               ("slower_trot", 0.45, 0.7, 0.3, 0.55, 0.1, 0.1),
+               ("slow_trot", 0.65, 0.9, 0.5, 0.7, 0.2, 0.2),
+               ("trot", 0.8, 1.3, 0.65, 10.0, 0.2, 0.2),
+               ("run", 1.2, 10.0, 0.65, 10.0, 0.2, 0.2))
+
+
+class GaitTilingError(RuntimeError):
+    """'The initial time for template-tiling is not greater than the last event time.' (GaitSchedule.cpp:127-129)"""
+
+
+class GaitOverflow(RuntimeError):
+    """the schedule would exceed max_events (a limit of the device form, not of the reference)"""
+
+
+class GaitSchedule:
+    """GaitSchedule.cpp.  template: (switching_times, modes) with modes as numbers; max_events: None (the reference) or the device's capacity."""
+
+    def __init__(self, event_times, mode_sequence, template, phase_transition_stance_time=0.0, max_events=None):
+        self.event_times, self.mode_sequence = list(event_times), list(mode_sequence)
+        self.template = (list(template[0]), list(template[1]))
+        self.phase_transition_stance_time = phase_transition_stance_time
+        self.max_events = max_events
+
+    def _push_event(self, t):
+        if self.max_events is not None and len(self.event_times) >= self.max_events:
+            raise GaitOverflow()
+        self.event_times.append(t)
+
+    def _push_mode(self, m):
+        if self.max_events is not None and len(self.mode_sequence) > self.max_events:
+            raise GaitOverflow()
+        self.mode_sequence.append(m)
+
+    def tile(self, start, final):
+        """tileModeSequenceTemplate (GaitSchedule.cpp:115-145)"""
+        times, modes = self.template
+        if not modes:
+            return
+        if self.event_times and start <= self.event_times[-1]:
+            raise GaitTilingError()
+        self._push_event(start)
+        while self.event_times[-1] < final:
+            for i, m in enumerate(modes):
+                self._push_mode(m)
+                self._push_event(self.event_times[-1] + (times[i + 1] - times[i]))
+        self._push_mode(STANCE)
+
+    def insert_template(self, template, start, final):
+        """insertModeSequenceTemplate (GaitSchedule.cpp:53-80)"""
+        self.template = (list(template[0]), list(template[1]))
+        ev, seq = self.event_times, self.mode_sequence
+        index = bisect.bisect_left(ev, start)
+        if index < len(ev):
+            del ev[index:]
+            del seq[index + 1:]
+        pts = self.phase_transition_stance_time
+        if seq and seq[-1] == STANCE:
+            pts = 0.0
+        if pts > 0.0:
+            self._push_event(start)
+            self._push_mode(STANCE)
+        self.tile(start + pts, final)
+
+    def get_mode_schedule(self, lower, upper):
+        """getModeSchedule (GaitSchedule.cpp:85-110): trims and re-tiles the resident schedule, returns copies of (event_times, mode_sequence)"""
+        ev, seq = self.event_times, self.mode_sequence
+        index = bisect.bisect_left(ev, lower)
+        if index > 0:
+            del ev[:index - 1]
+            del seq[:index - 1]
+            seq[0] = STANCE
+        if not ev:
+            raise GaitTilingError()      # (the reference erases end() - 1 of an empty vector)
+        tiling_start = ev[-1]
+        del ev[-1:]
+        del seq[-1:]
+        self.tile(tiling_start, upper)
+        return list(ev), list(seq)
+
+
+def update_gait_schedule(gs, template, init_time, final_time):
+    """GaitScheduleUpdater::updateGaitSchedule (GaitScheduleUpdater.cpp:45-69)"""
+    horizon = final_time - init_time
+    earliest = 0.7 * final_time + 0.3 * init_time
+    ev, seq = gs.get_mode_schedule(init_time, final_time + horizon)
+    it = bisect.bisect_right(ev, earliest)
+    if it == len(ev):
+        nxt = final_time
+    elif seq[bisect.bisect_left(ev, ev[it])] == LF:       # modeSchedule.modeAtTime(*it)
+        if it == 0:
+            raise GaitTilingError()                        # (*(it - 1) of begin(): not reachable, the front mode of a trimmed schedule is STANCE)
+        nxt = ev[it - 1]
+    else:
+        nxt = ev[it]
+    gs.insert_template(template, nxt, 1.5 * horizon)      # a duration where a time is expected: kept
+
+
+def transition_to_faster_gait(cmd, base_vel, cfg):
+    """cfg: a row of GAIT_LADDER (or of gait_settings' rungs) without its name: (minLin, maxLin, minAng, maxAng, linThresh, angThresh)"""
+    _, max_lin, _, max_ang, lin_thr, ang_thr = cfg
+    requested = abs(cmd[0]) > max_lin or abs(cmd[1]) > max_lin or abs(cmd[3]) > max_ang
+    within = abs(base_vel[0]) > max_lin - lin_thr or abs(base_vel[1]) > max_lin - lin_thr or abs(base_vel[3]) > max_ang - ang_thr
+    return requested and within
+
+
+def transition_to_slower_gait(cmd, base_vel, cfg):
+    min_lin, _, min_ang, _, lin_thr, ang_thr = cfg
+    requested = abs(cmd[0]) < min_lin and abs(cmd[1]) < min_lin and abs(cmd[3]) < min_ang
+    # the third clause tests velCommandVec(3), not baseVelocity(3) (ProceduralMpcMotionManager.cpp:110): kept
+    slow_enough = abs(base_vel[0]) < min_lin + lin_thr and abs(base_vel[1]) < min_lin + lin_thr and abs(cmd[3]) < min_ang + ang_thr
+    return requested and slow_enough
+
+
+def gait_settings(model, ladder=GAIT_LADDER, phase_transition_stance_time=None, min_change_interval=0.2, max_events=128):
+    """_abi.GaitSettings: the ladder's thresholds and names with the templates of model.gaits (gait.info) under the rungs' names;
+    phase_transition_stance_time None: the exported task.info value."""
+    s = _abi.GaitSettings()
+    s.n_rungs, s.max_events, s.min_change_interval = len(ladder), int(max_events), float(min_change_interval)
+    s.phase_transition_stance_time = float(model.raw["phase_transition_stance_time"] if phase_transition_stance_time is None else phase_transition_stance_time)
+    for r, row in enumerate(ladder):
+        c, g = s.rungs[r], model.gaits[row[0]]
+        (c.min_lin_vel_cmd, c.max_lin_vel_cmd, c.min_ang_vel_cmd, c.max_ang_vel_cmd, c.lin_vel_error_thresh, c.ang_vel_error_thresh) = [float(v) for v in row[1:]]
+        c.name = row[0].encode()[:_abi.GAIT_NAME_LEN - 1]
+        c.n_phases = len(g["modeSequence"])
+        for i, t in enumerate(g["switchingTimes"]):
+            c.switching_times[i] = float(t)
+        for i, m in enumerate(g["modeSequence"]):
+            c.modes[i] = MODE_BY_NAME[m]
+    return s
+
+
+class GaitInstance:
+    """The state of one instance after hsqp_gait_reset(settings, t0)."""
+
+    def __init__(self, settings, t0=0.0):
+        self.settings = settings
+        self.rung = self.command = self.last_command = 0
+        self.last_change_time = t0
+        self.schedule = GaitSchedule([t0 + 0.5], [STANCE, STANCE], self.template_of(0), settings.phase_transition_stance_time, settings.max_events)
+
+    def template_of(self, r):
+        c = self.settings.rungs[r]
+        return list(c.switching_times[:c.n_phases + 1]), list(c.modes[:c.n_phases])
+
+    def thresholds_of(self, r):
+        c = self.settings.rungs[r]
+        return (c.min_lin_vel_cmd, c.max_lin_vel_cmd, c.min_ang_vel_cmd, c.max_ang_vel_cmd, c.lin_vel_error_thresh, c.ang_vel_error_thresh)
+
+
+def gait_cycle(state, t, horizon, v, x):
+    """One update (include/hsqp_gait.h steps 1 to 3) of a GaitInstance at time t with the filtered command v [4] and the measured state x [58]:
+    (status, event_times, mode_sequence) of this cycle's schedule.  All or nothing, like the device: a status other than GAIT_OK leaves `state`
+    as it was (the schedule of step 1 is still returned where step 1 succeeded)."""
+    import copy
+    nj = _abi.NJ
+    final_time = t + horizon
+    th = final_time - t
+    s = copy.copy(state)
+    s.schedule = copy.deepcopy(state.schedule)
+    ev = seq = None
+    try:
+        ev, seq = s.schedule.get_mode_schedule(t - th, final_time + th)                       # 1. SwitchedModelReferenceManager::modifyReferences
+        base_vel = [float(a) for a in x[6 + nj:12 + nj]]                                       # WBAccelMpcRobotModel::getBaseComVelocity
+        if t > s.last_change_time + s.settings.min_change_interval:                            # 2. ProceduralMpcMotionManager.cpp:134-152
+            cfg = s.thresholds_of(s.rung)
+            step = 1 if transition_to_faster_gait(v, base_vel, cfg) else -1 if transition_to_slower_gait(v, base_vel, cfg) else 0
+            if step:
+                s.rung = min(max(s.rung + step, 0), s.settings.n_rungs - 1)                    # (the clamp is not in the reference)
+                s.command = s.rung
+                s.last_change_time = t
+        if s.command != s.last_command:                                                        # 3. ProceduralMpcMotionManager.cpp:154-159
+            update_gait_schedule(s.schedule, s.template_of(s.command), t, final_time)
+            s.last_command = s.command
+    except GaitOverflow:
+        return GAIT_OVERFLOW, ev, seq
+    except GaitTilingError:
+        return GAIT_BAD_TILING, ev, seq
+    state.__dict__.update(s.__dict__)
+    return GAIT_OK, ev, seq

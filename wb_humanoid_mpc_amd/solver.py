@@ -110,6 +110,16 @@ def load_library():
     lib.hsqp_loop_run_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int)]
     lib.hsqp_loop_state.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.hsqp_loop_state_device.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    # include/hsqp_gait.h
+    _gs = C.POINTER(_abi.GaitSettings)
+    lib.hsqp_gait_ladder_defaults.argtypes = [_gs]
+    lib.hsqp_gait_ladder_defaults.restype = None
+    lib.hsqp_gait_reset.argtypes = [C.c_void_p, _gs, C.c_int, C.c_double]
+    lib.hsqp_gait_update.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, _dp, _dp, _ip, _dp, _ip]
+    lib.hsqp_gait_update_device.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, _dp, _dp, _ip, _dp, _ip]
+    lib.hsqp_gait_state.argtypes = [C.c_void_p, _ip, _dp, _ip, _dp, _ip]
+    lib.hsqp_gait_state_device.argtypes = [C.c_void_p, _ip, _dp, _ip, _dp, _ip]
+    lib.hsqp_loop_start_gait.argtypes = [C.c_void_p, _ls, _gs, C.c_int, C.c_double, _dp, _dp]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -516,12 +526,24 @@ class HipSqpSolver:
         st.terrain_height, st.arm_swing = float(terrain_height), 1 if arm_swing else 0
         return st
 
-    def loop_start(self, settings, t0, x0, v_cmd, n_events, event_times, mode_sequence):
+    def loop_start(self, settings, t0, x0, v_cmd, n_events=None, event_times=None, mode_sequence=None, gait=None):
         """hsqp_loop_start: B = len(x0) instances, their commands [B][4] and mode schedules (reference.pack_reference's first three arrays),
-        uploaded once."""
+        uploaded once.  gait (an _abi.GaitSettings, reference.gait_settings) instead of the schedules: hsqp_loop_start_gait, the resident
+        gait schedule and ladder of include/hsqp_gait.h own the schedule."""
         x0 = _c(np.atleast_2d(x0))
         B = x0.shape[0]
         v_cmd = _c(np.broadcast_to(v_cmd, (B, _abi.CMD_N)))
+        if gait is not None:
+            if n_events is not None or event_times is not None or mode_sequence is not None:
+                raise ValueError("either mode schedules or gait settings")
+            if x0.shape != (B, _abi.NX):
+                raise ValueError("inconsistent loop array shapes")
+            self._loop_batch = 0
+            self._check(self.lib.hsqp_loop_start_gait(self.h, C.byref(settings), C.byref(gait), B, C.c_double(t0), x0.ctypes.data_as(_dp), v_cmd.ctypes.data_as(_dp)))
+            self._loop_batch = self._gait_batch = B
+            self._gait_events = int(gait.max_events)
+            self._shape = (B, int(settings.n_nodes))
+            return
         n_events = np.ascontiguousarray(n_events, dtype=np.int32)
         mode_sequence = np.ascontiguousarray(mode_sequence, dtype=np.int32)
         event_times = _c(event_times)
@@ -577,6 +599,55 @@ class HipSqpSolver:
         t = C.c_double(0.0)
         self._check(self.lib.hsqp_loop_state_device(self.h, C.byref(t), cast(x_ptr), cast(v_filt_ptr)))
         return t.value
+
+    # ---- include/hsqp_gait.h: per-instance gait schedule and ladder
+    def gait_reset(self, settings, batch, t0=0.0):
+        """hsqp_gait_reset: `batch` instances in the initial state ({[t0 + 0.5], [STANCE, STANCE]}, rung 0) under `settings` (reference.gait_settings)."""
+        self._gait_batch = 0
+        self._check(self.lib.hsqp_gait_reset(self.h, C.byref(settings), int(batch), C.c_double(t0)))
+        self._gait_batch, self._gait_events = int(batch), int(settings.max_events)
+
+    def _gait_arrays(self):
+        B, E = max(getattr(self, "_gait_batch", 0), 1), max(getattr(self, "_gait_events", 0), 1)
+        return np.zeros(B, np.int32), np.zeros((B, E)), np.zeros((B, E + 1), np.int32)
+
+    def gait_update(self, t, horizon, v_filt, x):
+        """hsqp_gait_update: one update of every instance at time t from the filtered commands [B][4] and the measured states [B][58]:
+        (n_events[B], event_times[B, E], mode_sequence[B, E + 1]) of this cycle, the layout upload_reference takes.  A failed update raises
+        HsqpError (the state is unchanged) with those arrays as its `result` attribute."""
+        ne, ev, seq = self._gait_arrays()
+        B = ne.shape[0]
+        v_filt, x = _c(np.broadcast_to(v_filt, (B, _abi.CMD_N))), _c(np.broadcast_to(x, (B, _abi.NX)))
+        ip = C.POINTER(C.c_int32)
+        rc = self.lib.hsqp_gait_update(self.h, B, C.c_double(t), C.c_double(horizon), v_filt.ctypes.data_as(_dp), x.ctypes.data_as(_dp), ne.ctypes.data_as(ip),
+                                       ev.ctypes.data_as(_dp), seq.ctypes.data_as(ip))
+        if rc != 0:
+            err = HsqpError(rc, self.lib.hsqp_last_error(self.h).decode())
+            err.result = (ne, ev, seq)
+            raise err
+        return ne, ev, seq
+
+    def gait_update_device(self, batch, t, horizon, v_filt_ptr, x_ptr, n_events_ptr, event_times_ptr, mode_sequence_ptr):
+        """hsqp_gait_update_device: the same with every array in device memory (addresses)."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp)  # noqa: E731
+        icast = lambda a: C.cast(C.c_void_p(int(a)), C.POINTER(C.c_int32))  # noqa: E731
+        self._check(self.lib.hsqp_gait_update_device(self.h, int(batch), C.c_double(t), C.c_double(horizon), cast(v_filt_ptr), cast(x_ptr), icast(n_events_ptr),
+                                                     cast(event_times_ptr), icast(mode_sequence_ptr)))
+
+    def gait_state(self):
+        """hsqp_gait_state: dict(rung[B], last_change_time[B], n_events[B], event_times[B, E], mode_sequence[B, E + 1]) of the resident state
+        (a gait loop's: that of its last completed cycle)."""
+        ne, ev, seq = self._gait_arrays()
+        rung, tc = np.zeros_like(ne), np.zeros(ne.shape[0])
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.hsqp_gait_state(self.h, rung.ctypes.data_as(ip), tc.ctypes.data_as(_dp), ne.ctypes.data_as(ip), ev.ctypes.data_as(_dp), seq.ctypes.data_as(ip)))
+        return dict(rung=rung, last_change_time=tc, n_events=ne, event_times=ev, mode_sequence=seq)
+
+    def gait_state_device(self, rung_ptr=0, last_change_time_ptr=0, n_events_ptr=0, event_times_ptr=0, mode_sequence_ptr=0):
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        icast = lambda a: C.cast(C.c_void_p(int(a)), C.POINTER(C.c_int32)) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_gait_state_device(self.h, icast(rung_ptr), cast(last_change_time_ptr), icast(n_events_ptr), cast(event_times_ptr),
+                                                    icast(mode_sequence_ptr)))
 
     def joint_torques(self, x, u):
         x, u = _c(np.atleast_2d(x)), _c(np.atleast_2d(u))
