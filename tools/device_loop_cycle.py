@@ -7,11 +7,13 @@ reports one hsqp_loop_run(cycles) call per cycle (`run_ms_per_cycle`), which is 
 Prints one JSON line with the fields of tools/closed_loop_cycle.py (no rollout share and no step counts: the loop does not stop between the
 iteration and the rollout, and its rollout keeps no step counters).
     python tools/device_loop_cycle.py [--cycles 30] [--warmup 3] [--batch 256] [--nodes 100] [--controller feedforward|feedback]
-                                      [--commands same|spread] [--gait ladder|walk]
+                                      [--commands same|spread] [--gait ladder|walk] [--isolate park|reset]
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
 reports the rungs at the end; walk: --commands from the start (feet lift about one second in: choose --warmup 120 to time walking cycles).
+--isolate: hsqp_loop_isolate (include/hsqp_episode.h) behind the start, with the bounds off: every cycle also runs the triage (and, with --gait, the
+per-instance gait reset); the line reports the episode counters at the end.
 --commands same: every instance is commanded (0.3, 0, 0.7925, 0), the other tool's command; spread: vx from 0 to 0.6 m/s and yaw rates from
 -0.2 to 0.2 rad/s across the batch.
 """
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--commands", default="same", choices=("same", "spread"))
     ap.add_argument("--filter-alpha", type=float, default=0.8)
     ap.add_argument("--gait", default=None, choices=("ladder", "walk"))
+    ap.add_argument("--isolate", default=None, choices=("park", "reset"))
     args = ap.parse_args()
     m = load_model()
     B, N, dt = args.batch, args.nodes, m.sqp["dt"]
@@ -74,6 +77,8 @@ def main():
             s.loop_start(st, 0.0, x_init, cmd, gait=gait_settings(m))
         else:
             s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
+        if args.isolate:
+            s.loop_isolate(s.episode_settings(args.isolate))
         for c in range(args.warmup + args.cycles):
             if c in changes:
                 s.loop_command(changes[c])
@@ -88,13 +93,15 @@ def main():
         run_ms = 1e3 * (time.perf_counter() - t_a) / args.cycles
         t_end, x_end, v_filt = s.loop_state()
         rungs = np.bincount(s.gait_state()["rung"], minlength=7).tolist() if args.gait else None
+        ep = s.loop_episodes() if args.isolate else None
         heights.append(x_end[:, 2].copy())
     finally:
         s.close()
     heights = np.concatenate(heights)
     q = np.percentile(cycle_ms, [25, 75])
     print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
-                      "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs,
+                      "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate,
+                      "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),
                       "run_ms_per_cycle": round(float(run_ms), 3), "t_end": round(float(t_end), 6),

@@ -147,6 +147,18 @@ class GaitSettings(C.Structure):   # hsqp_gait_settings
 GAIT_ENTRY_POINTS = ("hsqp_gait_ladder_defaults", "hsqp_gait_reset", "hsqp_gait_update", "hsqp_gait_update_device", "hsqp_gait_state", "hsqp_gait_state_device",
                      "hsqp_loop_start_gait")
 
+# include/hsqp_episode.h
+EPISODE_PARK, EPISODE_RESET = 0, 1
+EP_ALIVE, EP_FAILED_NUMERIC, EP_FAILED_ROLLOUT, EP_FAILED_BOUNDS = 0, 1, 2, 3
+
+
+class EpisodeSettings(C.Structure):   # hsqp_episode_settings
+    _fields_ = [("on_failure", C.c_int32), ("reserved", C.c_int32), ("min_base_height", C.c_double), ("max_base_height", C.c_double), ("max_tilt", C.c_double)]
+
+
+# entry points of include/hsqp_episode.h (tests/test_episode.py checks that the library exports each of them and the binding declares it)
+EPISODE_ENTRY_POINTS = ("hsqp_episode_defaults", "hsqp_loop_isolate", "hsqp_loop_reset_instances", "hsqp_loop_episodes", "hsqp_loop_episodes_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

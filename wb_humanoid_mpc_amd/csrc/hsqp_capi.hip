@@ -22,6 +22,7 @@
 #include "hsqp_loop.h"
 #include "../../include/hsqp_loop.h"
 #include "hsqp_gait.h"
+#include "hsqp_episode.h"
 #include "hsqp_warm.h"
 #include "hsqp_cent.h"
 #include "hsqp_cent_lq.h"
@@ -814,13 +815,31 @@ __global__ __launch_bounds__(64) void k_gait_update(const hsqp_gait_settings* __
   if (threadIdx.x == 0) status[b] = st;
 }
 
+// ---- failure isolation and episode reset of the resident loop (hsqp_episode.h): one wave per instance
+__global__ __launch_bounds__(64) void k_loop_triage(TriageArgs a) { triage_instance(Ctx{(int)threadIdx.x, 64, nullptr}, a, blockIdx.x); }
+// entry blockIdx.x of a hsqp_loop_reset_instances request
+__global__ __launch_bounds__(64) void k_episode_host_reset(HostResetArgs a) { host_reset_instance(Ctx{(int)threadIdx.x, 64, nullptr}, a, blockIdx.x); }
+// the command in use of every instance from its state (behind hsqp_loop_isolate and hsqp_loop_command): one thread per entry
+__global__ __launch_bounds__(64) void k_episode_commands(const int* __restrict__ state, const double* __restrict__ v_cmd, const double* __restrict__ x_reset, int B,
+                                                         double* __restrict__ v_use) {
+  const int id = blockIdx.x * 64 + threadIdx.x, b = id / CMD_N, i = id % CMD_N;
+  if (b < B) v_use[id] = episode_command_entry(state[b], v_cmd + (size_t)b * CMD_N, x_reset + (size_t)b * NX, i);
+}
+// the per-instance gait reset at time t.  ids == null: workgroup b serves instance b if flags[b] is set (behind the triage); otherwise workgroup i
+// serves instance ids[i] (hsqp_loop_reset_instances)
+__global__ __launch_bounds__(64) void k_gait_reset_instances(GaitState s, int E, const int* __restrict__ ids, const int* __restrict__ flags, double t) {
+  const int b = ids ? ids[blockIdx.x] : (int)blockIdx.x;
+  if (!ids && !flags[b]) return;
+  gait_reset_instance(Ctx{(int)threadIdx.x, 64, nullptr}, s, E, b, t);
+}
+
 // ---- receding-horizon warm start (hsqp_warm.h) behind k_params: one wave per node of the new grid, WARM_WAVES nodes per workgroup
 // (blockIdx.x), one instance per blockIdx.y; the instance's previous stamps are staged in LDS once per workgroup (SHIFT)
 constexpr int WARM_WAVES = 4;
 __global__ __launch_bounds__(64 * WARM_WAVES) void k_warm_start(WarmArgs w) {
   double* tp = reinterpret_cast<double*>(hsqp_smem);
   const int b = blockIdx.y, k = blockIdx.x * WARM_WAVES + wave_index(threadIdx.x);
-  if (w.mode == HSQP_WARM_SHIFT) {
+  if (warm_mode(w, b) == HSQP_WARM_SHIFT) {   // (uniform: a workgroup serves one instance)
     const double* src = w.stamps_prev + (size_t)b * (w.N_prev + 1);
     for (int i = threadIdx.x; i <= w.N_prev; i += blockDim.x) tp[i] = src[i];
     __syncthreads();
@@ -1109,6 +1128,12 @@ struct hsqp_handle {
     double* ev = nullptr; double* tt = nullptr; double* ts = nullptr; double* s0 = nullptr;
     double* v_cmd = nullptr; double* v_filt = nullptr; double* x = nullptr; double* xs = nullptr; double* us = nullptr;
     bool gait = false;                          // started through hsqp_loop_start_gait: ne / seq / ev are written by k_gait_update in every cycle
+    int cycle = 0;                              // cycles completed since hsqp_loop_start
+    // failure isolation (include/hsqp_episode.h): off after every start; the episode arrays, x_reset [B][58] and the command in use [B][4], carved from d_episode
+    bool isolate = false;
+    hsqp_episode_settings ep_st;
+    EpisodeState ep = {};
+    double* x_reset = nullptr; double* v_use = nullptr;
   } loop;
   // the resident gait state (include/hsqp_gait.h): two copies carved from d_gait, s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
   struct Gait {
@@ -1120,7 +1145,7 @@ struct hsqp_handle {
     int* status = nullptr; int* ne = nullptr; int* seq = nullptr;
     double* ev = nullptr; double* v = nullptr; double* x = nullptr;
   } gait;
-  DevBuf<char> d_gait;
+  DevBuf<char> d_gait, d_episode;
   DevBuf<char> d_loop, d_loop_log;   // the loop's resident arrays; staging of hsqp_loop_run's host logs and of hsqp_command_targets' host arrays
   double kernel_ms[5] = {0, 0, 0, 0, 0};
   int last_iterations = 0;
@@ -1528,14 +1553,17 @@ static int check_status(hsqp_handle* h, const std::vector<int>& status) {
   return HSQP_OK;
 }
 
-// HSQP_WARM_SHIFT's preconditions, checked before anything is copied: a rejected call leaves the resident solution as it was
-static int warm_shift_ready(hsqp_handle* h, int batch, bool sorted) {
+// HSQP_WARM_SHIFT's preconditions, checked before anything is copied: a rejected call leaves the resident solution as it was.
+// per_instance (the isolated loop): the refusal after a numeric failure is the instance's — the triage has marked it HSQP_WARM_COLD on the device
+// (RefDev::warm_b), so the status words are not read here
+static int warm_shift_ready(hsqp_handle* h, int batch, bool sorted, bool per_instance = false) {
   if (!h->have_solution || !h->have_stamps) {
     h->err = "warm_start SHIFT: no resident solution of a problem uploaded through hsqp_upload_reference";
     return HSQP_ERR_BAD_ARG;
   }
   if (h->B != batch) { h->err = "warm_start SHIFT: the batch differs from the resident solution's"; return HSQP_ERR_BAD_ARG; }
   if (!sorted) { h->err = "warm_start SHIFT: node_times must not decrease"; return HSQP_ERR_BAD_ARG; }
+  if (per_instance) return HSQP_OK;
   std::vector<int> status(h->B);
   HCHECK(hipMemcpy(status.data(), h->d_status, status.size() * sizeof(int), hipMemcpyDeviceToHost));
   return check_status(h, status);
@@ -1551,6 +1579,7 @@ struct RefDev {
   double t0, dt;
   hsqp_swing_config swing; double terrain_height; int arm_swing, warm, N_prev;
   bool sorted;
+  const int* warm_b = nullptr;     // [B] HSQP_WARM_SHIFT / _COLD per instance (the isolated loop; `warm` is then SHIFT), or null: `warm` for all
 };
 
 // The device side of hsqp_upload_reference, behind the copies `step` has queued on the stream (x_init in d_xinit, the grid in d_dt, the CALLER warm start
@@ -1567,7 +1596,7 @@ static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& 
   }
   if (step.rc == HSQP_OK) {   // the grid's raw stamps (every mode) and the device-built warm start (SHIFT / COLD), after k_params wrote the contact flags
     WarmArgs w{};
-    w.mode = r.warm; w.B = (int)B; w.N = (int)N; w.N_prev = r.warm == HSQP_WARM_SHIFT ? r.N_prev : 0; w.cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
+    w.mode = r.warm; w.mode_b = r.warm_b; w.B = (int)B; w.N = (int)N; w.N_prev = r.warm == HSQP_WARM_SHIFT ? r.N_prev : 0; w.cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
     w.t0 = r.t0; w.dt = r.dt; w.total_mass = h->hdm.total_mass;
     w.node_times = r.nt; w.dts = h->d_dt; w.par = h->d_par; w.x_init = h->d_xinit;
     w.x_prev = h->d_xnew; w.u_prev = h->d_unew; w.stamps_prev = h->d_stamps[h->stamps_cur];
@@ -2216,8 +2245,10 @@ static const char* rollout_settings_error(const hsqp_rollout_settings& st) {
 }
 
 // dev: every array argument is device memory of the handle's GPU
+// per_instance (the isolated loop, include/hsqp_episode.h): an instance's status word — of the iteration, of the integration — is the instance's
+// alone: it is written to `status`, not turned into the call's return code
 static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const double* s0, const double* x0, double duration, int n, double* x, double* u,
-                        int32_t* status, int32_t* steps, int32_t* rejected, bool dev) {
+                        int32_t* status, int32_t* steps, int32_t* rejected, bool dev, bool per_instance = false) {
   if (!h) return HSQP_ERR_BAD_ARG;
   const char* who = dev ? "hsqp_rollout_policy_device" : "hsqp_rollout_policy";
   const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
@@ -2225,7 +2256,8 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
   if (const char* what = rollout_settings_error(*st)) return bad(what);
   if (!(duration >= 0.0) || !std::isfinite(duration)) return bad("duration < 0 or not finite");
   if (n < 1) return bad("n_samples < 1");
-  { const int rc = feedback_ready(h, who); if (rc != HSQP_OK) return rc; }
+  if (per_instance) { if (!h->have_policy) return bad("no feedback policy (no successful iteration since the last upload)"); }
+  else { const int rc = feedback_ready(h, who); if (rc != HSQP_OK) return rc; }
   const size_t B = h->B, nn = (size_t)n;
   const int N = h->N;
   const bool cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL, feedback = st->controller == HSQP_ROLLOUT_FEEDBACK;
@@ -2285,6 +2317,7 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
   step(hipStreamSynchronize(h->stream), "sync");
   if (step.rc != HSQP_OK) return step.rc;
   if (!dev) memcpy(status, hs.data(), B * 4);
+  if (per_instance) return HSQP_OK;
   int nonfinite = -1, capped = -1;
   for (size_t b = 0; b < B; ++b) {
     if (hs[b] == HSQP_ROLLOUT_NONFINITE && nonfinite < 0) nonfinite = (int)b;
@@ -2448,6 +2481,8 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
   if (step.rc != HSQP_OK) return step.rc;
   L.st = *st; L.B = batch; L.E = max_events; L.t = t0;
   L.have_cycle = false;
+  L.cycle = 0;
+  L.isolate = false;
   L.gait = gait != nullptr;
   L.started = true;
   return HSQP_OK;
@@ -2472,6 +2507,10 @@ static int loop_command_impl(hsqp_handle* h, const double* v_cmd, bool dev) {
   if (!dev && !all_finite(v_cmd, n)) return loop_bad(h, who, "non-finite command");
   HCHECK(hipSetDevice(h->device));
   HCHECK(hipMemcpyAsync(h->loop.v_cmd, v_cmd, n * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+  if (h->loop.isolate) {   // the command in use: a parked instance keeps the stance command
+    HSQP_LAUNCH(k_episode_commands, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->loop.ep.state, h->loop.v_cmd, h->loop.x_reset, h->loop.B, h->loop.v_use);
+    HCHECK(hipGetLastError());
+  }
   HCHECK(hipStreamSynchronize(h->stream));
   return HSQP_OK;
 }
@@ -2673,22 +2712,24 @@ int hsqp_loop_start_gait(hsqp_handle* h, const hsqp_loop_settings* settings, con
 
 // One cycle from the resident buffers (include/hsqp_loop.h, steps 1 to 5).  d_xlog / d_ulog: this cycle's log rows (device) or null.  On a failure the
 // loop's own state (t, x, v_filt) is that of the last completed cycle: the filter state is advanced on a copy and committed with the state.
+// Under isolation (include/hsqp_episode.h): the command in use, the warm start per instance, the status words left to the triage behind step 5.
 static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   hsqp_handle::Loop& L = h->loop;
   const hsqp_loop_settings& st = L.st;
   const size_t B = L.B;
+  const bool iso = L.isolate;
   const int warm = L.have_cycle ? HSQP_WARM_SHIFT : HSQP_WARM_COLD;
   hsqp_problem p{};
   p.batch = L.B; p.n_nodes = st.n_nodes; p.dt = st.dt; p.x_init = L.x;
   // step 2's checks come first, as in hsqp_upload_reference: a rejected cycle leaves the resident solution as it was
   h->have_policy = false;
   const int N_prev = h->N;
-  if (warm == HSQP_WARM_SHIFT) { const int rc = warm_shift_ready(h, L.B, true); if (rc != HSQP_OK) return rc; }
+  if (warm == HSQP_WARM_SHIFT) { const int rc = warm_shift_ready(h, L.B, true, iso); if (rc != HSQP_OK) return rc; }
   StickyError step{h};
   // 1. the targets; the filter state advances in the second half of its buffer
   double* vf_next = L.v_filt + B * CMD_N;
   step(hipMemcpyAsync(vf_next, L.v_filt, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream), "copy v_filt");
-  launch_command_targets(h, L.B, L.v_cmd, vf_next, st.filter_alpha, L.x, L.t, st.n_nodes * st.dt, L.tt, L.ts);
+  launch_command_targets(h, L.B, iso ? L.v_use : L.v_cmd, vf_next, st.filter_alpha, L.x, L.t, st.n_nodes * st.dt, L.tt, L.ts);
   step(hipGetLastError(), "k_command_targets");
   // the gait update between steps 1 and 2 (include/hsqp_gait.h): this cycle's schedule into ne / ev / seq; the shadow state becomes the live one with step 5
   if (L.gait) {
@@ -2701,12 +2742,13 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   { const int rc = set_grid(h, &p, false); if (rc != HSQP_OK) return rc; }
   step(hipMemsetAsync(L.bad, 0, 4, h->stream), "memset");
   step(hipMemcpyAsync(h->d_xinit, L.x, B * NX * 8, hipMemcpyDeviceToDevice, h->stream), "copy x_init");
-  const RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, nullptr, L.bad, L.t, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
+  RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, nullptr, L.bad, L.t, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
+  if (iso && warm == HSQP_WARM_SHIFT) rd.warm_b = L.ep.mode;
   { const int rc = reference_build(h, &p, rd, step); if (rc != HSQP_OK) return rc; }
   // 3. the iteration
   { const int rc = hsqp_iterate_device(h, st.iterations, st.iterate_flags); if (rc != HSQP_OK) return rc; }
   // 4. the plant under the policy over one period
-  { const int rc = rollout_impl(h, &st.rollout, L.s0, L.x, st.period, 1, L.xs, L.us, L.ro_status, nullptr, nullptr, true); if (rc != HSQP_OK) return rc; }
+  { const int rc = rollout_impl(h, &st.rollout, L.s0, L.x, st.period, 1, L.xs, L.us, L.ro_status, nullptr, nullptr, true, iso); if (rc != HSQP_OK) return rc; }
   // 5. the rolled-out state is the next measured state
   HCHECK(hipMemcpyAsync(L.x, L.xs, B * NX * 8, hipMemcpyDeviceToDevice, h->stream));
   HCHECK(hipMemcpyAsync(L.v_filt, vf_next, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -2714,6 +2756,14 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   if (d_ulog) HCHECK(hipMemcpyAsync(d_ulog, L.us, B * NU * 8, hipMemcpyDeviceToDevice, h->stream));
   if (L.gait) h->gait.cur ^= 1;
   L.t += st.period;
+  if (iso) {   // 6. the triage of every instance, and with a resident gait the reset of those that start a new episode at the new loop time
+    const TriageArgs a{L.ep_st, L.cycle, h->d_status, h->d_perf_after, L.ro_status, L.xs, L.x_reset, L.v_cmd, L.ep, L.x, L.v_filt, L.v_use, d_xlog, d_ulog};
+    HSQP_LAUNCH(k_loop_triage, dim3(L.B), dim3(64), 0, h->stream, a);
+    if (L.gait)
+      HSQP_LAUNCH(k_gait_reset_instances, dim3(L.B), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)nullptr, (const int*)L.ep.reset, L.t);
+    HCHECK(hipGetLastError());
+  }
+  ++L.cycle;
   L.have_cycle = true;
   return HSQP_OK;
 }
@@ -2767,6 +2817,131 @@ static int loop_state_impl(hsqp_handle* h, double* t, double* x, double* v_filt,
 }
 int hsqp_loop_state(hsqp_handle* h, double* t, double* x, double* v_filt) { return loop_state_impl(h, t, x, v_filt, false); }
 int hsqp_loop_state_device(hsqp_handle* h, double* t, double* d_x, double* d_v_filt) { return loop_state_impl(h, t, d_x, d_v_filt, true); }
+
+// ---- per-instance failure isolation and episode reset (include/hsqp_episode.h, csrc/hsqp_episode.h)
+void hsqp_episode_defaults(hsqp_episode_settings* s) {
+  if (!s) return;
+  memset(s, 0, sizeof(*s));
+  s->on_failure = HSQP_EPISODE_PARK;
+  s->min_base_height = -HUGE_VAL; s->max_base_height = HUGE_VAL; s->max_tilt = HUGE_VAL;
+}
+
+int hsqp_loop_isolate(hsqp_handle* h, const hsqp_episode_settings* es, const double* x_reset) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_isolate";
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Loop& L = h->loop;
+  if (!es) return loop_bad(h, who, "null settings");
+  if (es->on_failure != HSQP_EPISODE_PARK && es->on_failure != HSQP_EPISODE_RESET) return loop_bad(h, who, "on_failure must be HSQP_EPISODE_PARK or HSQP_EPISODE_RESET");
+  if (es->min_base_height != es->min_base_height || es->max_base_height != es->max_base_height || es->max_tilt != es->max_tilt) return loop_bad(h, who, "NaN bound");
+  if (es->min_base_height > es->max_base_height) return loop_bad(h, who, "min_base_height > max_base_height");
+  if (es->max_tilt < 0.0) return loop_bad(h, who, "max_tilt < 0");
+  const size_t B = L.B;
+  if (x_reset && !all_finite(x_reset, B * NX)) return loop_bad(h, who, "non-finite x_reset");
+  // the gated sweeps take ONE verdict per batch (choose_sweep, the gate in hsqp_iterate_device): one instance's NaN would change the others' bits
+  const int flags = h->st.flags;
+  if ((flags & (HSQP_FLAG_SEGMENTED_RICCATI | HSQP_FLAG_PARALLEL_RICCATI)) ||
+      (!(flags & HSQP_FLAG_SERIAL_RICCATI) && L.B <= HSQP_SCAN_AUTO_BATCH && L.st.n_nodes >= HSQP_SCAN_AUTO_MIN_NODES))
+    return loop_bad(h, who, "this loop takes a KKT-gated backward sweep (parallel-in-time or two-level), whose gate is one verdict for the whole batch: "
+                            "create the handle with HSQP_FLAG_SERIAL_RICCATI");
+  HCHECK(hipSetDevice(h->device));
+  // the episode arrays, x_reset, the command in use, and the staging of a hsqp_loop_reset_instances request (ids, x0, v_cmd)
+  size_t o = 0;
+  const auto carve = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+  size_t o_i[7];
+  for (size_t& v : o_i) v = carve(B * 4);
+  const size_t o_xr = carve(B * NX * 8), o_vu = carve(B * CMD_N * 8);
+  carve(B * 4); carve(B * NX * 8); carve(B * CMD_N * 8);   // (the request's staging: episode_request below)
+  L.isolate = false;
+  DEV_ENSURE(h->d_episode, o, "episode arrays");
+  char* base = h->d_episode.p;
+  int* ip[7];
+  for (int k = 0; k < 7; ++k) ip[k] = reinterpret_cast<int*>(base + o_i[k]);
+  L.ep = EpisodeState{ip[0], ip[1], ip[2], ip[3], ip[4], ip[5], ip[6]};
+  L.x_reset = reinterpret_cast<double*>(base + o_xr); L.v_use = reinterpret_cast<double*>(base + o_vu);
+  const std::vector<int> zero(B, 0), none(B, -1), one(B, 1), shift(B, HSQP_WARM_SHIFT);
+  StickyError step{h};
+  step(hipMemcpyAsync(L.ep.state, zero.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode state");
+  step(hipMemcpyAsync(L.ep.cause, zero.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode cause");
+  step(hipMemcpyAsync(L.ep.fail_cycle, none.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode fail_cycle");
+  step(hipMemcpyAsync(L.ep.n_failures, zero.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode n_failures");
+  step(hipMemcpyAsync(L.ep.n_episodes, one.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode n_episodes");
+  step(hipMemcpyAsync(L.ep.mode, shift.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode mode");
+  step(hipMemcpyAsync(L.ep.reset, zero.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode flags");
+  step(hipMemcpyAsync(L.x_reset, x_reset ? x_reset : L.x, B * NX * 8, x_reset ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream), "upload x_reset");
+  step(hipMemcpyAsync(L.v_use, L.v_cmd, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream), "copy v_cmd");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  L.ep_st = *es;
+  L.isolate = true;
+  return HSQP_OK;
+}
+
+static int loop_isolated(hsqp_handle* h, const char* who) {
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  if (!h->loop.isolate) return loop_bad(h, who, "isolation is off (hsqp_loop_isolate; every hsqp_loop_start turns it off)");
+  return HSQP_OK;
+}
+
+int hsqp_loop_reset_instances(hsqp_handle* h, int n, const int32_t* ids, const double* x0, const double* v_cmd) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_reset_instances";
+  { const int rc = loop_isolated(h, who); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Loop& L = h->loop;
+  if (n < 1) return loop_bad(h, who, "n < 1");
+  if (!ids) return loop_bad(h, who, "null ids");
+  if (n > L.B) return loop_bad(h, who, "more ids than instances (an id is repeated)");
+  std::vector<char> seen(L.B, 0);
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= L.B) return loop_bad(h, who, "id outside [0, B)");
+    if (seen[ids[i]]) return loop_bad(h, who, "repeated id");
+    seen[ids[i]] = 1;
+  }
+  if (x0 && !all_finite(x0, (size_t)n * NX)) return loop_bad(h, who, "non-finite x0");
+  if (v_cmd && !all_finite(v_cmd, (size_t)n * CMD_N)) return loop_bad(h, who, "non-finite command");
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = L.B;
+  // the request's staging lies behind the command in use (hsqp_loop_isolate carved it)
+  char* at = reinterpret_cast<char*>(L.v_use) + align256(B * CMD_N * 8);
+  int* d_ids = reinterpret_cast<int*>(at); at += align256(B * 4);
+  double* d_x0 = reinterpret_cast<double*>(at); at += align256(B * NX * 8);
+  double* d_v = reinterpret_cast<double*>(at);
+  StickyError step{h};
+  step(hipMemcpyAsync(d_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream), "upload ids");
+  if (x0) step(hipMemcpyAsync(d_x0, x0, (size_t)n * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
+  if (v_cmd) step(hipMemcpyAsync(d_v, v_cmd, (size_t)n * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
+  if (step.rc == HSQP_OK) {
+    const HostResetArgs a{d_ids, x0 ? d_x0 : nullptr, v_cmd ? d_v : nullptr, L.x_reset, L.ep, L.x, L.v_cmd, L.v_filt, L.v_use};
+    HSQP_LAUNCH(k_episode_host_reset, dim3(n), dim3(64), 0, h->stream, a);
+    if (L.gait)
+      HSQP_LAUNCH(k_gait_reset_instances, dim3(n), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)d_ids, (const int*)nullptr, L.t);
+    step(hipGetLastError(), "k_episode_host_reset");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+
+static int loop_episodes_impl(hsqp_handle* h, int32_t* state, int32_t* cause, int32_t* fail_cycle, int32_t* n_failures, int32_t* n_episodes, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  { const int rc = loop_isolated(h, dev ? "hsqp_loop_episodes_device" : "hsqp_loop_episodes"); if (rc != HSQP_OK) return rc; }
+  HCHECK(hipSetDevice(h->device));
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const EpisodeState& e = h->loop.ep;
+  const size_t bytes = (size_t)h->loop.B * 4;
+  if (state) HCHECK(hipMemcpyAsync(state, e.state, bytes, kind, h->stream));
+  if (cause) HCHECK(hipMemcpyAsync(cause, e.cause, bytes, kind, h->stream));
+  if (fail_cycle) HCHECK(hipMemcpyAsync(fail_cycle, e.fail_cycle, bytes, kind, h->stream));
+  if (n_failures) HCHECK(hipMemcpyAsync(n_failures, e.n_failures, bytes, kind, h->stream));
+  if (n_episodes) HCHECK(hipMemcpyAsync(n_episodes, e.n_episodes, bytes, kind, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_loop_episodes(hsqp_handle* h, int32_t* state, int32_t* cause, int32_t* fail_cycle, int32_t* n_failures, int32_t* n_episodes) {
+  return loop_episodes_impl(h, state, cause, fail_cycle, n_failures, n_episodes, false);
+}
+int hsqp_loop_episodes_device(hsqp_handle* h, int32_t* d_state, int32_t* d_cause, int32_t* d_fail_cycle, int32_t* d_n_failures, int32_t* d_n_episodes) {
+  return loop_episodes_impl(h, d_state, d_cause, d_fail_cycle, d_n_failures, d_n_episodes, true);
+}
 
 int hsqp_last_kernel_ms(hsqp_handle* h, double out_ms[5]) {
   if (!h || !out_ms) return HSQP_ERR_BAD_ARG;

@@ -21,6 +21,7 @@ namespace hsqp {
 
 struct WarmArgs {
   int mode;                  // HSQP_WARM_CALLER (stamps only), HSQP_WARM_SHIFT, HSQP_WARM_COLD
+  const int* mode_b;         // [B] HSQP_WARM_SHIFT / _COLD per instance (the isolated loop, include/hsqp_episode.h), or null: `mode` for all
   int B, N, N_prev;          // batch, intervals of the new grid, intervals of the previous solution
   int cent;                  // centroidal handle: entries HSQP_CNX.. of a state row are zero
   double t0, dt;             // uniform grid (node_times == null)
@@ -36,6 +37,9 @@ struct WarmArgs {
   double* u;                 // [B][N][NU]
   double* stamps;            // [B][N+1] out: raw stamps of the new grid
 };
+
+// the mode of instance b.  A COLD instance reads nothing of the previous solution (x_prev, u_prev, stamps_prev): it may be NaN.
+HSQP_HD int warm_mode(const WarmArgs& w, int b) { return w.mode_b ? w.mode_b[b] : w.mode; }
 
 // raw stamp of node k of instance b of the new grid
 HSQP_HD double warm_stamp(const WarmArgs& w, int b, int k) {
@@ -91,8 +95,9 @@ HSQP_HD void warm_node(const Ctx& ctx, const WarmArgs& w, const double* tp, int 
   const int N = w.N, Np = w.N_prev;
   const double tau = warm_stamp(w, b, k);
   if (ctx.tid == 0) w.stamps[(size_t)b * (N + 1) + k] = tau;
-  if (w.mode == HSQP_WARM_CALLER) return;
-  const bool shift = w.mode == HSQP_WARM_SHIFT;
+  const int mode = warm_mode(w, b);
+  if (mode == HSQP_WARM_CALLER) return;
+  const bool shift = mode == HSQP_WARM_SHIFT;
   const double T = shift ? tp[Np] : 0.0;
   const bool covered = shift && tau <= T;
   // the state: interpolated at node src's stamp; a node past T keeps the state of the last covered node before it (src), x_init

@@ -18,6 +18,7 @@
 #include "../../include/hsqp_rollout.h"
 #include "../../include/hsqp_loop.h"
 #include "../../include/hsqp_gait.h"
+#include "../../include/hsqp_episode.h"
 
 namespace hsqp_host {
 
@@ -216,6 +217,31 @@ class HipSqpSolver {
     x.assign(loopBatch_ * HSQP_NX, 0.0); filteredCommands.assign(loopBatch_ * HSQP_CMD_N, 0.0);
     const int rc = hsqp_loop_state(h_, &t, x.data(), filteredCommands.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_state failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** ---- per-instance failure isolation and episode reset of the started loop (include/hsqp_episode.h): a failed instance is parked or reset on
+   *  the device, the others go on; runLoop then throws only for what is not per instance.  xReset [batch][HSQP_NX], or empty: the measured
+   *  states the loop holds now. */
+  void isolateLoop(const hsqp_episode_settings& st, const std::vector<double>& xReset = {}) {
+    if (!xReset.empty() && xReset.size() != loopBatch_ * HSQP_NX) throw std::runtime_error("[HipSqpSolver] isolateLoop: one state per instance of the started loop expected");
+    const int rc = hsqp_loop_isolate(h_, &st, xReset.empty() ? nullptr : xReset.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_isolate failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** A new episode for the instances `ids` from the next cycle on: x0 [ids.size()][HSQP_NX] or empty (their xReset), velocityCommands
+   *  [ids.size()][4] or empty (keep). */
+  void resetLoopInstances(const std::vector<int32_t>& ids, const std::vector<double>& x0 = {}, const std::vector<double>& velocityCommands = {}) {
+    if ((!x0.empty() && x0.size() != ids.size() * HSQP_NX) || (!velocityCommands.empty() && velocityCommands.size() != ids.size() * HSQP_CMD_N))
+      throw std::runtime_error("[HipSqpSolver] resetLoopInstances: inconsistent array sizes");
+    const int rc = hsqp_loop_reset_instances(h_, (int)ids.size(), ids.data(), x0.empty() ? nullptr : x0.data(), velocityCommands.empty() ? nullptr : velocityCommands.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_reset_instances failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** The episode record of every instance: HSQP_EP_* state and cause of the last failure, its cycle (-1: none), failures and episodes so far. */
+  struct LoopEpisodes { std::vector<int32_t> state, cause, failCycle, nFailures, nEpisodes; };
+  LoopEpisodes loopEpisodes() {
+    LoopEpisodes e;
+    for (std::vector<int32_t>* v : {&e.state, &e.cause, &e.failCycle, &e.nFailures, &e.nEpisodes}) v->assign(loopBatch_, 0);
+    const int rc = hsqp_loop_episodes(h_, e.state.data(), e.cause.data(), e.failCycle.data(), e.nFailures.data(), e.nEpisodes.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_episodes failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return e;
   }
 
   const PrimalSolution& getPrimalSolution() const { return solution_; }

@@ -120,6 +120,13 @@ def load_library():
     lib.hsqp_gait_state.argtypes = [C.c_void_p, _ip, _dp, _ip, _dp, _ip]
     lib.hsqp_gait_state_device.argtypes = [C.c_void_p, _ip, _dp, _ip, _dp, _ip]
     lib.hsqp_loop_start_gait.argtypes = [C.c_void_p, _ls, _gs, C.c_int, C.c_double, _dp, _dp]
+    _es = C.POINTER(_abi.EpisodeSettings)
+    lib.hsqp_episode_defaults.argtypes = [_es]
+    lib.hsqp_episode_defaults.restype = None
+    lib.hsqp_loop_isolate.argtypes = [C.c_void_p, _es, _dp]
+    lib.hsqp_loop_reset_instances.argtypes = [C.c_void_p, C.c_int, _ip, _dp, _dp]
+    lib.hsqp_loop_episodes.argtypes = [C.c_void_p, _ip, _ip, _ip, _ip, _ip]
+    lib.hsqp_loop_episodes_device.argtypes = [C.c_void_p, _ip, _ip, _ip, _ip, _ip]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -599,6 +606,48 @@ class HipSqpSolver:
         t = C.c_double(0.0)
         self._check(self.lib.hsqp_loop_state_device(self.h, C.byref(t), cast(x_ptr), cast(v_filt_ptr)))
         return t.value
+
+    # ---- include/hsqp_episode.h: per-instance failure isolation and episode reset
+    def episode_settings(self, on_failure="park", min_base_height=None, max_base_height=None, max_tilt=None):
+        """hsqp_episode_settings: hsqp_episode_defaults (park, bounds off) with the given policy ("park" / "reset") and box."""
+        st = _abi.EpisodeSettings()
+        self.lib.hsqp_episode_defaults(C.byref(st))
+        st.on_failure = {"park": _abi.EPISODE_PARK, "reset": _abi.EPISODE_RESET}.get(on_failure, on_failure)
+        for k, v in (("min_base_height", min_base_height), ("max_base_height", max_base_height), ("max_tilt", max_tilt)):
+            if v is not None:
+                setattr(st, k, float(v))
+        return st
+
+    def loop_isolate(self, settings=None, x_reset=None):
+        """hsqp_loop_isolate on the started loop: a failed instance is parked or reset on the device (settings: episode_settings()), the others
+        go on.  x_reset [B][58]: where a failed instance restarts (None: the measured states the loop holds now)."""
+        settings = self.episode_settings() if settings is None else settings
+        if x_reset is not None:
+            x_reset = _c(np.broadcast_to(x_reset, (max(self._loop_batch, 1), _abi.NX)))
+        self._check(self.lib.hsqp_loop_isolate(self.h, C.byref(settings), x_reset.ctypes.data_as(_dp) if x_reset is not None else None))
+
+    def loop_reset(self, ids, x0=None, v_cmd=None):
+        """hsqp_loop_reset_instances: a new episode for the instances `ids`, from x0 [n][58] (None: their x_reset) with the commands v_cmd [n][4]
+        (None: keep), in effect from the next cycle."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        n = ids.shape[0]
+        if x0 is not None:
+            x0 = _c(np.broadcast_to(x0, (n, _abi.NX)))
+        if v_cmd is not None:
+            v_cmd = _c(np.broadcast_to(v_cmd, (n, _abi.CMD_N)))
+        self._check(self.lib.hsqp_loop_reset_instances(self.h, n, ids.ctypes.data_as(C.POINTER(C.c_int32)), x0.ctypes.data_as(_dp) if x0 is not None else None,
+                                                       v_cmd.ctypes.data_as(_dp) if v_cmd is not None else None))
+
+    def loop_episodes(self):
+        """hsqp_loop_episodes: dict(state[B], cause[B], fail_cycle[B], n_failures[B], n_episodes[B]) (_abi.EP_*)."""
+        names = ("state", "cause", "fail_cycle", "n_failures", "n_episodes")
+        out = {k: np.zeros(max(self._loop_batch, 1), np.int32) for k in names}
+        self._check(self.lib.hsqp_loop_episodes(self.h, *[out[k].ctypes.data_as(C.POINTER(C.c_int32)) for k in names]))
+        return out
+
+    def loop_episodes_device(self, state_ptr=0, cause_ptr=0, fail_cycle_ptr=0, n_failures_ptr=0, n_episodes_ptr=0):
+        icast = lambda a: C.cast(C.c_void_p(int(a)), C.POINTER(C.c_int32)) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_loop_episodes_device(self.h, icast(state_ptr), icast(cause_ptr), icast(fail_cycle_ptr), icast(n_failures_ptr), icast(n_episodes_ptr)))
 
     # ---- include/hsqp_gait.h: per-instance gait schedule and ladder
     def gait_reset(self, settings, batch, t0=0.0):
