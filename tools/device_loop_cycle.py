@@ -7,7 +7,14 @@ reports one hsqp_loop_run(cycles) call per cycle (`run_ms_per_cycle`), which is 
 Prints one JSON line with the fields of tools/closed_loop_cycle.py (no rollout share and no step counts: the loop does not stop between the
 iteration and the rollout, and its rollout keeps no step counters).
     python tools/device_loop_cycle.py [--cycles 30] [--warmup 3] [--batch 256] [--nodes 100] [--controller feedforward|feedback]
-                                      [--commands same|spread] [--gait ladder|walk] [--isolate park|reset]
+                                      [--commands same|spread] [--gait ladder|walk] [--isolate park|reset] [--with-push NEWTONS]
+    python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
+--with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
+--push: a small push-recovery sweep instead of the timing.  Every instance walks under the same command; instance b is pushed sideways at the
+pelvis (the base link's origin) with b / (batch - 1) of --push-max newtons from --push-at seconds on for --push-for seconds.  Isolation is on
+(park; box: base height above 0.45 m, tilt below 0.7 rad), and the sweep runs once with the feed-forward and once with the feedback controller.
+It prints which instances the triage recorded as failed, with which cause and in which cycle.  It reports; it asserts nothing: the plant's joints
+are ideal acceleration sources and its contacts do not slip, and nobody has measured at which magnitude the G1 falls in this model.
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -32,6 +39,50 @@ from wb_humanoid_mpc_amd.reference import gait_settings, pack_reference, tile_ga
 from wb_humanoid_mpc_amd.solver import HipSqpSolver  # noqa: E402
 
 
+def push_sweep(args):
+    m = load_model()
+    given = {a.split("=")[0] for a in sys.argv[1:]}
+    B = args.batch if "--batch" in given else 16
+    N = args.nodes if "--nodes" in given else 40
+    cycles = args.cycles if "--cycles" in given else 120
+    dt = m.sqp["dt"]
+    t_final = cycles * args.period + N * dt + 1.0
+    schedule = tile_gait(m.gaits["walk"], 0.3, t_final)
+    knots = velocity_command_targets(m, (0.3, 0.0, 0.7925, 0.0), 0.0, m.initial_state, t_final)
+    n_events, event_times, mode_sequence = pack_reference([schedule] * B, [knots] * B)[:3]
+    x_init = np.tile(m.initial_state, (B, 1))
+    cmd = np.tile((0.3, 0.0, 0.7925, 0.0), (B, 1))
+    force = args.push_max * np.arange(B) / max(B - 1, 1)
+    pushes = [[dict(body=0, t_start=args.push_at, duration=args.push_for, point=(0.0, 0.0, 0.0), force=(0.0, f, 0.0))] for f in force]
+    causes = {0: "alive", 1: "numeric", 2: "rollout", 3: "bounds"}
+    rows = {}
+    s = HipSqpSolver(m, max_nodes=N, max_batch=B, linesearch=True)
+    s.set_scan_backoff_persistent(True)
+    try:
+        s.set_pushes(pushes)
+        for controller in ("feedforward", "feedback"):
+            st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True, controller=controller)
+            s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
+            s.loop_isolate(s.episode_settings("park", min_base_height=0.45, max_tilt=0.7))
+            r = s.loop_run(cycles)
+            ep = s.loop_episodes()
+            x = r["x"]                                         # [cycle][instance][58], NaN rows once parked
+            sway = np.nanmax(np.abs(x[:, :, 1] - x[:, :1, 1]), axis=0)
+            rows[controller] = (ep, sway)
+    finally:
+        s.close()
+    print(f"push sweep: {B} instances x {N} nodes, walk at 0.3 m/s, {cycles} cycles of {args.period:.4f} s; lateral push at the pelvis from "
+          f"{args.push_at} s for {args.push_for} s (cycles {int(args.push_at / args.period)} .. {int((args.push_at + args.push_for) / args.period)})")
+    print(f"{'instance':>8} {'force [N]':>10} | " + " | ".join(f"{c + ': state':>20} {'cycle':>6} {'sway [m]':>9}" for c in rows))
+    for b in range(B):
+        cells = []
+        for c, (ep, sway) in rows.items():
+            cells.append(f"{causes.get(int(ep['cause'][b]), '?'):>20} {int(ep['fail_cycle'][b]) if ep['n_failures'][b] else '-':>6} {sway[b]:9.4f}")
+        print(f"{b:8d} {force[b]:10.1f} | " + " | ".join(cells))
+    print(json.dumps({"metric": "push_sweep", "batch": B, "nodes": N, "cycles": cycles, "forces": [round(float(f), 2) for f in force],
+                      **{c: {"failed": [int(b) for b in np.nonzero(ep["n_failures"])[0]], "fail_cycle": [int(v) for v in ep["fail_cycle"]]} for c, (ep, _) in rows.items()}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=30)
@@ -44,7 +95,14 @@ def main():
     ap.add_argument("--filter-alpha", type=float, default=0.8)
     ap.add_argument("--gait", default=None, choices=("ladder", "walk"))
     ap.add_argument("--isolate", default=None, choices=("park", "reset"))
+    ap.add_argument("--with-push", type=float, default=None)
+    ap.add_argument("--push", action="store_true")
+    ap.add_argument("--push-max", type=float, default=400.0)
+    ap.add_argument("--push-at", type=float, default=0.5)
+    ap.add_argument("--push-for", type=float, default=0.2)
     args = ap.parse_args()
+    if args.push:
+        return push_sweep(args)
     m = load_model()
     B, N, dt = args.batch, args.nodes, m.sqp["dt"]
     t_final = (2 * args.warmup + 2 * args.cycles) * args.period + N * dt + 1.0
@@ -79,6 +137,8 @@ def main():
             s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
         if args.isolate:
             s.loop_isolate(s.episode_settings(args.isolate))
+        if args.with_push is not None:
+            s.set_pushes([[dict(body=0, t_start=0.0, duration=1e6, point=(0.0, 0.0, 0.0), force=(0.0, args.with_push, 0.0))]] * B)
         for c in range(args.warmup + args.cycles):
             if c in changes:
                 s.loop_command(changes[c])
@@ -100,7 +160,7 @@ def main():
     heights = np.concatenate(heights)
     q = np.percentile(cycle_ms, [25, 75])
     print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
-                      "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate,
+                      "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
                       "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),

@@ -159,6 +159,18 @@ class EpisodeSettings(C.Structure):   # hsqp_episode_settings
 # entry points of include/hsqp_episode.h (tests/test_episode.py checks that the library exports each of them and the binding declares it)
 EPISODE_ENTRY_POINTS = ("hsqp_episode_defaults", "hsqp_loop_isolate", "hsqp_loop_reset_instances", "hsqp_loop_episodes", "hsqp_loop_episodes_device")
 
+# include/hsqp_push.h
+PUSH_MAX = 8
+
+
+class Push(C.Structure):   # hsqp_push
+    _fields_ = [("body", C.c_int32), ("reserved", C.c_int32), ("t_start", C.c_double), ("duration", C.c_double), ("point", C.c_double * 3),
+                ("force", C.c_double * 3)]
+
+
+# entry points of include/hsqp_push.h (tests/test_push.py checks that the library exports each of them and the binding declares it)
+PUSH_ENTRY_POINTS = ("hsqp_push_set", "hsqp_push_set_device", "hsqp_push_clear", "hsqp_push_get")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

@@ -981,6 +981,7 @@ struct RolloutArgs {
   hsqp_rollout_settings st;
   const double* s0; const double* x0; double duration; int n;
   double* x; double* u; int32_t* status; int32_t* steps; int32_t* rejected;
+  PushTable push;                                           // the resident push table (include/hsqp_push.h; n null: none)
 };
 template <class SW>
 __global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restrict__ dm, RolloutArgs a) {
@@ -990,7 +991,7 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restri
                         a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count, dm->formulation == HSQP_FORM_CENTROIDAL ? 1 : 0};
   rollout_instance(Ctx{(int)threadIdx.x, RO_THREADS, nullptr}, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n,
                    a.x ? a.x + (size_t)b * a.n * NX : nullptr, a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr,
-                   a.rejected ? a.rejected + b : nullptr);
+                   a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
 static_assert(sizeof(RolloutWS<StageWST<false>>) <= 65536 && sizeof(RolloutWS<CentWST<false>>) <= 65536, "the rollout runs without a dynamic-LDS attribute");
 
@@ -1112,6 +1113,10 @@ struct hsqp_handle {
   DevBuf<double> d_fb;            // staging of hsqp_feedback_policy (host destinations)
   DevBuf<double> d_ro_gain;       // gain window of the rollout's feedback controller: K [B][count][35][58], then uff [B][count][35] (allocated when first used, sized by the window)
   DevBuf<char> d_ro;              // staging of the rollout (s0, x0, outputs of the host entry point, window, statuses)
+  // the resident push table (include/hsqp_push.h): n_pushes [push_B] (int32, padded to 256 bytes), then pushes [push_B][push_max]; push_B == 0: no table
+  DevBuf<char> d_push;
+  int push_B = 0, push_max = 0;
+  bool stamps_resident = false;   // d_stamps[stamps_cur] holds the raw stamps of the resident problem (it came through hsqp_upload_reference or the loop): the pushes' clock
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
   // with non-decreasing stamps
@@ -1536,6 +1541,7 @@ static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   HCHECK(hipMemcpyAsync(h->d_par, p->node_params, B * (N + 1) * NP * 8, kind, h->stream));
   HCHECK(hipStreamSynchronize(h->stream));
   commit_problem(h, p, false);
+  h->stamps_resident = false;
   return HSQP_OK;
 }
 
@@ -1612,6 +1618,7 @@ static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& 
   if (bad) { h->err = "a swing phase has no lift-off / touch-down inside the mode schedule"; return HSQP_ERR_BAD_ARG; }
   h->stamps_cur = 1 - h->stamps_cur;
   commit_problem(h, p, r.sorted);
+  h->stamps_resident = true;
   return HSQP_OK;
 }
 
@@ -2244,6 +2251,9 @@ static const char* rollout_settings_error(const hsqp_rollout_settings& st) {
   return nullptr;
 }
 
+// bytes of the n_pushes block in front of the pushes in d_push
+static size_t push_n_bytes(int batch) { return align256((size_t)batch * 4); }
+
 // dev: every array argument is device memory of the handle's GPU
 // per_instance (the isolated loop, include/hsqp_episode.h): an instance's status word — of the iteration, of the integration — is the instance's
 // alone: it is written to `status`, not turned into the call's return code
@@ -2258,6 +2268,8 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
   if (n < 1) return bad("n_samples < 1");
   if (per_instance) { if (!h->have_policy) return bad("no feedback policy (no successful iteration since the last upload)"); }
   else { const int rc = feedback_ready(h, who); if (rc != HSQP_OK) return rc; }
+  if (h->push_B && h->push_B != h->B)
+    return bad(("the push table holds " + std::to_string(h->push_B) + " instances, the resident problem " + std::to_string(h->B) + " (hsqp_push_set / hsqp_push_clear)").c_str());
   const size_t B = h->B, nn = (size_t)n;
   const int N = h->N;
   const bool cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL, feedback = st->controller == HSQP_ROLLOUT_FEEDBACK;
@@ -2301,7 +2313,11 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
                 (const double*)h->d_xnew, (const double*)h->d_unew, (const double*)h->d_dt, N, first, count, cent ? 1 : 0, dK, duff);
     step(hipGetLastError(), "k_feedback_gains");
   }
-  const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, d_status, d_steps, d_rej};
+  PushTable pt{nullptr, nullptr, 0, nullptr, 0};
+  if (h->push_B)
+    pt = PushTable{reinterpret_cast<const int32_t*>(h->d_push.p), reinterpret_cast<const hsqp_push*>(h->d_push.p + push_n_bytes(h->push_B)), h->push_max,
+                   h->stamps_resident ? (const double*)h->d_stamps[h->stamps_cur] : nullptr, N + 1};
+  const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, d_status, d_steps, d_rej, pt};
   if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
   else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
   step(hipGetLastError(), "k_rollout");
@@ -2335,6 +2351,66 @@ int hsqp_rollout_policy(hsqp_handle* h, const hsqp_rollout_settings* st, const d
 int hsqp_rollout_policy_device(hsqp_handle* h, const hsqp_rollout_settings* st, const double* d_s0, const double* d_x0, double duration, int n_samples,
                                double* d_x, double* d_u, int32_t* d_status, int32_t* d_steps, int32_t* d_rejected) {
   return rollout_impl(h, st, d_s0, d_x0, duration, n_samples, d_x, d_u, d_status, d_steps, d_rejected, true);
+}
+
+// ---- external pushes on the plant (include/hsqp_push.h, csrc/hsqp_push.h): the resident table
+static int push_set_impl(hsqp_handle* h, int batch, int max_pushes, const int32_t* n_pushes, const hsqp_push* pushes, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_push_set_device" : "hsqp_push_set";
+  const auto bad = [&](const std::string& what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (!n_pushes || !pushes) return bad("null n_pushes or pushes");
+  if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+  if (max_pushes < 1 || max_pushes > HSQP_PUSH_MAX) return bad("max_pushes outside [1, HSQP_PUSH_MAX]");
+  if (!dev) {
+    for (int b = 0; b < batch; ++b) {
+      const std::string at = "instance " + std::to_string(b);
+      if (n_pushes[b] < 0 || n_pushes[b] > max_pushes) return bad(at + ": n_pushes outside [0, max_pushes]");
+      for (int i = 0; i < n_pushes[b]; ++i) {
+        const hsqp_push& p = pushes[(size_t)b * max_pushes + i];
+        const std::string pi = at + ", push " + std::to_string(i);
+        if (p.body < 0 || p.body >= NB) return bad(pi + ": body outside the tree");
+        if (p.reserved != 0) return bad(pi + ": reserved must be 0");
+        bool finite = std::isfinite(p.t_start) && std::isfinite(p.duration);
+        for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(p.point[k]) && std::isfinite(p.force[k]);
+        if (!finite)
+          return bad(pi + ": non-finite t_start, duration, point or force");
+        if (p.duration < 0.0) return bad(pi + ": negative duration");
+      }
+    }
+  }
+  HCHECK(hipSetDevice(h->device));
+  const size_t nb = push_n_bytes(batch), pb = (size_t)batch * max_pushes * sizeof(hsqp_push);
+  h->push_B = 0;   // (a failure below leaves no table)
+  DEV_ENSURE(h->d_push, nb + pb, "push table");
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HCHECK(hipMemcpyAsync(h->d_push.p, n_pushes, (size_t)batch * 4, kind, h->stream));
+  HCHECK(hipMemcpyAsync(h->d_push.p + nb, pushes, pb, kind, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  h->push_B = batch; h->push_max = max_pushes;
+  return HSQP_OK;
+}
+int hsqp_push_set(hsqp_handle* h, int batch, int max_pushes, const int32_t* n_pushes, const hsqp_push* pushes) {
+  return push_set_impl(h, batch, max_pushes, n_pushes, pushes, false);
+}
+int hsqp_push_set_device(hsqp_handle* h, int batch, int max_pushes, const int32_t* d_n_pushes, const hsqp_push* d_pushes) {
+  return push_set_impl(h, batch, max_pushes, d_n_pushes, d_pushes, true);
+}
+int hsqp_push_clear(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  h->push_B = 0; h->push_max = 0;
+  return HSQP_OK;
+}
+int hsqp_push_get(hsqp_handle* h, int* batch, int* max_pushes, int32_t* n_pushes, hsqp_push* pushes) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (!h->push_B) { h->err = "hsqp_push_get: no push table set"; return HSQP_ERR_BAD_ARG; }
+  if (batch) *batch = h->push_B;
+  if (max_pushes) *max_pushes = h->push_max;
+  HCHECK(hipSetDevice(h->device));
+  if (n_pushes) HCHECK(hipMemcpyAsync(n_pushes, h->d_push.p, (size_t)h->push_B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (pushes)
+    HCHECK(hipMemcpyAsync(pushes, h->d_push.p + push_n_bytes(h->push_B), (size_t)h->push_B * h->push_max * sizeof(hsqp_push), hipMemcpyDeviceToHost, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
 }
 
 // ---- velocity-command targets and the resident closed loop (include/hsqp_loop.h, csrc/hsqp_loop.h)
@@ -2774,6 +2850,8 @@ static int loop_run_impl(hsqp_handle* h, int n_cycles, double* x_log, double* u_
   const char* who = dev ? "hsqp_loop_run_device" : "hsqp_loop_run";
   { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
   if (n_cycles < 1) return loop_bad(h, who, "n_cycles < 1");
+  if (h->push_B && h->push_B != h->loop.B)
+    return loop_bad(h, who, ("the push table holds " + std::to_string(h->push_B) + " instances, the loop " + std::to_string(h->loop.B) + " (hsqp_push_set / hsqp_push_clear)").c_str());
   HCHECK(hipSetDevice(h->device));
   const size_t B = h->loop.B, nx = B * NX, nu = B * NU, n = n_cycles;
   double* d_xl = x_log;

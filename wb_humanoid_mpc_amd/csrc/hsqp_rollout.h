@@ -9,11 +9,16 @@
 //                              window of policy entries [first, first + count) formed beforehand by k_feedback_gains
 //   integrators: Dormand–Prince 5(4) with FSAL and odeint's step control (ODE45), classical RK4 with a fixed step; the step-control
 //                rules and the step cap are restated from memory of boost odeint / ocs2 (include/hsqp_rollout.h: the assumptions).
-// The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp).
+//   pushes:      the external pushes of the instance (include/hsqp_push.h, hsqp_push.h) act on the plant only: rollout_push adds the active
+//                ones behind the flow evaluation of the rollout (no other user of stage_eval<false> / cent_lane_flow sees them), their edges
+//                are break points beside the grid's events, and a segment's activity is fixed at its start.  An instance without pushes
+//                never enters that code.
+// The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp, tests/push/push_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
 #include "hsqp_cent_lq.h"
 #include "hsqp_feedback.h"
+#include "hsqp_push.h"
 #include "../../include/hsqp_rollout.h"
 
 namespace hsqp {
@@ -42,6 +47,7 @@ struct RolloutWS {
   double xn[NX];          // state at the end of the step
   double u[NU];           // controller input of the evaluation
   double red[RO_THREADS]; // per-thread partials of the workgroup reductions (error norm, finiteness)
+  PushSet push;           // the instance's pushes (read once at the start of rollout_instance)
 };
 
 HSQP_HD bool ro_finite(double v) { return v - v == 0.0; }
@@ -79,6 +85,54 @@ HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, CentWST<false>& ws
   WG_SYNC(ctx);
 }
 
+// ---- external pushes (include/hsqp_push.h): the pushes `mask` names, applied to the xdot rollout_flow has just formed from the same workspace.
+// The placements R / r of every body (relative to the base origin O) are those of the evaluation.
+// Whole-body: the wrench {P x f, f} about O joins F_ext - F in Ftil, where the contact wrenches entered, and the two base solves of
+// stage_eval's totals are redone on it (Iinv, Einv and the total mass are still in the workspace).
+HSQP_HD void rollout_push(const Ctx& ctx, const DevModel&, StageWST<false>& ws, PushSet& ps, unsigned mask, double* xdot) {
+  WG_FOR(ctx, i, ps.n) {
+    if (!((mask >> i) & 1u)) continue;
+    const int b = ps.body[i];
+    double P[3], mom[3];
+    m3_mulv(ws.R[b], ps.point[i], P);
+    for (int k = 0; k < 3; ++k) P[k] += ws.r[b][k];
+    v3_cross(P, ps.force[i], mom);
+    for (int k = 0; k < 3; ++k) { ps.wr[i][k] = mom[k]; ps.wr[i][3 + k] = ps.force[i][k]; }
+  }
+  WG_SYNC(ctx);
+  WG_FOR(ctx, it, 1) {
+    for (int i = 0; i < ps.n; ++i)
+      if ((mask >> i) & 1u) for (int k = 0; k < 6; ++k) ws.Ftil[k] += ps.wr[i][k];
+    m3_mulv(ws.Iinv, ws.Ftil, ws.y);
+    const double minv = 1.0 / ws.Ic[0][0];
+    for (int k = 0; k < 3; ++k) ws.ab[k] = ws.Ftil[3 + k] * minv;
+    m3_mulv(ws.Einv, ws.y, ws.ab + 3);
+    for (int k = 0; k < 6; ++k) xdot[NV + k] = ws.ab[k];
+  }
+  WG_SYNC(ctx);
+}
+// Centroidal: f / m into the linear, (P - com) x f / m into the angular rows of the normalised momentum rate (com as cent_finish forms it)
+HSQP_HD void rollout_push(const Ctx& ctx, const DevModel& dm, CentWST<false>& ws, PushSet& ps, unsigned mask, double* xdot) {
+  WG_FOR(ctx, i, ps.n) {
+    if (!((mask >> i) & 1u)) continue;
+    const int b = ps.body[i];
+    const double iM = 1.0 / dm.total_mass;
+    double P[3], arm[3], mom[3];
+    m3_mulv(ws.R[b], ps.point[i], P);
+    for (int k = 0; k < 3; ++k) arm[k] = (P[k] + ws.r[b][k]) - ws.sums[k] * iM;
+    v3_cross(arm, ps.force[i], mom);
+    for (int k = 0; k < 3; ++k) { ps.wr[i][k] = ps.force[i][k] * iM; ps.wr[i][3 + k] = mom[k] * iM; }
+  }
+  WG_SYNC(ctx);
+  WG_FOR(ctx, r, 6) {
+    double acc = xdot[r];
+    for (int i = 0; i < ps.n; ++i)
+      if ((mask >> i) & 1u) acc += ps.wr[i][r];
+    xdot[r] = acc;
+  }
+  WG_SYNC(ctx);
+}
+
 // ---- controller input u [NU] at s seconds after the first node and the state x
 HSQP_HD void rollout_control(const Ctx& ctx, const RolloutPolicy& p, int controller, double s, const double* x, double* u) {
   const PolicySegment g = p.dts ? policy_segment_grid(p.N, p.dts, s) : policy_segment_uniform(p.N, p.dt, s);
@@ -105,12 +159,14 @@ HSQP_HD void rollout_control(const Ctx& ctx, const RolloutPolicy& p, int control
   WG_SYNC(ctx);
 }
 
-// one evaluation of the closed loop: k = f(x, u(s, x)) (a non-finite input reaches k: its joint part is copied, the wrenches enter a_b)
+// one evaluation of the closed loop: k = f(x, u(s, x)) (a non-finite input reaches k: its joint part is copied, the wrenches enter a_b),
+// with the pushes `mask` of the segment (0: none)
 template <class SW>
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, int controller, double s, const double* x,
-                          double* k) {
+                          double* k, unsigned mask) {
   rollout_control(ctx, p, controller, s, x, w.u);
   rollout_flow(ctx, dm, w.sw, x, w.u, k);
+  if (mask) rollout_push(ctx, dm, w.sw, w.push, mask, k);
 }
 
 // whether any of the first n entries of rows r0 .. r1 - 1 of v (row stride NX) is not finite: a workgroup reduction, uniform
@@ -172,12 +228,12 @@ HSQP_HD void rollout_combine(const Ctx& ctx, RolloutWS<SW>& w, int nl, bool ode4
 // derivative, the stage-6 state — the 5th-order solution — goes to w.xn; RK4: 0 .. 3).  One call site of the flow evaluation per step.
 template <class SW>
 HSQP_HD void rollout_stages(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, int controller, bool ode45, int nl, double t,
-                            double h, double tn) {
+                            double h, double tn, unsigned mask) {
   for (int s = ode45 ? 1 : 0; s < (ode45 ? 7 : 4); ++s) {
     const double c = rollout_c(ode45, s);
     double* xe = s == 6 ? w.xn : w.xs;
     if (s > 0) rollout_combine(ctx, w, nl, ode45, s, h, xe);
-    rollout_eval(ctx, dm, w, p, controller, c == 1.0 ? tn : t + c * h, s > 0 ? xe : w.x, w.k[s]);
+    rollout_eval(ctx, dm, w, p, controller, c == 1.0 ? tn : t + c * h, s > 0 ? xe : w.x, w.k[s], mask);
   }
 }
 
@@ -199,8 +255,9 @@ HSQP_HD double rollout_error(const Ctx& ctx, RolloutWS<SW>& w, int nl, double h,
   return err;
 }
 
-// Integrates w.x from ta to tb (no event inside) and returns HSQP_ROLLOUT_*.  acc: accepted steps of the sample interval so far (cap: its
-// limit), nacc / nrej: the instance's accepted / rejected steps.
+// Integrates w.x from ta to tb (no event and no push edge inside) and returns HSQP_ROLLOUT_*.  acc: accepted steps of the sample interval so
+// far (cap: its limit), nacc / nrej: the instance's accepted / rejected steps.  The pushes that act are those active at ta, for every stage
+// evaluation of the segment (the one at tb included).
 template <class SW>
 HSQP_HD int rollout_segment(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, const hsqp_rollout_settings& st, double ta,
                             double tb, double cap, int& acc, int& nacc, int& nrej) {
@@ -209,8 +266,9 @@ HSQP_HD int rollout_segment(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w
   double h = st.initial_step < tb - ta ? st.initial_step : tb - ta;
   double t = ta;
   int fails = 0;
+  const unsigned mask = w.push.n ? push_active(w.push, ta) : 0u;
   if (ode45) {   // FSAL: the derivative at the start of the segment, then the last stage of every accepted step
-    rollout_eval(ctx, dm, w, p, st.controller, t, w.x, w.k[0]);
+    rollout_eval(ctx, dm, w, p, st.controller, t, w.x, w.k[0], mask);
     if (rollout_nonfinite(ctx, w, &w.k[0][0], 0, 1, nl)) return HSQP_ROLLOUT_NONFINITE;
   }
   while (t < tb) {
@@ -219,7 +277,7 @@ HSQP_HD int rollout_segment(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w
       const bool last = tb - t <= h;
       if (last) h = tb - t;
       const double tn = last ? tb : t + h;
-      rollout_stages(ctx, dm, w, p, st.controller, true, nl, t, h, tn);
+      rollout_stages(ctx, dm, w, p, st.controller, true, nl, t, h, tn, mask);
       if (rollout_nonfinite(ctx, w, &w.k[0][0], 1, 7, nl)) return HSQP_ROLLOUT_NONFINITE;
       const double err = rollout_error(ctx, w, nl, h, st.abs_tol, st.rel_tol);
       if (!(err <= 1.0)) {
@@ -242,7 +300,7 @@ HSQP_HD int rollout_segment(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w
     } else {
       const bool last = tb - t <= h;
       const double hs = last ? tb - t : h, tn = last ? tb : t + hs;
-      rollout_stages(ctx, dm, w, p, st.controller, false, nl, t, hs, tn);
+      rollout_stages(ctx, dm, w, p, st.controller, false, nl, t, hs, tn, mask);
       if (rollout_nonfinite(ctx, w, &w.k[0][0], 0, 4, nl)) return HSQP_ROLLOUT_NONFINITE;
       WG_FOR(ctx, i, nl) w.x[i] = w.x[i] + hs / 6.0 * (w.k[0][i] + 2.0 * w.k[1][i] + 2.0 * w.k[2][i] + w.k[3][i]);
       WG_SYNC(ctx);
@@ -253,25 +311,31 @@ HSQP_HD int rollout_segment(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w
   return HSQP_ROLLOUT_OK;
 }
 
-// the first event stamp of the grid strictly inside (t, tb), else tb (stamps summed in the order of policy_segment_grid)
-HSQP_HD double rollout_next_event(const RolloutPolicy& p, double t, double tb) {
-  if (!p.dts) return tb;
-  double tk = 0.0;
-  for (int k = 0; k < p.N; ++k) {
-    if (p.dts[k] == 0.0 && tk > t && tk < tb) return tk;
-    tk += p.dts[k];
+// the first break point strictly inside (t, tb), else tb: an event stamp of the grid (stamps summed in the order of policy_segment_grid) or an
+// edge of one of the instance's pushes
+HSQP_HD double rollout_next_event(const RolloutPolicy& p, const PushSet& ps, double t, double tb) {
+  double te = tb;
+  if (p.dts) {
+    double tk = 0.0;
+    for (int k = 0; k < p.N; ++k) {
+      if (p.dts[k] == 0.0 && tk > t && tk < tb) { te = tk; break; }
+      tk += p.dts[k];
+    }
   }
-  return tb;
+  return ps.n ? push_next_edge(ps, t, te) : te;
 }
 
 // sample j of n: s0 + duration (j + 1) / n, the last one s0 + duration exactly
 HSQP_HD double rollout_sample_time(double s0, double duration, int j, int n) { return j + 1 == n ? s0 + duration : s0 + duration * (double)(j + 1) / (double)n; }
 
 // One instance: x0 at s0, n samples over duration.  xo [n][NX], uo [n][NU] (may be null); the counters are written by item 0.
+// tbl, b: the resident push table and the instance's row in it (the default: no table).
 template <class SW>
 HSQP_HD void rollout_instance(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, const hsqp_rollout_settings& st, double s0,
-                              const double* x0, double duration, int n, double* xo, double* uo, int32_t* status, int32_t* steps, int32_t* rejected) {
+                              const double* x0, double duration, int n, double* xo, double* uo, int32_t* status, int32_t* steps, int32_t* rejected,
+                              const PushTable& tbl = PushTable{nullptr, nullptr, 0, nullptr, 0}, int b = 0) {
   const int nl = p.cent ? CNX : NX;
+  push_load(ctx, tbl, b, w.push);
   rollout_topology(ctx, dm, w.sw);
   WG_FOR(ctx, i, NX) w.x[i] = i < nl ? x0[i] : 0.0;
   WG_SYNC(ctx);
@@ -285,7 +349,7 @@ HSQP_HD void rollout_instance(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>&
       int acc = 0;
       double t = ta;
       while (stat == HSQP_ROLLOUT_OK && t < tb) {
-        const double te = rollout_next_event(p, t, tb);
+        const double te = rollout_next_event(p, w.push, t, tb);
         stat = rollout_segment(ctx, dm, w, p, st, t, te, cap, acc, nacc, nrej);
         t = te;
       }

@@ -19,6 +19,7 @@
 #include "../../include/hsqp_loop.h"
 #include "../../include/hsqp_gait.h"
 #include "../../include/hsqp_episode.h"
+#include "../../include/hsqp_push.h"
 
 namespace hsqp_host {
 
@@ -156,6 +157,38 @@ class HipSqpSolver {
     x.assign(B * nSamples * HSQP_NX, 0.0); u.assign(B * nSamples * HSQP_NU, 0.0); status.assign(B, 0);
     const int rc = hsqp_rollout_policy(h_, &st, secondsAfterStart.data(), x0.data(), duration, nSamples, x.data(), u.data(), status.data(), nullptr, nullptr);
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_rollout_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** ---- external pushes on the plant (include/hsqp_push.h): pushes[b] are the pushes of instance b (at most HSQP_PUSH_MAX each).  The table stays
+   *  resident until clearPushes() or the next setPushes(); every rolloutPolicy and every loop cycle of a batch of pushes.size() instances applies
+   *  it (another batch throws).  The MPC never sees a push. */
+  void setPushes(const std::vector<std::vector<hsqp_push>>& pushes) {
+    size_t mp = 1;
+    for (const auto& p : pushes) mp = p.size() > mp ? p.size() : mp;
+    std::vector<int32_t> n(pushes.size());
+    std::vector<hsqp_push> table(pushes.size() * mp, hsqp_push{});
+    for (size_t b = 0; b < pushes.size(); ++b) {
+      n[b] = (int32_t)pushes[b].size();
+      for (size_t i = 0; i < pushes[b].size(); ++i) table[b * mp + i] = pushes[b][i];
+    }
+    const int rc = hsqp_push_set(h_, (int)pushes.size(), (int)mp, n.data(), table.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_push_set failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void clearPushes() {
+    const int rc = hsqp_push_clear(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_push_clear failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** The resident table, as setPushes takes it (throws if none is set). */
+  std::vector<std::vector<hsqp_push>> pushes() {
+    int B = 0, mp = 0;
+    int rc = hsqp_push_get(h_, &B, &mp, nullptr, nullptr);
+    std::vector<int32_t> n((size_t)(rc == HSQP_OK ? B : 0));
+    std::vector<hsqp_push> table(n.size() * (size_t)mp);
+    if (rc == HSQP_OK) rc = hsqp_push_get(h_, nullptr, nullptr, n.data(), table.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_push_get failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    std::vector<std::vector<hsqp_push>> out(n.size());
+    for (size_t b = 0; b < n.size(); ++b) out[b].assign(table.begin() + b * mp, table.begin() + b * mp + n[b]);
+    return out;
   }
 
   /** ---- the closed loop resident on the device (include/hsqp_loop.h): what ProceduralMpcMotionManager::preSolverRun's target generation, MPC_BASE::run

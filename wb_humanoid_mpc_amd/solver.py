@@ -96,6 +96,12 @@ def load_library():
     lib.hsqp_rollout_defaults.restype = None
     lib.hsqp_rollout_policy.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
     lib.hsqp_rollout_policy_device.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
+    # include/hsqp_push.h
+    _pp = C.POINTER(_abi.Push)
+    lib.hsqp_push_set.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _pp]
+    lib.hsqp_push_set_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _pp]
+    lib.hsqp_push_clear.argtypes = [C.c_void_p]
+    lib.hsqp_push_get.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _ip, _pp]
     # include/hsqp_loop.h
     _ls = C.POINTER(_abi.LoopSettings)
     lib.hsqp_set_default_joint_state.argtypes = [C.c_void_p, _dp]
@@ -494,6 +500,50 @@ class HipSqpSolver:
             if rc in (_abi.ERR_NOT_CONVERGED, _abi.ERR_NUMERIC):
                 err.result = result
             raise err
+
+    # ---- include/hsqp_push.h: per-instance external pushes on the plant of the rollout and the resident loop
+    @staticmethod
+    def pack_pushes(pushes, max_pushes=None):
+        """(n_pushes int32 [B], table (_abi.Push * max_pushes) * B, max_pushes) from a list, one entry per instance, of lists of pushes: dicts
+        (body, t_start, duration, point, force; reserved optional) or tuples in that order."""
+        B = len(pushes)
+        mp = max(1, max((len(p) for p in pushes), default=1)) if max_pushes is None else int(max_pushes)
+        n = np.array([len(p) for p in pushes], dtype=np.int32)
+        table = ((_abi.Push * mp) * max(B, 1))()
+        for b, row in enumerate(pushes):
+            for i, p in enumerate(row[:mp]):
+                if not isinstance(p, dict):
+                    p = dict(zip(("body", "t_start", "duration", "point", "force"), p))
+                e = table[b][i]
+                e.body, e.reserved = int(p["body"]), int(p.get("reserved", 0))
+                e.t_start, e.duration = float(p["t_start"]), float(p["duration"])
+                e.point[:] = [float(v) for v in p.get("point", (0.0, 0.0, 0.0))]
+                e.force[:] = [float(v) for v in p["force"]]
+        return n, table, mp
+
+    def set_pushes(self, pushes, max_pushes=None):
+        """hsqp_push_set: the resident push table, pushes[b] the pushes of instance b (pack_pushes).  It stays until clear_pushes() or the
+        next set_pushes(); every rollout and loop cycle of a problem with len(pushes) instances applies it."""
+        n, table, mp = self.pack_pushes(pushes, max_pushes)
+        self._check(self.lib.hsqp_push_set(self.h, len(pushes), mp, n.ctypes.data_as(C.POINTER(C.c_int32)), C.cast(table, C.POINTER(_abi.Push))))
+
+    def set_pushes_device(self, batch, max_pushes, n_pushes_ptr, pushes_ptr):
+        """hsqp_push_set_device: both arrays in device memory (addresses); their values are not checked."""
+        self._check(self.lib.hsqp_push_set_device(self.h, int(batch), int(max_pushes), C.cast(C.c_void_p(int(n_pushes_ptr)), C.POINTER(C.c_int32)),
+                                                  C.cast(C.c_void_p(int(pushes_ptr)), C.POINTER(_abi.Push))))
+
+    def clear_pushes(self):
+        self._check(self.lib.hsqp_push_clear(self.h))
+
+    def get_pushes(self):
+        """hsqp_push_get: the resident table as set_pushes takes it (a list per instance of dicts); HsqpError if none is set."""
+        B, mp = C.c_int(0), C.c_int(0)
+        self._check(self.lib.hsqp_push_get(self.h, C.byref(B), C.byref(mp), None, None))
+        n = np.zeros(B.value, np.int32)
+        table = ((_abi.Push * mp.value) * B.value)()
+        self._check(self.lib.hsqp_push_get(self.h, None, None, n.ctypes.data_as(C.POINTER(C.c_int32)), C.cast(table, C.POINTER(_abi.Push))))
+        return [[dict(body=int(e.body), t_start=e.t_start, duration=e.duration, point=list(e.point), force=list(e.force)) for e in table[b][:n[b]]]
+                for b in range(B.value)]
 
     # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
     def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
