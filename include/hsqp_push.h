@@ -25,6 +25,8 @@
  *     rows (commanded joint velocities) are unchanged.
  * Overlapping pushes of one instance add (in the order of the table).  What this model of a push leaves out: joint compliance (see above),
  * and contact slip — a stance foot stays where the policy's wrenches hold it, no friction limit is enforced on the plant.
+ * The compliant plant is hsqp_plant.h: with HSQP_PLANT_TORQUE set a push acts through the whole tree (the base rows and every joint between the
+ * base and the pushed body) under the joint PD law; edges, activity and break points are the ones above.
  *
  * Piecewise-constant forcing, exact restarts: the edges of every push of an instance are break points of the integration, like the event
  * stamps of the grid.  Edge arithmetic: in rollout time an edge is

@@ -8,8 +8,13 @@ Prints one JSON line with the fields of tools/closed_loop_cycle.py (no rollout s
 iteration and the rollout, and its rollout keeps no step counters).
     python tools/device_loop_cycle.py [--cycles 30] [--warmup 3] [--batch 256] [--nodes 100] [--controller feedforward|feedback]
                                       [--commands same|spread] [--gait ladder|walk] [--isolate park|reset] [--with-push NEWTONS]
+                                      [--plant flow|torque] [--kp 100] [--kd 2] [--armature 0.01] [--lookahead 0.005]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
 --with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
+--plant: the plant of the loop's rollout (include/hsqp_plant.h).  torque: full forward dynamics under the joint PD law with the given gains
+(defaults: the gains of the tests); flow: the MPC's own flow map, set explicitly.  With --plant the line also carries `rollout_probe`: after the
+timed cycles one more hsqp_rollout_policy call over the period from the loop's last state on the resident policy, timed by the wall clock
+(median of five), with its accepted / rejected step counts per instance — the rollout's share of a cycle and what the integrator spends.
 --push: a small push-recovery sweep instead of the timing.  Every instance walks under the same command; instance b is pushed sideways at the
 pelvis (the base link's origin) with b / (batch - 1) of --push-max newtons from --push-at seconds on for --push-for seconds.  Isolation is on
 (park; box: base height above 0.45 m, tilt below 0.7 rad), and the sweep runs once with the feed-forward and once with the feedback controller.
@@ -83,6 +88,24 @@ def push_sweep(args):
                       **{c: {"failed": [int(b) for b in np.nonzero(ep["n_failures"])[0]], "fail_cycle": [int(v) for v in ep["fail_cycle"]]} for c, (ep, _) in rows.items()}}))
 
 
+def rollout_probe(s, args, x_end):
+    """One rollout over the period from the loop's last state on the resident policy: wall-clock ms (median of five calls) and step counts."""
+    from wb_humanoid_mpc_amd.solver import HsqpError
+    B = len(x_end)
+    ms, r = [], None
+    for _ in range(5):
+        t_a = time.perf_counter()
+        try:
+            r = s.rollout_policy(np.zeros(B), x_end, args.period, 1, controller=args.controller)
+        except HsqpError as e:
+            r = e.result
+        ms.append(1e3 * (time.perf_counter() - t_a))
+    if r is None:
+        return None
+    return {"rollout_ms_median": round(float(np.median(ms)), 3), "steps_mean": round(float(r["steps"].mean()), 2), "steps_max": int(r["steps"].max()),
+            "rejected_mean": round(float(r["rejected"].mean()), 2), "rejected_max": int(r["rejected"].max()), "status_ok": int((r["status"] == 0).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=30)
@@ -97,6 +120,11 @@ def main():
     ap.add_argument("--isolate", default=None, choices=("park", "reset"))
     ap.add_argument("--with-push", type=float, default=None)
     ap.add_argument("--push", action="store_true")
+    ap.add_argument("--plant", default=None, choices=("flow", "torque"))
+    ap.add_argument("--kp", type=float, default=100.0)
+    ap.add_argument("--kd", type=float, default=2.0)
+    ap.add_argument("--armature", type=float, default=0.01)
+    ap.add_argument("--lookahead", type=float, default=0.005)
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -139,6 +167,8 @@ def main():
             s.loop_isolate(s.episode_settings(args.isolate))
         if args.with_push is not None:
             s.set_pushes([[dict(body=0, t_start=0.0, duration=1e6, point=(0.0, 0.0, 0.0), force=(0.0, args.with_push, 0.0))]] * B)
+        if args.plant:
+            s.set_plant(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead)
         for c in range(args.warmup + args.cycles):
             if c in changes:
                 s.loop_command(changes[c])
@@ -155,12 +185,14 @@ def main():
         rungs = np.bincount(s.gait_state()["rung"], minlength=7).tolist() if args.gait else None
         ep = s.loop_episodes() if args.isolate else None
         heights.append(x_end[:, 2].copy())
+        probe = rollout_probe(s, args, x_end) if args.plant else None
     finally:
         s.close()
     heights = np.concatenate(heights)
     q = np.percentile(cycle_ms, [25, 75])
     print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
                       "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
+                      "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None, "rollout_probe": probe,
                       "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),

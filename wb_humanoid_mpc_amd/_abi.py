@@ -171,6 +171,18 @@ class Push(C.Structure):   # hsqp_push
 # entry points of include/hsqp_push.h (tests/test_push.py checks that the library exports each of them and the binding declares it)
 PUSH_ENTRY_POINTS = ("hsqp_push_set", "hsqp_push_set_device", "hsqp_push_clear", "hsqp_push_get")
 
+# include/hsqp_plant.h
+PLANT_FLOW, PLANT_TORQUE = 0, 1
+
+
+class PlantSettings(C.Structure):   # hsqp_plant_settings
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("lookahead", C.c_double), ("kp", C.c_double * NJ), ("kd", C.c_double * NJ),
+                ("armature", C.c_double * NJ)]
+
+
+# entry points of include/hsqp_plant.h (tests/test_plant.py checks that the library exports each of them and the binding declares it)
+PLANT_ENTRY_POINTS = ("hsqp_plant_defaults", "hsqp_plant_set", "hsqp_plant_clear", "hsqp_plant_get")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

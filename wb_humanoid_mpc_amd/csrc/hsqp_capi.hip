@@ -994,6 +994,19 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restri
                    a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
 static_assert(sizeof(RolloutWS<StageWST<false>>) <= 65536 && sizeof(RolloutWS<CentWST<false>>) <= 65536, "the rollout runs without a dynamic-LDS attribute");
+// the rollout on the torque plant (include/hsqp_plant.h, csrc/hsqp_plant.h): the instantiation of its own that a handle with HSQP_PLANT_TORQUE set launches
+// instead of k_rollout<StageWST<false>>, which does not contain it
+__global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp) {
+  RolloutWS<PlantStage>& w = *reinterpret_cast<RolloutWS<PlantStage>*>(hsqp_smem);
+  const int b = blockIdx.x;
+  const Ctx ctx{(int)threadIdx.x, RO_THREADS, nullptr};
+  const RolloutPolicy p{a.ut + (size_t)b * a.N * NU, a.dts ? a.dts + (size_t)b * a.N : nullptr, a.N, a.dt, a.K ? a.K + (size_t)b * a.count * NU * NX : nullptr,
+                        a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count, 0};
+  plant_load(ctx, pp, b, a.N, w.sw.pl);
+  rollout_instance(ctx, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
+                   a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr, a.rejected ? a.rejected + b : nullptr, a.push, b);
+}
+static_assert(sizeof(RolloutWS<PlantStage>) <= 65536, "the rollout on the torque plant runs without a dynamic-LDS attribute");
 
 // ---- per-instance performance index from per-node {ne, dt*cost, dt*eq^2, dt*dyn^2} + terminal cost
 __device__ inline void perf_reduce_instance(int b, const DevModel* __restrict__ dm, const double* __restrict__ misc, int misc_stride, const double* __restrict__ x,
@@ -1116,6 +1129,9 @@ struct hsqp_handle {
   // the resident push table (include/hsqp_push.h): n_pushes [push_B] (int32, padded to 256 bytes), then pushes [push_B][push_max]; push_B == 0: no table
   DevBuf<char> d_push;
   int push_B = 0, push_max = 0;
+  // the resident plant setting (include/hsqp_plant.h): kind FLOW = none; d_plant: kp, kd, armature [23] each
+  hsqp_plant_settings plant = [] { hsqp_plant_settings p; hsqp_plant_defaults(&p); p.kind = HSQP_PLANT_FLOW; return p; }();
+  DevBuf<double> d_plant;
   bool stamps_resident = false;   // d_stamps[stamps_cur] holds the raw stamps of the resident problem (it came through hsqp_upload_reference or the loop): the pushes' clock
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
@@ -2293,7 +2309,9 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     step(hipMemcpyAsync(base + o_x0, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
   }
   const double* dts = h->uniform_grid ? nullptr : (const double*)h->d_dt;
-  HSQP_LAUNCH(k_rollout_window, dim3(1), dim3(RO_WIN_THREADS), 0, h->stream, d_s0, (int)B, duration, (const double*)h->d_dt, N, h->dt, h->uniform_grid ? 1 : 0, d_win);
+  // (the torque plant evaluates the policy up to `lookahead` past the call's last time: the gain window covers it)
+  const bool torque = h->plant.kind == HSQP_PLANT_TORQUE;
+  HSQP_LAUNCH(k_rollout_window, dim3(1), dim3(RO_WIN_THREADS), 0, h->stream, d_s0, (int)B, torque ? duration + h->plant.lookahead : duration, (const double*)h->d_dt, N, h->dt, h->uniform_grid ? 1 : 0, d_win);
   step(hipGetLastError(), "k_rollout_window");
   int win[3] = {0, 0, 0};
   step(hipMemcpyAsync(win, d_win, sizeof(win), hipMemcpyDeviceToHost, h->stream), "download window");
@@ -2318,7 +2336,9 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     pt = PushTable{reinterpret_cast<const int32_t*>(h->d_push.p), reinterpret_cast<const hsqp_push*>(h->d_push.p + push_n_bytes(h->push_B)), h->push_max,
                    h->stamps_resident ? (const double*)h->d_stamps[h->stamps_cur] : nullptr, N + 1};
   const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, d_status, d_steps, d_rej, pt};
-  if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
+  if (torque)
+    HSQP_LAUNCH(k_rollout_plant, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, PlantParams{h->d_plant.p, h->plant.lookahead, (const double*)h->d_xnew});
+  else if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
   else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
   step(hipGetLastError(), "k_rollout");
   std::vector<int32_t> hs(B);
@@ -2413,7 +2433,46 @@ int hsqp_push_get(hsqp_handle* h, int* batch, int* max_pushes, int32_t* n_pushes
   return HSQP_OK;
 }
 
-// ---- velocity-command targets and the resident closed loop (include/hsqp_loop.h, csrc/hsqp_loop.h)
+// ---- the plant of the rollout (include/hsqp_plant.h, csrc/hsqp_plant.h): the resident setting
+void hsqp_plant_defaults(hsqp_plant_settings* s) {
+  if (!s) return;
+  s->kind = HSQP_PLANT_TORQUE; s->reserved = 0;
+  s->lookahead = 0.005;
+  for (int j = 0; j < NJ; ++j) { s->kp[j] = 1200.0; s->kd[j] = 10.0; s->armature[j] = 0.0; }
+}
+int hsqp_plant_set(hsqp_handle* h, const hsqp_plant_settings* s) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const auto bad = [&](const char* what) { h->err = std::string("hsqp_plant_set: ") + what; return HSQP_ERR_BAD_ARG; };
+  if (!s) return bad("null settings");
+  if (h->hdm.formulation != HSQP_FORM_WB) return bad("whole-body handles only (the torque plant is the whole-body tree's forward dynamics)");
+  if (s->kind != HSQP_PLANT_FLOW && s->kind != HSQP_PLANT_TORQUE) return bad("unknown kind");
+  if (s->reserved != 0) return bad("reserved must be 0");
+  const auto ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
+  if (!ok(s->lookahead)) return bad("negative or non-finite lookahead");
+  for (int j = 0; j < NJ; ++j)
+    if (!ok(s->kp[j]) || !ok(s->kd[j]) || !ok(s->armature[j])) return bad(("joint " + std::to_string(j) + ": negative or non-finite kp, kd or armature").c_str());
+  HCHECK(hipSetDevice(h->device));
+  double g[3 * NJ];
+  for (int j = 0; j < NJ; ++j) { g[j] = s->kp[j]; g[NJ + j] = s->kd[j]; g[2 * NJ + j] = s->armature[j]; }
+  DEV_ENSURE(h->d_plant, sizeof(g), "plant gains");
+  HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the gains that are replaced)
+  HCHECK(hipMemcpy(h->d_plant.p, g, sizeof(g), hipMemcpyHostToDevice));
+  h->plant = *s;
+  return HSQP_OK;
+}
+int hsqp_plant_clear(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  hsqp_plant_defaults(&h->plant);
+  h->plant.kind = HSQP_PLANT_FLOW;
+  return HSQP_OK;
+}
+int hsqp_plant_get(hsqp_handle* h, hsqp_plant_settings* s) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (!s) { h->err = "hsqp_plant_get: null settings"; return HSQP_ERR_BAD_ARG; }
+  *s = h->plant;
+  return HSQP_OK;
+}
+
 static int loop_bad(hsqp_handle* h, const char* who, const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; }
 // whole-body handle with a default joint state
 static int loop_handle_ok(hsqp_handle* h, const char* who) {

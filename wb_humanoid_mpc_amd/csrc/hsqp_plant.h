@@ -1,0 +1,166 @@
+// Torque-level plant of the rollout (include/hsqp_plant.h): full forward dynamics of the whole-body tree under the joint PD law of the
+// reference's WBMpcMrtJointController::computeJointControlAction (humanoid_wb_mpc/src/mrt/WBMpcMrtJointController.cpp:125-194),
+//     (M(q) + diag(0_6, armature)) vd = [0; tau] + sum_feet J^T W - nle(q, v) + sum_pushes J_P^T f.
+// Everything is formed from what stage_eval<false> leaves in the stage workspace at (q, v, qdd_j = 0, W): the spatial inertias In[i] and the
+// bias forces f[i] of every body about the base origin O (gravity trick, zero base acceleration), the motion axes S, the contact wrenches Fx.
+//   composites:  I^c_b, f^c_b = sums over the depth-first range [b, b + sub_b) of the subtree of b
+//   mass matrix: M_rc = S_r . (I^c_c S_c) for r an ancestor-or-self of c (coordinates 0..2: unit translations, 3..5: the euler axes — the
+//                floating base is the chain x, y, z, rz, ry', rx'', so every base coordinate carries the total inertia), mirrored, else 0
+//   bias:        nle_c = S_c . f^c_c;  the generalised force of a wrench {moment, force} about O on a body below c is S_c . wrench
+//   solve:       Cholesky of the system bordered by the right-hand side as row 29 (the forward substitution rides on the trailing updates),
+//                then one back substitution.  A pivot that is not positive makes the solution non-finite (HSQP_ROLLOUT_NONFINITE).
+// Phase style of hsqp_common.h: the same source builds for the host with a one-lane context (tests/plant/plant_emu.cpp).
+#pragma once
+#include "hsqp_policy.h"
+#include "hsqp_push.h"
+#include "../../include/hsqp_plant.h"
+
+namespace hsqp {
+
+constexpr int PL_N = NV + 1;      // the bordered system: row NV is the right-hand side
+constexpr int PL_LD = PL_N + 1;   // odd leading dimension
+
+// The resident plant setting as the kernel sees it (gains null: HSQP_PLANT_FLOW, nothing else is read)
+struct PlantParams {
+  const double* gains;    // kp [NJ], kd [NJ], armature [NJ]
+  double lookahead;
+  const double* xt;       // [B][N + 1][NX] nominal states of the resident policy (the state hsqp_evaluate_policy interpolates)
+};
+
+struct PlantWS {
+  const double* xt;                 // nominal states of THIS instance
+  double lookahead;
+  double kp[NJ], kd[NJ], arm[NJ];
+  double xp[NX];                    // policy state at s + lookahead
+  double tau[NJ];                   // feed-forward torques, then the joint law's torques
+  double Ic[NB][10], fc[NB][6];     // composites of In / f over the subtrees
+  double Fc[NV][6];                 // I^c_c S_c per coordinate
+  double A[PL_N][PL_LD];            // the bordered system, then its Cholesky factor (lower)
+  double l[PL_N];                   // the scaled pivot column of one elimination step
+  double dinv[NV];                  // reciprocals of the factor's diagonal
+  double vd[NV];                    // the accelerations
+};
+
+// The stage workspace of the torque plant: the flow map's, and the plant's own
+struct PlantStage {
+  StageWST<false> st;
+  PlantWS pl;
+};
+
+// instance b of the setting into the workspace
+HSQP_HD void plant_load(const Ctx& ctx, const PlantParams& pp, int b, int N, PlantWS& pl) {
+  WG_FOR(ctx, i, 3 * NJ + 1) {
+    if (i == 3 * NJ) { pl.xt = pp.xt + (size_t)b * (N + 1) * NX; pl.lookahead = pp.lookahead; continue; }
+    (i < NJ ? pl.kp[i] : (i < 2 * NJ ? pl.kd[i - NJ] : pl.arm[i - 2 * NJ])) = pp.gains[i];
+  }
+  WG_SYNC(ctx);
+}
+
+// (q, v, qdd_j, W) of one evaluation into the stage workspace
+HSQP_HD void plant_inputs(const Ctx& ctx, StageWST<false>& ws, const double* x, const double* u, bool zero_qdd) {
+  WG_FOR(ctx, i, NV + NV + NJ + 12) {
+    if (i < NV) ws.q[i] = x[i];
+    else if (i < 2 * NV) ws.v[i - NV] = x[i];
+    else if (i < 2 * NV + NJ) ws.qddj[i - 2 * NV] = zero_qdd ? 0.0 : u[12 + i - 2 * NV];
+    else ws.W[i - 2 * NV - NJ] = u[i - 2 * NV - NJ];
+  }
+  WG_SYNC(ctx);
+}
+
+// motion axis of generalised coordinate c
+HSQP_HD void plant_axis(const StageWST<false>& ws, int c, double* s) {
+  if (c < 3) { for (int k = 0; k < 6; ++k) s[k] = k == 3 + c ? 1.0 : 0.0; }
+  else { for (int k = 0; k < 6; ++k) s[k] = ws.S[c - 3][k]; }
+}
+// the body whose subtree coordinate c moves, and one past the last body of that subtree
+HSQP_HD int plant_body(int c) { return c < 6 ? 0 : c - 5; }
+HSQP_HD int plant_end(const StageWST<false>& ws, int c) { return c < 6 ? NB : (c - 5) + (int)ws.sub[c - 5]; }
+
+// vd [NV] (into pl.vd) of the plant at the state and the contact wrenches stage_eval<false> has just been run on (qdd_j = 0), under the joint
+// torques pl.tau and the pushes `mask` of ps (0: none).  Ends with a barrier.
+HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, PlantWS& pl, PushSet& ps, unsigned mask) {
+  // ---- composites over the subtrees; the wrench {P x f, f} about O of every active push
+  WG_FOR(ctx, it, NB * 16 + HSQP_PUSH_MAX) {
+    if (it >= NB * 16) {
+      const int i = it - NB * 16;
+      if (!((mask >> i) & 1u)) continue;
+      const int b = ps.body[i];
+      double P[3], mom[3];
+      m3_mulv(ws.R[b], ps.point[i], P);
+      for (int k = 0; k < 3; ++k) P[k] += ws.r[b][k];
+      v3_cross(P, ps.force[i], mom);
+      for (int k = 0; k < 3; ++k) { ps.wr[i][k] = mom[k]; ps.wr[i][3 + k] = ps.force[i][k]; }
+      continue;
+    }
+    const int b = it / 16, e = it % 16, end = b + (int)ws.sub[b];
+    double s = 0.0;
+    if (e < 10) { for (int i = b; i < end; ++i) s += ws.In[i][e]; pl.Ic[b][e] = s; }
+    else { for (int i = b; i < end; ++i) s += ws.f[i][e - 10]; pl.fc[b][e - 10] = s; }
+  }
+  WG_SYNC(ctx);
+  // ---- per coordinate: I^c S, and the right-hand side  tau - S . (f^c - contact wrenches below - push wrenches below)  into the border row
+  WG_FOR(ctx, c, NV + 1) {
+    if (c == NV) { pl.A[NV][NV] = 0.0; continue; }   // (the border's corner: carried through the updates, never used)
+    const int b = plant_body(c), end = plant_end(ws, c);
+    double Sx[6], F[6];
+    plant_axis(ws, c, Sx);
+    inertia_apply(pl.Ic[b], Sx, pl.Fc[c]);
+    for (int k = 0; k < 6; ++k) F[k] = pl.fc[b][k];
+    for (int f = 0; f < 2; ++f) {
+      const int cb = dm.contact_body[f];
+      if (cb >= b && cb < end) for (int k = 0; k < 6; ++k) F[k] -= ws.Fx[f][k];
+    }
+    for (int i = 0; i < HSQP_PUSH_MAX; ++i) {
+      if (!((mask >> i) & 1u)) continue;
+      const int pb = ps.body[i];
+      if (pb >= b && pb < end) for (int k = 0; k < 6; ++k) F[k] -= ps.wr[i][k];
+    }
+    double s = 0.0;
+    for (int k = 0; k < 6; ++k) s += Sx[k] * F[k];
+    pl.A[NV][c] = (c < 6 ? 0.0 : pl.tau[c - 6]) - s;
+  }
+  WG_SYNC(ctx);
+  // ---- mass matrix: both triangles from the same expression (exactly symmetric), the armature on the joint diagonal
+  WG_FOR(ctx, it, NV * NV) {
+    const int i = it / NV, j = it % NV, r = i < j ? i : j, c = i < j ? j : i;
+    const int bc = plant_body(c);
+    double m = 0.0;
+    if (r < 6 || (bc >= plant_body(r) && bc < plant_end(ws, r))) {
+      double Sx[6];
+      plant_axis(ws, r, Sx);
+      for (int k = 0; k < 6; ++k) m += Sx[k] * pl.Fc[c][k];
+    }
+    if (i == j && i >= 6) m += pl.arm[i - 6];
+    pl.A[i][j] = m;
+  }
+  WG_SYNC(ctx);
+  // ---- Cholesky of the leading NV x NV block, the border row eliminated along: after step k the border holds y_k = (L^-1 rhs)_k
+  for (int k = 0; k < NV; ++k) {
+    WG_FOR(ctx, i, PL_N - k) {
+      const double piv = pl.A[k][k];
+      const double inv = piv > 0.0 ? inv_sqrt(piv) : __builtin_nan("");
+      pl.l[k + i] = pl.A[k + i][k] * inv;
+      if (i == 0) pl.dinv[k] = inv;
+    }
+    WG_SYNC(ctx);
+    const int n = PL_N - k;   // rows k .. NV: item (i, 0) stores the column, items (i, j), 1 <= j <= i, update the trailing block
+    WG_FOR(ctx, it, n * n) {
+      const int i = it / n, j = it % n;
+      if (j > i) continue;
+      if (j == 0) pl.A[k + i][k] = pl.l[k + i];
+      else pl.A[k + i][k + j] -= pl.l[k + i] * pl.l[k + j];
+    }
+    WG_SYNC(ctx);
+  }
+  // ---- back substitution L^T vd = y
+  WG_FOR(ctx, it, 1) {
+    for (int k = NV - 1; k >= 0; --k) {
+      double s = pl.A[NV][k];
+      for (int i = k + 1; i < NV; ++i) s -= pl.A[i][k] * pl.vd[i];
+      pl.vd[k] = s * pl.dinv[k];
+    }
+  }
+  WG_SYNC(ctx);
+}
+
+}  // namespace hsqp

@@ -13,12 +13,16 @@
 //                ones behind the flow evaluation of the rollout (no other user of stage_eval<false> / cent_lane_flow sees them), their edges
 //                are break points beside the grid's events, and a segment's activity is fixed at its start.  An instance without pushes
 //                never enters that code.
+//   plant:       with the torque plant set (include/hsqp_plant.h, hsqp_plant.h) a second instantiation of the kernel — workspace
+//                RolloutWS<PlantStage> — replaces the flow evaluation by the compliant plant: full forward dynamics under the joint PD law,
+//                the pushes acting through the whole tree.  The instantiations above do not contain it.
 // The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp, tests/push/push_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
 #include "hsqp_cent_lq.h"
 #include "hsqp_feedback.h"
 #include "hsqp_push.h"
+#include "hsqp_plant.h"
 #include "../../include/hsqp_rollout.h"
 
 namespace hsqp {
@@ -55,6 +59,7 @@ HSQP_HD bool ro_finite(double v) { return v - v == 0.0; }
 // ---- flow maps: xdot [NX] of (x, u) through the workspace.  Entries of the centroidal padding are zero.
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws) { stage_topology(ctx, dm, ws); }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, CentWST<false>& ws) { cent_ws_topology(ctx, dm, ws); }
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantStage& ws) { stage_topology(ctx, dm, ws.st); }
 
 HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, const double* x, const double* u, double* xdot) {
   WG_FOR(ctx, i, NV + NV + NJ + 12) {
@@ -167,6 +172,28 @@ HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, 
   rollout_control(ctx, p, controller, s, x, w.u);
   rollout_flow(ctx, dm, w.sw, x, w.u, k);
   if (mask) rollout_push(ctx, dm, w.sw, w.push, mask, k);
+}
+
+// The same with the torque plant (include/hsqp_plant.h; the workspace's plant setting was loaded by plant_load): the policy (x_p, u_p) at
+// s + lookahead — feedback: u_p = uff + K x at the measured plant state, x_p the interpolated nominal state —, tau_ff = joint_torques at
+// (x_p, u_p), the joint law, then forward dynamics at the plant's own state under the policy's contact wrenches and the pushes `mask`.
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantStage>& w, const RolloutPolicy& p, int controller, double s, const double* x,
+                          double* k, unsigned mask) {
+  PlantWS& pl = w.sw.pl;
+  const double sl = s + pl.lookahead;
+  rollout_control(ctx, p, controller, sl, x, w.u);
+  const PolicySegment g = p.dts ? policy_segment_grid(p.N, p.dts, sl) : policy_segment_uniform(p.N, p.dt, sl);
+  WG_FOR(ctx, i, NX) pl.xp[i] = (1.0 - g.ax) * pl.xt[(size_t)g.kx * NX + i] + g.ax * pl.xt[(size_t)(g.kx + 1) * NX + i];
+  WG_SYNC(ctx);
+  plant_inputs(ctx, w.sw.st, pl.xp, w.u, false);
+  stage_eval<false>(ctx, dm, w.sw.st);
+  joint_torques(ctx, dm, w.sw.st, pl.tau);
+  WG_FOR(ctx, j, NJ) pl.tau[j] = (pl.tau[j] + pl.kp[j] * (pl.xp[6 + j] - x[6 + j])) + pl.kd[j] * (pl.xp[NV + 6 + j] - x[NV + 6 + j]);
+  plant_inputs(ctx, w.sw.st, x, w.u, true);   // (its barrier also closes the joint law)
+  stage_eval<false>(ctx, dm, w.sw.st);
+  plant_forward_dynamics(ctx, dm, w.sw.st, pl, w.push, mask);
+  WG_FOR(ctx, i, NX) k[i] = i < NV ? x[NV + i] : pl.vd[i - NV];
+  WG_SYNC(ctx);
 }
 
 // whether any of the first n entries of rows r0 .. r1 - 1 of v (row stride NX) is not finite: a workgroup reduction, uniform

@@ -20,6 +20,7 @@
 #include "../../include/hsqp_gait.h"
 #include "../../include/hsqp_episode.h"
 #include "../../include/hsqp_push.h"
+#include "../../include/hsqp_plant.h"
 
 namespace hsqp_host {
 
@@ -189,6 +190,24 @@ class HipSqpSolver {
     std::vector<std::vector<hsqp_push>> out(n.size());
     for (size_t b = 0; b < n.size(); ++b) out[b].assign(table.begin() + b * mp, table.begin() + b * mp + n[b]);
     return out;
+  }
+
+  /** ---- the plant of the rollout and the resident loop (include/hsqp_plant.h).  setPlant with kind HSQP_PLANT_TORQUE (hsqp_plant_defaults: the
+   *  reference's lookahead and gains, no armature) makes every rolloutPolicy and every loop cycle integrate full forward dynamics under the
+   *  joint PD law; clearPlant goes back to the MPC's own flow map.  The setting stays resident; the MPC never sees it. */
+  void setPlant(const hsqp_plant_settings& settings) {
+    const int rc = hsqp_plant_set(h_, &settings);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_plant_set failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void clearPlant() {
+    const int rc = hsqp_plant_clear(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_plant_clear failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  hsqp_plant_settings plant() {
+    hsqp_plant_settings s;
+    const int rc = hsqp_plant_get(h_, &s);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_plant_get failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return s;
   }
 
   /** ---- the closed loop resident on the device (include/hsqp_loop.h): what ProceduralMpcMotionManager::preSolverRun's target generation, MPC_BASE::run

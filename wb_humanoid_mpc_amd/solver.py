@@ -102,6 +102,13 @@ def load_library():
     lib.hsqp_push_set_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _pp]
     lib.hsqp_push_clear.argtypes = [C.c_void_p]
     lib.hsqp_push_get.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _ip, _pp]
+    # include/hsqp_plant.h
+    _pl = C.POINTER(_abi.PlantSettings)
+    lib.hsqp_plant_defaults.argtypes = [_pl]
+    lib.hsqp_plant_defaults.restype = None
+    lib.hsqp_plant_set.argtypes = [C.c_void_p, _pl]
+    lib.hsqp_plant_clear.argtypes = [C.c_void_p]
+    lib.hsqp_plant_get.argtypes = [C.c_void_p, _pl]
     # include/hsqp_loop.h
     _ls = C.POINTER(_abi.LoopSettings)
     lib.hsqp_set_default_joint_state.argtypes = [C.c_void_p, _dp]
@@ -544,6 +551,37 @@ class HipSqpSolver:
         self._check(self.lib.hsqp_push_get(self.h, None, None, n.ctypes.data_as(C.POINTER(C.c_int32)), C.cast(table, C.POINTER(_abi.Push))))
         return [[dict(body=int(e.body), t_start=e.t_start, duration=e.duration, point=list(e.point), force=list(e.force)) for e in table[b][:n[b]]]
                 for b in range(B.value)]
+
+    # ---- include/hsqp_plant.h: the plant of the rollout and the resident loop
+    def plant_settings(self, kind="torque", kp=None, kd=None, armature=None, lookahead=None, reserved=0):
+        """hsqp_plant_defaults with the given fields replaced (kp, kd, armature: a scalar for every joint or 23 values)."""
+        st = _abi.PlantSettings()
+        self.lib.hsqp_plant_defaults(C.byref(st))
+        st.kind = {"flow": _abi.PLANT_FLOW, "torque": _abi.PLANT_TORQUE}.get(kind, kind)
+        st.reserved = int(reserved)
+        if lookahead is not None:
+            st.lookahead = float(lookahead)
+        for name, v in (("kp", kp), ("kd", kd), ("armature", armature)):
+            if v is not None:
+                getattr(st, name)[:] = [float(e) for e in np.broadcast_to(np.asarray(v, dtype=float), (_abi.NJ,))]
+        return st
+
+    def set_plant(self, kind="torque", kp=None, kd=None, armature=None, lookahead=None):
+        """hsqp_plant_set: the resident plant of every rollout and loop cycle of this handle.  kind "torque": full forward dynamics under the joint
+        law tau = tau_ff + kp (q_p - q) + kd (v_p - v) with the policy evaluated `lookahead` seconds ahead; "flow": the MPC's own flow map.
+        It stays until clear_plant() or the next set_plant()."""
+        st = self.plant_settings(kind, kp, kd, armature, lookahead)
+        self._check(self.lib.hsqp_plant_set(self.h, C.byref(st)))
+
+    def clear_plant(self):
+        self._check(self.lib.hsqp_plant_clear(self.h))
+
+    def get_plant(self):
+        """hsqp_plant_get: dict(kind "flow" / "torque", lookahead, kp [23], kd [23], armature [23])."""
+        st = _abi.PlantSettings()
+        self._check(self.lib.hsqp_plant_get(self.h, C.byref(st)))
+        return dict(kind="torque" if st.kind == _abi.PLANT_TORQUE else "flow", lookahead=st.lookahead, kp=np.array(st.kp[:]), kd=np.array(st.kd[:]),
+                    armature=np.array(st.armature[:]))
 
     # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
     def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
