@@ -230,7 +230,60 @@ def test_the_host_starts_new_episodes_on_chosen_instances(s, model, gait):
         assert_rows_equal(got_state, fresh_state, ids)
 
 
-# ---------------------------------------------------------------------------------------------- 6. bad arguments
+# ---------------------------------------------------------------------------------------------- 6. buffers laid out a second time
+def test_a_restart_on_more_instances_equals_a_fresh_handle(s, model):
+    """One handle, the resident gait: a loop on 2 instances, isolated, 2 cycles; then a loop on all B instances, isolated (the loop's, the gait's and
+    the episodes' buffers are outgrown and laid out again: loop_layout, gait_layout, episode_layout of csrc/hsqp_capi.hip), 2 cycles, a host reset
+    of instances [3, 0] with new states and commands, 2 more cycles.  Everything equals, bit for bit, a fresh handle taken through the B-instance
+    part alone.
+    Both handles lay their buffers out through the same function, so a request staging that lay on x_reset or on the command in use would be the
+    same mistake on both.  Two checks therefore do not compare handles: the instances the request does not name equal a run without the request (a
+    staging on the command in use leaves new_cmd[1] as instance 1's command), and at the end instance 1 restarts from its x_reset (a staging on
+    x_reset leaves new_x[1] there)."""
+    case = loop_case(model, batch=B)
+    rng = np.random.default_rng(11)
+    moved, rest = np.array([3, 0], np.int32), np.array([1, 2, 4])
+    new_x = np.tile(model.initial_state, (2, 1))
+    new_x[:, 6:6 + _abi.NJ] += 0.01 * rng.standard_normal((2, _abi.NJ))
+    new_cmd = np.array([[0.2, -0.05, 0.78, 0.1], [0.1, 0.0, 0.79, -0.15]])
+
+    def whole_batch_part(h):
+        start(h, model, case, True)
+        h.loop_isolate(h.episode_settings("park"))
+        first = h.loop_run(2)
+        h.loop_reset(moved, x0=new_x, v_cmd=new_cmd)
+        last = h.loop_run(2)
+        assert first["cycles_done"] == 2 and last["cycles_done"] == 2 and np.isfinite(last["x"]).all()
+        return dict(state=snapshot(h, True), ep=h.loop_episodes(), x=last["x"], u=last["u"])
+
+    start(s, model, case, True, rows=slice(0, 2))
+    s.loop_isolate(s.episode_settings("park"))
+    assert s.loop_run(2)["cycles_done"] == 2
+    got = whole_batch_part(s)
+    fresh = HipSqpSolver(model, max_nodes=N, max_batch=B, linesearch=True, riccati="serial")
+    try:
+        want = whole_batch_part(fresh)
+        start(fresh, model, case, True)                          # the same four cycles without the request
+        fresh.loop_isolate(fresh.episode_settings("park"))
+        plain = fresh.loop_run(4)
+        plain_state = snapshot(fresh, True)
+    finally:
+        fresh.close()
+    assert_rows_equal(got["state"], want["state"], slice(None))
+    assert sorted(got["ep"]) == ["cause", "fail_cycle", "n_episodes", "n_failures", "state"]
+    for k in want["ep"]:
+        assert np.array_equal(got["ep"][k], want["ep"][k]), k
+    assert np.array_equal(got["x"], want["x"]) and np.array_equal(got["u"], want["u"])
+    assert (got["ep"]["state"] == ALIVE).all() and list(got["ep"]["n_episodes"]) == [2, 1, 1, 2, 1]
+    # the instances the request does not name
+    assert np.array_equal(got["x"][:, rest], plain["x"][2:][:, rest]) and np.array_equal(got["u"][:, rest], plain["u"][2:][:, rest])
+    assert_rows_equal(got["state"], plain_state, rest, rest)
+    # x_reset is still the start of the whole-batch loop
+    s.loop_reset([1])
+    assert np.array_equal(s.loop_state()[1][1], case["x0"][1])
+
+
+# ---------------------------------------------------------------------------------------------- 7. bad arguments
 def test_bad_arguments(s, model, cmodel):
     case = loop_case(model, batch=B)
     lib = s.lib

@@ -30,6 +30,7 @@
 #include "hsqp_segment.h"
 #include "hsqp_lqv.h"
 #include "hsqp_lql.h"
+#include "hsqp_carve.h"
 
 using namespace hsqp;
 
@@ -1059,6 +1060,15 @@ struct DevBuf {
   operator T*() const { return p; }
 };
 
+// the gate block of a handle for max_batch instances (d_kkt, h_gate): kkt [2 per instance] | |g|_inf | flags of the scan kernels (bad pivot, rank-deficient D,
+// failed Lam) of the current attempt: one memset, one read-back for the scan's gate.  A null block: the sizing pass.
+// (the block's own packing, which the kernels index, not Carve::take: nothing inside it is 256-byte aligned)
+struct GateView { double* kkt; double* ginf; int* flags; size_t bytes; };
+static GateView gate_view(double* block, size_t max_batch) {
+  double* end = block ? block + 3 * max_batch : nullptr;
+  return {block, block ? block + 2 * max_batch : nullptr, reinterpret_cast<int*>(end), max_batch * 3 * 8 + ((max_batch * sizeof(int) + 7) / 8) * 8};
+}
+
 struct hsqp_handle {
   hsqp_model_desc md;
   hsqp_settings st;
@@ -1077,7 +1087,7 @@ struct hsqp_handle {
   DevBuf<double> d_dx, d_du, d_ut, d_xnew, d_unew;
   DevBuf<double> d_fj;            // [B][N][NJ] rows 12 .. 34 of Px dx + Pu ut as the factored roll-out forms them (k_step then reads the wrench rows of Px / Pu only)
   DevBuf<double> d_misc, d_kkt;
-  double* d_ginf = nullptr;       // (inside d_kkt)
+  GateView gate = {};             // d_kkt's parts (gate_view)
   DevBuf<double> d_dt;            // [B][N] length of every interval (uniform grids: filled with dt)
   std::vector<double> h_dt;       // host copy (debug reads), empty for device-resident uploads
   bool uniform_grid = true, has_events = false;
@@ -1086,7 +1096,7 @@ struct hsqp_handle {
   double grid_dt = 0.0;
   DevBuf<double> d_vf;            // [B][N+1][VF_SIZE] value function of the last Riccati sweep (allocated when a KKT check is first asked for)
   DevBuf<double> d_vf2;           // scan path: value functions of the refinement pass (the KKT check then reads these)
-  double* h_gate = nullptr;       // pinned host copy of the gate block [kkt | |g|_inf | scan flags]
+  double* h_gate = nullptr;       // pinned host copy of the gate block
   long long scan_fallbacks = 0;   // iterations whose scan result failed the KKT gate and were redone with the serial recursion
   DevBuf<double> d_acl;           // scan path: closed loop [B][N][ACL_SIZE] of every stage for the roll-out (allocated when the scan is first used)
   // segmented sweep (allocated when first used): gains of the J = 0 recursions, (L^-1)^T of every stage, (J, s) at the segment starts, zeros
@@ -1108,7 +1118,6 @@ struct hsqp_handle {
   bool value_quad = false;                    // whole-body value pass on quads of lanes (hsqp_lqv.h): the tree has at most four limbs (HSQP_VALUE_PHASE_FORM in the environment at hsqp_create: the phase form, for A/B runs)
   DevBuf<hsqp_perf> d_perf_before, d_perf_after;
   DevBuf<int> d_status;
-  int* d_scanst = nullptr;   // flags of the scan kernels (bad pivot, rank-deficient D, failed Lam) of the current attempt: part of the gate, behind d_ginf
   DevBuf<double> d_stepinfo;      // [B][N][4] per-node {armijo, |dx|^2, |du|^2}
   DevBuf<LsState> d_ls;
   DevBuf<int> d_counts;
@@ -1116,7 +1125,7 @@ struct hsqp_handle {
   std::vector<LsState> h_ls;                  // host copies for HSQP_ITER_UNTIL_CONVERGED (reused across iterations and calls)
   std::vector<hsqp_perf> h_perf_before;
   DevBuf<double> d_el[2];         // scan elements (allocated when the parallel-in-time sweep is first used)
-  DevBuf<char> d_stage;           // staging area for the small per-call inputs (reference, policy queries; 256-byte aligned carving by the callers)
+  DevBuf<char> d_stage;           // staging area for the small per-call inputs (reference, policy queries: ref_stage_layout, policy_stage_layout)
   bool ls_ran = false;
   DevBuf<long long> d_prof;       // [4][128] phase-profile ticks (k_lq<true>, k_project, k_riccati, k_lq<false>)
   int B = 0, N = 0;
@@ -1139,7 +1148,7 @@ struct hsqp_handle {
   DevBuf<double> d_stamps[2];
   int stamps_cur = 0;
   bool have_stamps = false;
-  // the resident closed loop (include/hsqp_loop.h): settings, where it stands, and its buffers carved from d_loop
+  // the resident closed loop (include/hsqp_loop.h): settings, where it stands, and its arrays in d_loop (loop_layout)
   struct Loop {
     bool started = false, have_cycle = false;   // have_cycle: a cycle has completed since hsqp_loop_start (the next one shifts)
     hsqp_loop_settings st;
@@ -1150,13 +1159,14 @@ struct hsqp_handle {
     double* v_cmd = nullptr; double* v_filt = nullptr; double* x = nullptr; double* xs = nullptr; double* us = nullptr;
     bool gait = false;                          // started through hsqp_loop_start_gait: ne / seq / ev are written by k_gait_update in every cycle
     int cycle = 0;                              // cycles completed since hsqp_loop_start
-    // failure isolation (include/hsqp_episode.h): off after every start; the episode arrays, x_reset [B][58] and the command in use [B][4], carved from d_episode
+    // failure isolation (include/hsqp_episode.h): off after every start; the episode arrays, x_reset [B][58], the command in use [B][4] and a reset request's staging in d_episode (episode_layout)
     bool isolate = false;
     hsqp_episode_settings ep_st;
     EpisodeState ep = {};
     double* x_reset = nullptr; double* v_use = nullptr;
+    int* req_ids = nullptr; double* req_x0 = nullptr; double* req_v = nullptr;
   } loop;
-  // the resident gait state (include/hsqp_gait.h): two copies carved from d_gait, s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
+  // the resident gait state (include/hsqp_gait.h): two copies in d_gait (gait_layout), s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
   struct Gait {
     bool ready = false;
     hsqp_gait_settings st;
@@ -1191,8 +1201,6 @@ static int dev_ensure(hsqp_handle* h, DevBuf<T>& buf, size_t bytes, const char* 
 }
 #define DEV_ENSURE(buf, bytes, what) do { const int rc_ = dev_ensure(h, (buf), (bytes), (what)); if (rc_ != HSQP_OK) return rc_; } while (0)
 
-// the gate block [kkt (2 per instance) | |g|_inf | flags of the scan kernels] of a handle for max_batch instances: d_kkt, h_gate
-static size_t gate_block_bytes(size_t max_batch) { return max_batch * 3 * 8 + ((max_batch * sizeof(int) + 7) / 8) * 8; }
 // [max_batch][max_nodes + 1][VF_SIZE]: d_vf, d_vf2
 static size_t vf_bytes(const hsqp_handle* h) { return (size_t)h->st.max_batch * (h->st.max_nodes + 1) * VF_SIZE * 8; }
 
@@ -1205,7 +1213,65 @@ static size_t vf_bytes(const hsqp_handle* h) { return (size_t)h->st.max_batch * 
     }                                                                                                  \
   } while (0)
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+// ---- the layouts of the handle's carved buffers (hsqp_carve.h).  Each states its buffer's regions once, in order, and tells the bytes they take; a
+// caller runs it on a sizing cursor (Carve{}: null pointers, the bytes go to DEV_ENSURE) and again on the buffer.
+// d_stage, hsqp_upload_reference: the compact reference (a few KB per instance)
+struct RefStage { int* ne; int* seq; int* bad; double* ev; double* tt; double* ts; double* nt; size_t bytes; };
+static RefStage ref_stage_layout(Carve c, size_t B, size_t N, size_t E, size_t K, bool node_times) {
+  return {c.take<int>(B), c.take<int>(B * (E + 1)), c.take<int>(1), c.take<double>(B * E), c.take<double>(B * K), c.take<double>(B * K * NX),
+          c.take<double>(B * (N + 1), node_times), c.bytes()};
+}
+// d_stage, run_policy: nin input doubles, then x, u, tau of n queries and the whole-body (x, u) of a centroidal handle's
+struct PolicyStage { double* in; double* x; double* u; double* tau; double* xw; double* uw; size_t bytes; };
+static PolicyStage policy_stage_layout(Carve c, size_t n, size_t nin) {
+  return {c.take<double>(nin), c.take<double>(n * NX), c.take<double>(n * NU), c.take<double>(n * NJ), c.take<double>(n * NX), c.take<double>(n * NU), c.bytes()};
+}
+// d_ro, rollout_impl: window [3] | status, steps, rejected [B] each, one region | (host entry point) s0 [B], x0 [B][58], x [B][n][58], u [B][n][35]
+struct RolloutStage { int* win; int32_t* status; int32_t* steps; int32_t* rejected; double* s0; double* x0; double* x; double* u; size_t bytes; };
+static RolloutStage rollout_stage_layout(Carve c, size_t B, size_t n, bool host, bool want_x, bool want_u) {
+  int* win = c.take<int>(3);
+  int32_t* cnt = c.take<int32_t>(3 * B);
+  return {win, cnt, cnt ? cnt + B : nullptr, cnt ? cnt + 2 * B : nullptr, c.take<double>(B, host), c.take<double>(B * NX, host),
+          c.take<double>(B * n * NX, host && want_x), c.take<double>(B * n * NU, host && want_u), c.bytes()};
+}
+// d_loop_log, hsqp_command_targets (host arrays)
+struct CommandStage { double* v_cmd; double* v_filt; double* x0; double* tt; double* ts; size_t bytes; };
+static CommandStage command_stage_layout(Carve c, size_t B) {
+  return {c.take<double>(B * CMD_N), c.take<double>(B * CMD_N), c.take<double>(B * NX), c.take<double>(B * CMD_KNOTS), c.take<double>(B * CMD_KNOTS * NX), c.bytes()};
+}
+// d_loop: the loop's resident arrays
+static size_t loop_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t E) {
+  L.ne = c.take<int>(B); L.seq = c.take<int>(B * (E + 1)); L.bad = c.take<int>(1); L.ro_status = c.take<int32_t>(B); L.ev = c.take<double>(B * E);
+  L.tt = c.take<double>(B * CMD_KNOTS); L.ts = c.take<double>(B * CMD_KNOTS * NX); L.s0 = c.take<double>(B); L.v_cmd = c.take<double>(B * CMD_N);
+  L.v_filt = c.take<double>(2 * B * CMD_N); L.x = c.take<double>(B * NX); L.xs = c.take<double>(B * NX); L.us = c.take<double>(B * NU);
+  return c.bytes();
+}
+// d_gait: the settings, the status words, the host entry point's schedule and inputs, the two copies of the state
+static size_t gait_layout(Carve c, hsqp_handle::Gait& G, size_t B, size_t E) {
+  G.d_st = c.take<hsqp_gait_settings>(1); G.status = c.take<int>(B); G.ne = c.take<int>(B); G.seq = c.take<int>(B * (E + 1)); G.ev = c.take<double>(B * E);
+  G.v = c.take<double>(B * CMD_N); G.x = c.take<double>(B * NX);
+  for (GaitState& s : G.s) s = GaitState{c.take<int>(B), c.take<double>(B * E), c.take<int>(B * (E + 1)), c.take<int>(B * GAIT_SCAL), c.take<double>(B)};
+  return c.bytes();
+}
+// d_episode: the episode arrays, x_reset, the command in use, the staging of a hsqp_loop_reset_instances request
+static size_t episode_layout(Carve c, hsqp_handle::Loop& L, size_t B) {
+  L.ep = EpisodeState{c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B)};
+  L.x_reset = c.take<double>(B * NX); L.v_use = c.take<double>(B * CMD_N);
+  L.req_ids = c.take<int>(B); L.req_x0 = c.take<double>(B * NX); L.req_v = c.take<double>(B * CMD_N);
+  return c.bytes();
+}
+// d_push: n_pushes [B], then pushes [B][max_pushes]
+struct PushBuf { int32_t* n; hsqp_push* p; size_t bytes; };
+static PushBuf push_layout(Carve c, size_t B, size_t max_pushes) { return {c.take<int32_t>(B), c.take<hsqp_push>(B * max_pushes), c.bytes()}; }
+// d_plant, and the host array uploaded to it: kp | kd | armature, [NJ] each, which PlantParams::gains reads as one array (own packing, not Carve::take)
+struct PlantGains { double* kp; double* kd; double* armature; };
+static PlantGains plant_gains(double* g) { return {g, g + NJ, g + 2 * NJ}; }
+// d_loop_log, hsqp_loop_run's host logs: x_log [n][B][58] | u_log [n][B][35], the cycles' rows as one array each (own packing, not Carve::take); a null block: the sizing pass
+struct LoopLog { double* x; double* u; size_t bytes; };
+static LoopLog loop_log_layout(double* block, size_t n, size_t B, bool want_x, bool want_u) {
+  const size_t nx = want_x ? n * B * NX : 0, nu = want_u ? n * B * NU : 0;
+  return {block && want_x ? block : nullptr, block && want_u ? block + nx : nullptr, (nx + nu) * 8};
+}
 
 // (the KKT gate of the parallel-in-time sweep: scan_gate_accepts, hsqp_scan.h)
 // Refinement passes of the gains (one more stage of the exact Riccati map from the value functions of the previous pass).  Centroidal: one
@@ -1220,10 +1286,10 @@ static int launch_scan(hsqp_handle* h, int B, int N, bool want_kkt, int refineme
   constexpr int SZ = ScanEl<n>::SIZE;
   const int nodes = B * N;
   for (auto& el : h->d_el) DEV_ENSURE(el, (size_t)B * (N + 1) * SZ * 8, "scan elements");
-  HSQP_LAUNCH(k_scan_init<n>, dim3(B * (N + 1)), dim3(SCAN_INIT_THREADS), sizeof(ScanInitWS<n>), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, N, h->d_el[0], h->d_scanst);
+  HSQP_LAUNCH(k_scan_init<n>, dim3(B * (N + 1)), dim3(SCAN_INIT_THREADS), sizeof(ScanInitWS<n>), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, N, h->d_el[0], h->gate.flags);
   int cur = 0;
   for (int d = 1; d < N + 1; d *= 2) {
-    HSQP_LAUNCH(k_scan_combine<n>, dim3(B * (N + 1)), dim3(SCAN_COMB_THREADS), sizeof(ScanCombWS<n>), h->stream, h->d_el[cur], h->d_el[1 - cur], N, d, h->d_scanst, h->d_prof + 256);
+    HSQP_LAUNCH(k_scan_combine<n>, dim3(B * (N + 1)), dim3(SCAN_COMB_THREADS), sizeof(ScanCombWS<n>), h->stream, h->d_el[cur], h->d_el[1 - cur], N, d, h->gate.flags, h->d_prof + 256);
     cur = 1 - cur;
   }
   DEV_ENSURE(h->d_vf, vf_bytes(h), "value functions");
@@ -1234,7 +1300,7 @@ static int launch_scan(hsqp_handle* h, int B, int N, bool want_kkt, int refineme
   for (int pass = 0; pass <= refinements; ++pass) {
     const bool lastp = pass == refinements;
     HSQP_LAUNCH(k_scan_gains<n>, dim3(nodes), dim3(RIC_THREADS), sizeof(RicWS), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, h->d_el[cur],
-                       pass == 0 ? (const double*)nullptr : (const double*)vbuf[(pass - 1) & 1], h->d_ric, N, h->d_scanst,
+                       pass == 0 ? (const double*)nullptr : (const double*)vbuf[(pass - 1) & 1], h->d_ric, N, h->gate.flags,
                        (lastp && !want_kkt) ? (double*)nullptr : vbuf[pass & 1], lastp ? h->d_acl : (double*)nullptr);
   }
   HSQP_LAUNCH(k_scan_forward<n>, dim3(B), dim3(SCAN_FWD_THREADS), sizeof(RicWS), h->stream, h->d_xinit, h->d_x, h->d_acl, N, h->d_dx);   // 4 n <= 256 items per stage: four waves
@@ -1273,18 +1339,18 @@ static int launch_segmented(hsqp_handle* h, int B, int N, int P, bool want_vf) {
   DEV_ENSURE(h->d_vf2, vf_bytes(h), "value functions of the gated sweep");
   const int segs = B * P;
   HSQP_LAUNCH(k_seg_elem_ric<n>, dim3(segs), dim3(RIC_THREADS), sizeof(RicWS), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, (const double*)h->d_zero, h->d_ric2,
-                     h->d_linv, h->d_vf0, N, P, h->d_scanst);
+                     h->d_linv, h->d_vf0, N, P, h->gate.flags);
   HSQP_LAUNCH(k_seg_accumulate<n>, dim3(segs), dim3(SEG_ACC_THREADS), sizeof(SegAccWS), h->stream, (const double*)h->d_qp, (const double*)h->d_ric2,
                      (const double*)h->d_linv, (const double*)h->d_vf0, N, P, h->d_el[0]);
   HSQP_LAUNCH(k_seg_terminal<n>, dim3(B), dim3(256), 0, h->stream, h->d_dm, h->d_x, h->d_par, N, P, h->d_el[0]);
   int cur = 0;
   for (int d = 1; d < P + 1; d *= 2) {
-    HSQP_LAUNCH(k_scan_combine<n>, dim3(B * (P + 1)), dim3(SCAN_COMB_THREADS), sizeof(ScanCombWS<n>), h->stream, h->d_el[cur], h->d_el[1 - cur], P, d, h->d_scanst,
+    HSQP_LAUNCH(k_scan_combine<n>, dim3(B * (P + 1)), dim3(SCAN_COMB_THREADS), sizeof(ScanCombWS<n>), h->stream, h->d_el[cur], h->d_el[1 - cur], P, d, h->gate.flags,
                        (long long*)nullptr);
     cur = 1 - cur;
   }
   HSQP_LAUNCH(k_seg_riccati<n>, dim3(segs), dim3(RIC_THREADS), sizeof(RicWS), h->stream, h->d_dm, h->d_x, h->d_par, h->d_qp, (const double*)h->d_el[cur], h->d_ric, N, P,
-                     h->d_scanst, h->d_vf2, want_vf ? 0 : 2);
+                     h->gate.flags, h->d_vf2, want_vf ? 0 : 2);
   HSQP_LAUNCH(k_ric_forward<n>, dim3(B), dim3(RIC_THREADS), sizeof(RicWS), h->stream, h->d_xinit, h->d_x, h->d_qp, (const double*)h->d_ric, N, h->d_dx, h->d_ut);
   return HSQP_OK;
 }
@@ -1424,14 +1490,13 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
   alloc(h->d_qp, B * N * (size_t)QP_SIZE * 8, "QP record"); alloc(h->d_ric, B * N * (size_t)RIC_SIZE * 8, "gains"); alloc(h->d_dx, B * (N + 1) * NX * 8, "dx");
   alloc(h->d_du, B * N * NU * 8, "du"); alloc(h->d_ut, B * N * NUT * 8, "ut"); alloc(h->d_fj, B * N * NJ * 8, "joint rows of the roll-out");
   alloc(h->d_xnew, B * (N + 1) * NX * 8, "x_new"); alloc(h->d_unew, B * N * NU * 8, "u_new"); alloc(h->d_misc, B * N * 8 * 8, "value-pass terms");
-  alloc(h->d_kkt, gate_block_bytes(B), "gate block"); alloc(h->d_dt, B * N * 8, "interval lengths"); alloc(h->d_perf_before, B * sizeof(hsqp_perf), "perf_before");
+  alloc(h->d_kkt, gate_view(nullptr, B).bytes, "gate block"); alloc(h->d_dt, B * N * 8, "interval lengths"); alloc(h->d_perf_before, B * sizeof(hsqp_perf), "perf_before");
   alloc(h->d_perf_after, B * sizeof(hsqp_perf), "perf_after"); alloc(h->d_status, B * sizeof(int), "status"); alloc(h->d_prof, 4 * 128 * sizeof(long long), "phase profile");
   alloc(h->d_stepinfo, B * N * 4 * 8, "step terms"); alloc(h->d_ls, B * sizeof(LsState), "line-search state"); alloc(h->d_counts, 2 * sizeof(int), "line-search counters");
   alloc(h->d_stamps[0], B * (N + 1) * 8, "time stamps"); alloc(h->d_stamps[1], B * (N + 1) * 8, "time stamps");
   if (rc != HSQP_OK) return fail(rc, h->err);
-  if (hipHostMalloc((void**)&h->h_gate, gate_block_bytes(B)) != hipSuccess) { h->h_gate = nullptr; return fail(HSQP_ERR_OOM, "hipHostMalloc failed (gate block)"); }
-  h->d_ginf = h->d_kkt + 2 * B;   // one block [kkt (2 per instance of max_batch) | |g|_inf | flags of the scan kernels]: one memset, one read-back for the scan's gate
-  h->d_scanst = reinterpret_cast<int*>(h->d_kkt + 3 * B);
+  if (hipHostMalloc((void**)&h->h_gate, gate_view(nullptr, B).bytes) != hipSuccess) { h->h_gate = nullptr; return fail(HSQP_ERR_OOM, "hipHostMalloc failed (gate block)"); }
+  h->gate = gate_view(h->d_kkt, B);
   if (hipMemcpy(h->d_dm, &h->hdm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) return fail(HSQP_ERR_HIP, "model upload failed");
   if (hipMemset(h->d_prof, 0, 4 * 128 * sizeof(long long)) != hipSuccess) return fail(HSQP_ERR_HIP, "memset failed");
   // the limb-lane LQ kernel never writes record entries that are zero for every state (hsqp_lql.h)
@@ -1674,19 +1739,8 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
   const int N_prev = h->N;
   if (warm == HSQP_WARM_SHIFT) { const int rc = warm_shift_ready(h, p->batch, sorted); if (rc != HSQP_OK) return rc; }
   const size_t B = p->batch, N = p->n_nodes, E = r->max_events, K = r->n_knots;
-  // staging area for the compact reference (a few KB per instance)
-  const size_t o_ne = 0, o_seq = o_ne + align256(B * 4), o_bad = o_seq + align256(B * (E + 1) * 4), o_ev = o_bad + 256,
-               o_tt = o_ev + align256(B * E * 8), o_ts = o_tt + align256(B * K * 8), o_nt = o_ts + align256(B * K * NX * 8),
-               total = o_nt + align256(r->node_times ? B * (N + 1) * 8 : 0);
-  DEV_ENSURE(h->d_stage, total, "reference staging");
-  char* base = h->d_stage;
-  int* d_ne = reinterpret_cast<int*>(base + o_ne);
-  int* d_seq = reinterpret_cast<int*>(base + o_seq);
-  int* d_bad = reinterpret_cast<int*>(base + o_bad);
-  double* d_ev = reinterpret_cast<double*>(base + o_ev);
-  double* d_tt = reinterpret_cast<double*>(base + o_tt);
-  double* d_ts = reinterpret_cast<double*>(base + o_ts);
-  double* d_nt = r->node_times ? reinterpret_cast<double*>(base + o_nt) : nullptr;
+  DEV_ENSURE(h->d_stage, ref_stage_layout(Carve{}, B, N, E, K, r->node_times).bytes, "reference staging");
+  const auto [d_ne, d_seq, d_bad, d_ev, d_tt, d_ts, d_nt, staged] = ref_stage_layout(Carve{h->d_stage.p}, B, N, E, K, r->node_times);
   h->have_problem = false; h->have_solution = false; h->have_stamps = false;   // a failure below leaves no half-uploaded problem behind
   { const int rc = set_grid(h, p, false); if (rc != HSQP_OK) return rc; }
   StickyError step{h};
@@ -1821,7 +1875,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     if (last) HCHECK(hipEventRecord(h->ev[2], h->stream));
     if (want_kkt) DEV_ENSURE(h->d_vf, vf_bytes(h), "value functions");
     const int Bm = h->st.max_batch;
-    const size_t gate_bytes = gate_block_bytes(Bm);
+    const size_t gate_bytes = h->gate.bytes;
     int ut_given = 0;   // the last sweep's roll-out left ut = k + K dx of every node in d_ut (the serial roll-out does, the scan's closed-loop roll-out does not)
     int fj_given = 0;   // ... and rows 12 .. 34 of Px dx + Pu ut in d_fj (the factored roll-out does)
     auto launch_sweep = [&](bool use_scan, bool need_vf) -> int {
@@ -1857,7 +1911,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     // vf: the value functions of the sweep whose step is checked.  zeroed: the scan path has zeroed the block before its kernels
     auto launch_kkt = [&](const double* vf, bool zeroed) {
       const hipError_t e = zeroed ? hipSuccess : hipMemsetAsync(h->d_kkt, 0, gate_bytes, h->stream);   // kkt, |g|_inf (and the scan flags) are one block
-      if (e == hipSuccess) HSQP_LAUNCH(k_kkt, dim3(nodes), dim3(256), 0, h->stream, h->d_xinit, h->d_x, h->d_qp, vf, h->d_dx, h->d_ut, N, h->d_kkt, h->d_ginf);
+      if (e == hipSuccess) HSQP_LAUNCH(k_kkt, dim3(nodes), dim3(256), 0, h->stream, h->d_xinit, h->d_x, h->d_qp, vf, h->d_dx, h->d_ut, N, h->d_kkt, h->gate.ginf);
       return e;
     };
     if (scan) HCHECK(hipMemsetAsync(h->d_kkt, 0, gate_bytes, h->stream));   // also the flags the scan kernels OR into
@@ -1868,7 +1922,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
       // (two-level sweep: the gate block holds its boundary-consistency numbers instead — no KKT kernel; the KKT report, if asked for, follows the verdict)
       if (segP == 0) HCHECK(launch_kkt(h->d_vf2, true));
       else HSQP_LAUNCH(k_kkt_boundaries, dim3(B * (segP - 1)), dim3(256), 0, h->stream, h->d_xinit, h->d_x, h->d_qp, (const double*)h->d_vf2, h->d_dx, h->d_ut, N, segP,
-                              h->d_kkt, h->d_ginf);
+                              h->d_kkt, h->gate.ginf);
       HCHECK(hipMemcpyAsync(h->h_gate, h->d_kkt, gate_bytes, hipMemcpyDeviceToHost, h->stream));
     } else if (want_kkt) {
       HCHECK(launch_kkt(h->d_vf, false));
@@ -1883,16 +1937,15 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     if (ev4_early) HCHECK(hipEventRecord(h->ev[4], h->stream));
     if (scan) {
       HCHECK(hipStreamSynchronize(h->stream));
-      const double* hk = h->h_gate;
-      const int* flags = reinterpret_cast<const int*>(hk + 3 * Bm);
+      const GateView hg = gate_view(h->h_gate, Bm);
       bool accept = true;
       for (int b = 0; b < B; ++b) {
         // (a flag = a bad pivot / failed factorisation inside the scan: the serial recursion decides what is reported in d_status)
-        if (!scan_gate_accepts(hk[2 * b], hk[2 * b + 1], hk[2 * Bm + b], flags[b])) accept = false;
+        if (!scan_gate_accepts(hg.kkt[2 * b], hg.kkt[2 * b + 1], hg.ginf[b], hg.flags[b])) accept = false;
       }
       if (h->seg_debug && segP > 0) {
         double m0 = 0, m1 = 0, m2 = 0; int fl = 0;
-        for (int b = 0; b < B; ++b) { m0 = fmax(m0, hk[2 * b]); m1 = fmax(m1, hk[2 * b + 1]); m2 = fmax(m2, hk[2 * Bm + b]); fl |= flags[b]; }
+        for (int b = 0; b < B; ++b) { m0 = fmax(m0, hg.kkt[2 * b]); m1 = fmax(m1, hg.kkt[2 * b + 1]); m2 = fmax(m2, hg.ginf[b]); fl |= hg.flags[b]; }
         fprintf(stderr, "[hsqp seg gate] P=%d boundary-stage KKT stat %.3e prim %.3e |g| %.3e flags %d accept %d\n", segP, m0, m1, m2, fl, (int)accept);
       }
       if (accept && segP > 0 && want_kkt) HCHECK(launch_kkt(h->d_vf2, false));   // the KKT report of an accepted two-level sweep (the gate block is reused)
@@ -2088,7 +2141,7 @@ static int download_impl(hsqp_handle* h, hsqp_solution* s, bool device_dst) {
   if (s->perf_before) HCHECK(hipMemcpy(s->perf_before, h->d_perf_before, B * sizeof(hsqp_perf), kind));
   if (s->perf_after) HCHECK(hipMemcpy(s->perf_after, h->d_perf_after, B * sizeof(hsqp_perf), kind));
   if (s->kkt) HCHECK(hipMemcpy(s->kkt, h->d_kkt, B * 2 * 8, kind));
-  if (s->grad_inf) HCHECK(hipMemcpy(s->grad_inf, h->d_ginf, B * 8, kind));
+  if (s->grad_inf) HCHECK(hipMemcpy(s->grad_inf, h->gate.ginf, B * 8, kind));
   if (s->alpha || s->step_type || s->armijo) {
     std::vector<LsState> ls(B);
     HCHECK(hipMemcpy(ls.data(), h->d_ls, B * sizeof(LsState), hipMemcpyDeviceToHost));
@@ -2138,16 +2191,8 @@ static int run_policy(hsqp_handle* h, int n, bool from_solution, const double* s
   HCHECK(hipSetDevice(h->device));
   const bool cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;
   const size_t nin = from_solution ? (size_t)n * (x_meas ? 1 + NX : 1) : (size_t)n * (NX + NU);
-  const size_t o_in = 0, o_x = o_in + align256(nin * 8), o_u = o_x + align256((size_t)n * NX * 8), o_tau = o_u + align256((size_t)n * NU * 8),
-               o_xw = o_tau + align256((size_t)n * NJ * 8), o_uw = o_xw + align256((size_t)n * NX * 8), total = o_uw + align256((size_t)n * NU * 8);
-  DEV_ENSURE(h->d_stage, total, "policy evaluation staging");
-  char* base = h->d_stage;
-  double* d_in = reinterpret_cast<double*>(base + o_in);
-  double* d_x = reinterpret_cast<double*>(base + o_x);
-  double* d_u = reinterpret_cast<double*>(base + o_u);
-  double* d_tau = reinterpret_cast<double*>(base + o_tau);
-  double* d_xw = reinterpret_cast<double*>(base + o_xw);
-  double* d_uw = reinterpret_cast<double*>(base + o_uw);
+  DEV_ENSURE(h->d_stage, policy_stage_layout(Carve{}, n, nin).bytes, "policy evaluation staging");
+  const auto [d_in, d_x, d_u, d_tau, d_xw, d_uw, staged] = policy_stage_layout(Carve{h->d_stage.p}, n, nin);
   StickyError step{h};
   if (from_solution) {
     step(hipMemcpyAsync(d_in, s_or_x, (size_t)n * 8, hipMemcpyHostToDevice, h->stream), "upload s");
@@ -2267,9 +2312,6 @@ static const char* rollout_settings_error(const hsqp_rollout_settings& st) {
   return nullptr;
 }
 
-// bytes of the n_pushes block in front of the pushes in d_push
-static size_t push_n_bytes(int batch) { return align256((size_t)batch * 4); }
-
 // dev: every array argument is device memory of the handle's GPU
 // per_instance (the isolated loop, include/hsqp_episode.h): an instance's status word — of the iteration, of the integration — is the instance's
 // alone: it is written to `status`, not turned into the call's return code
@@ -2289,32 +2331,26 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
   const size_t B = h->B, nn = (size_t)n;
   const int N = h->N;
   const bool cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL, feedback = st->controller == HSQP_ROLLOUT_FEEDBACK;
-  // staging: window [3] | status, steps, rejected [B] each | (host entry point) s0 [B], x0 [B][58], x [B][n][58], u [B][n][35]
-  const size_t o_win = 0, o_cnt = o_win + 256, o_s0 = o_cnt + align256(B * 3 * 4), o_x0 = o_s0 + (dev ? 0 : align256(B * 8)),
-               o_x = o_x0 + (dev ? 0 : align256(B * NX * 8)), o_u = o_x + (dev || !x ? 0 : align256(B * nn * NX * 8)),
-               total = o_u + (dev || !u ? 0 : align256(B * nn * NU * 8));
-  DEV_ENSURE(h->d_ro, total, "rollout staging");
-  char* base = h->d_ro.p;
-  int* d_win = reinterpret_cast<int*>(base + o_win);
-  int32_t* d_status = reinterpret_cast<int32_t*>(base + o_cnt);
-  int32_t* d_steps = dev ? steps : (steps ? d_status + B : nullptr);
-  int32_t* d_rej = dev ? rejected : (rejected ? d_status + 2 * B : nullptr);
-  const double* d_s0 = dev ? s0 : reinterpret_cast<const double*>(base + o_s0);
-  const double* d_x0 = dev ? x0 : reinterpret_cast<const double*>(base + o_x0);
-  double* d_x = dev ? x : (x ? reinterpret_cast<double*>(base + o_x) : nullptr);
-  double* d_u = dev ? u : (u ? reinterpret_cast<double*>(base + o_u) : nullptr);
+  DEV_ENSURE(h->d_ro, rollout_stage_layout(Carve{}, B, nn, !dev, x, u).bytes, "rollout staging");
+  const RolloutStage sg = rollout_stage_layout(Carve{h->d_ro.p}, B, nn, !dev, x, u);
+  int32_t* d_steps = dev ? steps : (steps ? sg.steps : nullptr);
+  int32_t* d_rej = dev ? rejected : (rejected ? sg.rejected : nullptr);
+  const double* d_s0 = dev ? s0 : sg.s0;
+  const double* d_x0 = dev ? x0 : sg.x0;
+  double* d_x = dev ? x : sg.x;
+  double* d_u = dev ? u : sg.u;
   StickyError step{h};
   if (!dev) {
-    step(hipMemcpyAsync(base + o_s0, s0, B * 8, hipMemcpyHostToDevice, h->stream), "upload s0");
-    step(hipMemcpyAsync(base + o_x0, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
+    step(hipMemcpyAsync(sg.s0, s0, B * 8, hipMemcpyHostToDevice, h->stream), "upload s0");
+    step(hipMemcpyAsync(sg.x0, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
   }
   const double* dts = h->uniform_grid ? nullptr : (const double*)h->d_dt;
   // (the torque plant evaluates the policy up to `lookahead` past the call's last time: the gain window covers it)
   const bool torque = h->plant.kind == HSQP_PLANT_TORQUE;
-  HSQP_LAUNCH(k_rollout_window, dim3(1), dim3(RO_WIN_THREADS), 0, h->stream, d_s0, (int)B, torque ? duration + h->plant.lookahead : duration, (const double*)h->d_dt, N, h->dt, h->uniform_grid ? 1 : 0, d_win);
+  HSQP_LAUNCH(k_rollout_window, dim3(1), dim3(RO_WIN_THREADS), 0, h->stream, d_s0, (int)B, torque ? duration + h->plant.lookahead : duration, (const double*)h->d_dt, N, h->dt, h->uniform_grid ? 1 : 0, sg.win);
   step(hipGetLastError(), "k_rollout_window");
   int win[3] = {0, 0, 0};
-  step(hipMemcpyAsync(win, d_win, sizeof(win), hipMemcpyDeviceToHost, h->stream), "download window");
+  step(hipMemcpyAsync(win, sg.win, sizeof(win), hipMemcpyDeviceToHost, h->stream), "download window");
   step(hipStreamSynchronize(h->stream), "sync");
   if (step.rc != HSQP_OK) return step.rc;
   if (win[2]) return bad("non-finite s0");
@@ -2332,18 +2368,19 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     step(hipGetLastError(), "k_feedback_gains");
   }
   PushTable pt{nullptr, nullptr, 0, nullptr, 0};
-  if (h->push_B)
-    pt = PushTable{reinterpret_cast<const int32_t*>(h->d_push.p), reinterpret_cast<const hsqp_push*>(h->d_push.p + push_n_bytes(h->push_B)), h->push_max,
-                   h->stamps_resident ? (const double*)h->d_stamps[h->stamps_cur] : nullptr, N + 1};
-  const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, d_status, d_steps, d_rej, pt};
+  if (h->push_B) {
+    const PushBuf pb = push_layout(Carve{h->d_push.p}, h->push_B, h->push_max);
+    pt = PushTable{pb.n, pb.p, h->push_max, h->stamps_resident ? (const double*)h->d_stamps[h->stamps_cur] : nullptr, N + 1};
+  }
+  const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, sg.status, d_steps, d_rej, pt};
   if (torque)
-    HSQP_LAUNCH(k_rollout_plant, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, PlantParams{h->d_plant.p, h->plant.lookahead, (const double*)h->d_xnew});
+    HSQP_LAUNCH(k_rollout_plant, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, PlantParams{plant_gains(h->d_plant).kp, h->plant.lookahead, (const double*)h->d_xnew});
   else if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
   else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
   step(hipGetLastError(), "k_rollout");
   std::vector<int32_t> hs(B);
-  step(hipMemcpyAsync(hs.data(), d_status, B * 4, hipMemcpyDeviceToHost, h->stream), "download status");
-  if (dev) step(hipMemcpyAsync(status, d_status, B * 4, hipMemcpyDeviceToDevice, h->stream), "copy status");
+  step(hipMemcpyAsync(hs.data(), sg.status, B * 4, hipMemcpyDeviceToHost, h->stream), "download status");
+  if (dev) step(hipMemcpyAsync(status, sg.status, B * 4, hipMemcpyDeviceToDevice, h->stream), "copy status");
   else {
     if (x) step(hipMemcpyAsync(x, d_x, B * nn * NX * 8, hipMemcpyDeviceToHost, h->stream), "download x");
     if (u) step(hipMemcpyAsync(u, d_u, B * nn * NU * 8, hipMemcpyDeviceToHost, h->stream), "download u");
@@ -2399,12 +2436,12 @@ static int push_set_impl(hsqp_handle* h, int batch, int max_pushes, const int32_
     }
   }
   HCHECK(hipSetDevice(h->device));
-  const size_t nb = push_n_bytes(batch), pb = (size_t)batch * max_pushes * sizeof(hsqp_push);
   h->push_B = 0;   // (a failure below leaves no table)
-  DEV_ENSURE(h->d_push, nb + pb, "push table");
+  DEV_ENSURE(h->d_push, push_layout(Carve{}, batch, max_pushes).bytes, "push table");
+  const PushBuf pb = push_layout(Carve{h->d_push.p}, batch, max_pushes);
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  HCHECK(hipMemcpyAsync(h->d_push.p, n_pushes, (size_t)batch * 4, kind, h->stream));
-  HCHECK(hipMemcpyAsync(h->d_push.p + nb, pushes, pb, kind, h->stream));
+  HCHECK(hipMemcpyAsync(pb.n, n_pushes, (size_t)batch * 4, kind, h->stream));
+  HCHECK(hipMemcpyAsync(pb.p, pushes, (size_t)batch * max_pushes * sizeof(hsqp_push), kind, h->stream));
   HCHECK(hipStreamSynchronize(h->stream));
   h->push_B = batch; h->push_max = max_pushes;
   return HSQP_OK;
@@ -2426,9 +2463,9 @@ int hsqp_push_get(hsqp_handle* h, int* batch, int* max_pushes, int32_t* n_pushes
   if (batch) *batch = h->push_B;
   if (max_pushes) *max_pushes = h->push_max;
   HCHECK(hipSetDevice(h->device));
-  if (n_pushes) HCHECK(hipMemcpyAsync(n_pushes, h->d_push.p, (size_t)h->push_B * 4, hipMemcpyDeviceToHost, h->stream));
-  if (pushes)
-    HCHECK(hipMemcpyAsync(pushes, h->d_push.p + push_n_bytes(h->push_B), (size_t)h->push_B * h->push_max * sizeof(hsqp_push), hipMemcpyDeviceToHost, h->stream));
+  const PushBuf pb = push_layout(Carve{h->d_push.p}, h->push_B, h->push_max);
+  if (n_pushes) HCHECK(hipMemcpyAsync(n_pushes, pb.n, (size_t)h->push_B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (pushes) HCHECK(hipMemcpyAsync(pushes, pb.p, (size_t)h->push_B * h->push_max * sizeof(hsqp_push), hipMemcpyDeviceToHost, h->stream));
   HCHECK(hipStreamSynchronize(h->stream));
   return HSQP_OK;
 }
@@ -2453,7 +2490,8 @@ int hsqp_plant_set(hsqp_handle* h, const hsqp_plant_settings* s) {
     if (!ok(s->kp[j]) || !ok(s->kd[j]) || !ok(s->armature[j])) return bad(("joint " + std::to_string(j) + ": negative or non-finite kp, kd or armature").c_str());
   HCHECK(hipSetDevice(h->device));
   double g[3 * NJ];
-  for (int j = 0; j < NJ; ++j) { g[j] = s->kp[j]; g[NJ + j] = s->kd[j]; g[2 * NJ + j] = s->armature[j]; }
+  const PlantGains hg = plant_gains(g);
+  for (int j = 0; j < NJ; ++j) { hg.kp[j] = s->kp[j]; hg.kd[j] = s->kd[j]; hg.armature[j] = s->armature[j]; }
   DEV_ENSURE(h->d_plant, sizeof(g), "plant gains");
   HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the gains that are replaced)
   HCHECK(hipMemcpy(h->d_plant.p, g, sizeof(g), hipMemcpyHostToDevice));
@@ -2516,22 +2554,18 @@ static int command_targets_impl(hsqp_handle* h, int batch, const double* v_cmd, 
     launch_command_targets(h, batch, v_cmd, v_filt, alpha, x0, t0, horizon, tt, ts);
     step(hipGetLastError(), "k_command_targets");
   } else {
-    const size_t o_c = 0, o_f = o_c + align256(B * CMD_N * 8), o_x = o_f + align256(B * CMD_N * 8), o_tt = o_x + align256(B * NX * 8),
-                 o_ts = o_tt + align256(B * CMD_KNOTS * 8), total = o_ts + align256(B * CMD_KNOTS * NX * 8);
-    DEV_ENSURE(h->d_loop_log, total, "command-target staging");
-    char* base = h->d_loop_log.p;
-    double* d_f = reinterpret_cast<double*>(base + o_f);
-    step(hipMemcpyAsync(base + o_c, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
-    step(hipMemcpyAsync(d_f, v_filt, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_filt");
-    step(hipMemcpyAsync(base + o_x, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
+    DEV_ENSURE(h->d_loop_log, command_stage_layout(Carve{}, B).bytes, "command-target staging");
+    const CommandStage sg = command_stage_layout(Carve{h->d_loop_log.p}, B);
+    step(hipMemcpyAsync(sg.v_cmd, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
+    step(hipMemcpyAsync(sg.v_filt, v_filt, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_filt");
+    step(hipMemcpyAsync(sg.x0, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
     if (step.rc == HSQP_OK) {
-      launch_command_targets(h, batch, reinterpret_cast<const double*>(base + o_c), d_f, alpha, reinterpret_cast<const double*>(base + o_x), t0, horizon,
-                             reinterpret_cast<double*>(base + o_tt), reinterpret_cast<double*>(base + o_ts));
+      launch_command_targets(h, batch, sg.v_cmd, sg.v_filt, alpha, sg.x0, t0, horizon, sg.tt, sg.ts);
       step(hipGetLastError(), "k_command_targets");
     }
-    step(hipMemcpyAsync(v_filt, d_f, B * CMD_N * 8, hipMemcpyDeviceToHost, h->stream), "download v_filt");
-    step(hipMemcpyAsync(tt, base + o_tt, B * CMD_KNOTS * 8, hipMemcpyDeviceToHost, h->stream), "download target_times");
-    step(hipMemcpyAsync(ts, base + o_ts, B * CMD_KNOTS * NX * 8, hipMemcpyDeviceToHost, h->stream), "download target_states");
+    step(hipMemcpyAsync(v_filt, sg.v_filt, B * CMD_N * 8, hipMemcpyDeviceToHost, h->stream), "download v_filt");
+    step(hipMemcpyAsync(tt, sg.tt, B * CMD_KNOTS * 8, hipMemcpyDeviceToHost, h->stream), "download target_times");
+    step(hipMemcpyAsync(ts, sg.ts, B * CMD_KNOTS * NX * 8, hipMemcpyDeviceToHost, h->stream), "download target_states");
   }
   step(hipStreamSynchronize(h->stream), "sync");
   return step.rc;
@@ -2588,20 +2622,9 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
   if (!all_finite(v_cmd, B * CMD_N)) return loop_bad(h, who, "non-finite command");
   HCHECK(hipSetDevice(h->device));
   if (gait) { const int rc = gait_reset_impl(h, who, gait, batch, t0); if (rc != HSQP_OK) return rc; }
-  // the loop's resident arrays, carved from one buffer
-  size_t o = 0;
-  const auto carve = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-  const size_t o_ne = carve(B * 4), o_seq = carve(B * (E + 1) * 4), o_bad = carve(4), o_rs = carve(B * 4), o_ev = carve(B * E * 8), o_tt = carve(B * CMD_KNOTS * 8),
-               o_ts = carve(B * CMD_KNOTS * NX * 8), o_s0 = carve(B * 8), o_vc = carve(B * CMD_N * 8), o_vf = carve(2 * B * CMD_N * 8), o_x = carve(B * NX * 8),
-               o_xs = carve(B * NX * 8), o_us = carve(B * NU * 8);
-  DEV_ENSURE(h->d_loop, o, "loop buffers");
-  char* base = h->d_loop.p;
   hsqp_handle::Loop& L = h->loop;
-  L.ne = reinterpret_cast<int*>(base + o_ne); L.seq = reinterpret_cast<int*>(base + o_seq); L.bad = reinterpret_cast<int*>(base + o_bad);
-  L.ro_status = reinterpret_cast<int32_t*>(base + o_rs); L.ev = reinterpret_cast<double*>(base + o_ev); L.tt = reinterpret_cast<double*>(base + o_tt);
-  L.ts = reinterpret_cast<double*>(base + o_ts); L.s0 = reinterpret_cast<double*>(base + o_s0); L.v_cmd = reinterpret_cast<double*>(base + o_vc);
-  L.v_filt = reinterpret_cast<double*>(base + o_vf); L.x = reinterpret_cast<double*>(base + o_x); L.xs = reinterpret_cast<double*>(base + o_xs);
-  L.us = reinterpret_cast<double*>(base + o_us);
+  DEV_ENSURE(h->d_loop, loop_layout(Carve{}, L, B, E), "loop buffers");
+  loop_layout(Carve{h->d_loop.p}, L, B, E);
   StickyError step{h};
   if (!gait) {
     step(hipMemcpyAsync(L.ne, n_events, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
@@ -2713,21 +2736,9 @@ static int gait_reset_impl(hsqp_handle* h, const char* who, const hsqp_gait_sett
   { std::string text; if (const char* what = gait_settings_error(*gs, text)) return loop_bad(h, who, what); }
   HCHECK(hipSetDevice(h->device));
   const size_t B = batch, E = gs->max_events;
-  size_t o = 0;
-  const auto carve = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-  const size_t o_st = carve(sizeof(hsqp_gait_settings)), o_status = carve(B * 4), o_ne = carve(B * 4), o_seq = carve(B * (E + 1) * 4), o_ev = carve(B * E * 8),
-               o_v = carve(B * CMD_N * 8), o_x = carve(B * NX * 8);
-  size_t o_s[2][5];
-  for (int c = 0; c < 2; ++c) { o_s[c][0] = carve(B * 4); o_s[c][1] = carve(B * E * 8); o_s[c][2] = carve(B * (E + 1) * 4); o_s[c][3] = carve(B * GAIT_SCAL * 4); o_s[c][4] = carve(B * 8); }
-  DEV_ENSURE(h->d_gait, o, "gait state");
-  char* base = h->d_gait.p;
   hsqp_handle::Gait& G = h->gait;
-  G.d_st = reinterpret_cast<hsqp_gait_settings*>(base + o_st); G.status = reinterpret_cast<int*>(base + o_status); G.ne = reinterpret_cast<int*>(base + o_ne);
-  G.seq = reinterpret_cast<int*>(base + o_seq); G.ev = reinterpret_cast<double*>(base + o_ev); G.v = reinterpret_cast<double*>(base + o_v);
-  G.x = reinterpret_cast<double*>(base + o_x);
-  for (int c = 0; c < 2; ++c)
-    G.s[c] = GaitState{reinterpret_cast<int*>(base + o_s[c][0]), reinterpret_cast<double*>(base + o_s[c][1]), reinterpret_cast<int*>(base + o_s[c][2]),
-                       reinterpret_cast<int*>(base + o_s[c][3]), reinterpret_cast<double*>(base + o_s[c][4])};
+  DEV_ENSURE(h->d_gait, gait_layout(Carve{}, G, B, E), "gait state");
+  gait_layout(Carve{h->d_gait.p}, G, B, E);
   // reference.info initialModeSchedule {[0.5], [STANCE, STANCE]} offset by t0; rung 0, its template, both gait commands rung 0
   std::vector<int> n(B, 1), seq(B * (E + 1), HSQP_MODE_STANCE), scal(B * GAIT_SCAL, 0);
   std::vector<double> ev(B * E, t0 + 0.5), tc(B, t0);
@@ -2916,9 +2927,9 @@ static int loop_run_impl(hsqp_handle* h, int n_cycles, double* x_log, double* u_
   double* d_xl = x_log;
   double* d_ul = u_log;
   if (!dev && (x_log || u_log)) {
-    DEV_ENSURE(h->d_loop_log, ((x_log ? n * nx : 0) + (u_log ? n * nu : 0)) * 8, "loop log staging");
-    d_xl = x_log ? reinterpret_cast<double*>(h->d_loop_log.p) : nullptr;
-    d_ul = u_log ? reinterpret_cast<double*>(h->d_loop_log.p) + (x_log ? n * nx : 0) : nullptr;
+    DEV_ENSURE(h->d_loop_log, loop_log_layout(nullptr, n, B, x_log, u_log).bytes, "loop log staging");
+    const LoopLog lg = loop_log_layout(reinterpret_cast<double*>(h->d_loop_log.p), n, B, x_log, u_log);
+    d_xl = lg.x; d_ul = lg.u;
   }
   int rc = HSQP_OK, done = 0;
   for (; done < n_cycles && rc == HSQP_OK; done += rc == HSQP_OK)
@@ -2982,20 +2993,9 @@ int hsqp_loop_isolate(hsqp_handle* h, const hsqp_episode_settings* es, const dou
     return loop_bad(h, who, "this loop takes a KKT-gated backward sweep (parallel-in-time or two-level), whose gate is one verdict for the whole batch: "
                             "create the handle with HSQP_FLAG_SERIAL_RICCATI");
   HCHECK(hipSetDevice(h->device));
-  // the episode arrays, x_reset, the command in use, and the staging of a hsqp_loop_reset_instances request (ids, x0, v_cmd)
-  size_t o = 0;
-  const auto carve = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-  size_t o_i[7];
-  for (size_t& v : o_i) v = carve(B * 4);
-  const size_t o_xr = carve(B * NX * 8), o_vu = carve(B * CMD_N * 8);
-  carve(B * 4); carve(B * NX * 8); carve(B * CMD_N * 8);   // (the request's staging: episode_request below)
   L.isolate = false;
-  DEV_ENSURE(h->d_episode, o, "episode arrays");
-  char* base = h->d_episode.p;
-  int* ip[7];
-  for (int k = 0; k < 7; ++k) ip[k] = reinterpret_cast<int*>(base + o_i[k]);
-  L.ep = EpisodeState{ip[0], ip[1], ip[2], ip[3], ip[4], ip[5], ip[6]};
-  L.x_reset = reinterpret_cast<double*>(base + o_xr); L.v_use = reinterpret_cast<double*>(base + o_vu);
+  DEV_ENSURE(h->d_episode, episode_layout(Carve{}, L, B), "episode arrays");
+  episode_layout(Carve{h->d_episode.p}, L, B);
   const std::vector<int> zero(B, 0), none(B, -1), one(B, 1), shift(B, HSQP_WARM_SHIFT);
   StickyError step{h};
   step(hipMemcpyAsync(L.ep.state, zero.data(), B * 4, hipMemcpyHostToDevice, h->stream), "upload episode state");
@@ -3037,21 +3037,15 @@ int hsqp_loop_reset_instances(hsqp_handle* h, int n, const int32_t* ids, const d
   if (x0 && !all_finite(x0, (size_t)n * NX)) return loop_bad(h, who, "non-finite x0");
   if (v_cmd && !all_finite(v_cmd, (size_t)n * CMD_N)) return loop_bad(h, who, "non-finite command");
   HCHECK(hipSetDevice(h->device));
-  const size_t B = L.B;
-  // the request's staging lies behind the command in use (hsqp_loop_isolate carved it)
-  char* at = reinterpret_cast<char*>(L.v_use) + align256(B * CMD_N * 8);
-  int* d_ids = reinterpret_cast<int*>(at); at += align256(B * 4);
-  double* d_x0 = reinterpret_cast<double*>(at); at += align256(B * NX * 8);
-  double* d_v = reinterpret_cast<double*>(at);
   StickyError step{h};
-  step(hipMemcpyAsync(d_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream), "upload ids");
-  if (x0) step(hipMemcpyAsync(d_x0, x0, (size_t)n * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
-  if (v_cmd) step(hipMemcpyAsync(d_v, v_cmd, (size_t)n * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
+  step(hipMemcpyAsync(L.req_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream), "upload ids");
+  if (x0) step(hipMemcpyAsync(L.req_x0, x0, (size_t)n * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
+  if (v_cmd) step(hipMemcpyAsync(L.req_v, v_cmd, (size_t)n * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
   if (step.rc == HSQP_OK) {
-    const HostResetArgs a{d_ids, x0 ? d_x0 : nullptr, v_cmd ? d_v : nullptr, L.x_reset, L.ep, L.x, L.v_cmd, L.v_filt, L.v_use};
+    const HostResetArgs a{L.req_ids, x0 ? L.req_x0 : nullptr, v_cmd ? L.req_v : nullptr, L.x_reset, L.ep, L.x, L.v_cmd, L.v_filt, L.v_use};
     HSQP_LAUNCH(k_episode_host_reset, dim3(n), dim3(64), 0, h->stream, a);
     if (L.gait)
-      HSQP_LAUNCH(k_gait_reset_instances, dim3(n), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)d_ids, (const int*)nullptr, L.t);
+      HSQP_LAUNCH(k_gait_reset_instances, dim3(n), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)L.req_ids, (const int*)nullptr, L.t);
     step(hipGetLastError(), "k_episode_host_reset");
   }
   step(hipStreamSynchronize(h->stream), "sync");
