@@ -9,7 +9,9 @@ iteration and the rollout, and its rollout keeps no step counters).
     python tools/device_loop_cycle.py [--cycles 30] [--warmup 3] [--batch 256] [--nodes 100] [--controller feedforward|feedback]
                                       [--commands same|spread] [--gait ladder|walk] [--isolate park|reset] [--with-push NEWTONS]
                                       [--plant flow|torque] [--kp 100] [--kd 2] [--armature 0.01] [--lookahead 0.005]
+                                      [--contact] [--stiffness 5e4] [--damping 10] [--mu MODEL] [--slip-velocity 0.01]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
+                                      [--plant torque [--contact ...]]
 --with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
 --plant: the plant of the loop's rollout (include/hsqp_plant.h).  torque: full forward dynamics under the joint PD law with the given gains
 (defaults: the gains of the tests); flow: the MPC's own flow map, set explicitly.  With --plant the line also carries `rollout_probe`: after the
@@ -18,8 +20,12 @@ timed cycles one more hsqp_rollout_policy call over the period from the loop's l
 --push: a small push-recovery sweep instead of the timing.  Every instance walks under the same command; instance b is pushed sideways at the
 pelvis (the base link's origin) with b / (batch - 1) of --push-max newtons from --push-at seconds on for --push-for seconds.  Isolation is on
 (park; box: base height above 0.45 m, tilt below 0.7 rad), and the sweep runs once with the feed-forward and once with the feedback controller.
-It prints which instances the triage recorded as failed, with which cause and in which cycle.  It reports; it asserts nothing: the plant's joints
-are ideal acceleration sources and its contacts do not slip, and nobody has measured at which magnitude the G1 falls in this model.
+It prints which instances the triage recorded as failed, with which cause and in which cycle.  It reports; it asserts nothing: without --plant the
+plant's joints are ideal acceleration sources and its contacts do not slip, and nobody has measured at which magnitude the G1 falls in this model.
+With --plant torque --contact the feet stand on the ground of include/hsqp_contact.h, the ground reaction is the contact model's, and the sweep
+also prints each instance's peak total normal force and peak tangential / normal ratio, from contact_forces at the logged states.
+--contact: the ground under the torque plant (include/hsqp_contact.h; requires --plant torque): penalty contact with Coulomb friction at the eight
+sole corners, with the given stiffness [N/m per point], damping [s/m], friction coefficient (default: the model's) and slip velocity [m/s].
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -60,11 +66,15 @@ def push_sweep(args):
     force = args.push_max * np.arange(B) / max(B - 1, 1)
     pushes = [[dict(body=0, t_start=args.push_at, duration=args.push_for, point=(0.0, 0.0, 0.0), force=(0.0, f, 0.0))] for f in force]
     causes = {0: "alive", 1: "numeric", 2: "rollout", 3: "bounds"}
-    rows = {}
+    rows, ground = {}, {}
     s = HipSqpSolver(m, max_nodes=N, max_batch=B, linesearch=True)
     s.set_scan_backoff_persistent(True)
     try:
         s.set_pushes(pushes)
+        if args.plant:
+            s.set_plant(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead)
+        if args.contact:
+            s.set_contact(**contact_args(args))
         for controller in ("feedforward", "feedback"):
             st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True, controller=controller)
             s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
@@ -74,18 +84,40 @@ def push_sweep(args):
             x = r["x"]                                         # [cycle][instance][58], NaN rows once parked
             sway = np.nanmax(np.abs(x[:, :, 1] - x[:, :1, 1]), axis=0)
             rows[controller] = (ep, sway)
+            if args.contact:                                   # ground reaction at every logged state (parked rows: no force)
+                fn_peak, ratio_peak = np.zeros(B), np.zeros(B)
+                for xc in x:
+                    live = np.isfinite(xc).all(axis=1)
+                    f, _ = s.contact_forces(np.where(live[:, None], xc, x_init))
+                    fn = f[:, :, :, 2].sum(axis=(1, 2))
+                    ft = np.linalg.norm(f[:, :, :, :2].sum(axis=(1, 2)), axis=1)
+                    fn_peak = np.maximum(fn_peak, np.where(live, fn, 0.0))
+                    ratio_peak = np.maximum(ratio_peak, np.where(live & (fn > 0.0), ft / np.maximum(fn, 1e-300), 0.0))
+                ground[controller] = (fn_peak, ratio_peak)
     finally:
         s.close()
     print(f"push sweep: {B} instances x {N} nodes, walk at 0.3 m/s, {cycles} cycles of {args.period:.4f} s; lateral push at the pelvis from "
           f"{args.push_at} s for {args.push_for} s (cycles {int(args.push_at / args.period)} .. {int((args.push_at + args.push_for) / args.period)})")
-    print(f"{'instance':>8} {'force [N]':>10} | " + " | ".join(f"{c + ': state':>20} {'cycle':>6} {'sway [m]':>9}" for c in rows))
+    if args.plant:
+        print(f"plant {args.plant}: kp {args.kp} kd {args.kd} armature {args.armature} lookahead {args.lookahead}" + (f"; contact {contact_args(args)}" if args.contact else ""))
+    extra = f" {'peak fn [N]':>12} {'peak ft/fn':>10}" if args.contact else ""
+    print(f"{'instance':>8} {'force [N]':>10} | " + " | ".join(f"{c + ': state':>20} {'cycle':>6} {'sway [m]':>9}" + extra for c in rows))
     for b in range(B):
         cells = []
         for c, (ep, sway) in rows.items():
-            cells.append(f"{causes.get(int(ep['cause'][b]), '?'):>20} {int(ep['fail_cycle'][b]) if ep['n_failures'][b] else '-':>6} {sway[b]:9.4f}")
+            cells.append(f"{causes.get(int(ep['cause'][b]), '?'):>20} {int(ep['fail_cycle'][b]) if ep['n_failures'][b] else '-':>6} {sway[b]:9.4f}"
+                         + (f" {ground[c][0][b]:12.1f} {ground[c][1][b]:10.3f}" if args.contact else ""))
         print(f"{b:8d} {force[b]:10.1f} | " + " | ".join(cells))
     print(json.dumps({"metric": "push_sweep", "batch": B, "nodes": N, "cycles": cycles, "forces": [round(float(f), 2) for f in force],
+                      "plant": args.plant, "contact": contact_args(args) if args.contact else None,
+                      **({"peak_normal_force": {c: [round(float(v), 1) for v in g[0]] for c, g in ground.items()},
+                          "peak_tangential_ratio": {c: [round(float(v), 3) for v in g[1]] for c, g in ground.items()}} if args.contact else {}),
                       **{c: {"failed": [int(b) for b in np.nonzero(ep["n_failures"])[0]], "fail_cycle": [int(v) for v in ep["fail_cycle"]]} for c, (ep, _) in rows.items()}}))
+
+
+def contact_args(args):
+    """The keywords of HipSqpSolver.set_contact from the command line (mu None: the model's friction_mu)."""
+    return dict(stiffness=args.stiffness, damping=args.damping, mu=args.mu, slip_velocity=args.slip_velocity)
 
 
 def rollout_probe(s, args, x_end):
@@ -125,10 +157,17 @@ def main():
     ap.add_argument("--kd", type=float, default=2.0)
     ap.add_argument("--armature", type=float, default=0.01)
     ap.add_argument("--lookahead", type=float, default=0.005)
+    ap.add_argument("--contact", action="store_true")
+    ap.add_argument("--stiffness", type=float, default=5e4)
+    ap.add_argument("--damping", type=float, default=10.0)
+    ap.add_argument("--mu", type=float, default=None)
+    ap.add_argument("--slip-velocity", type=float, default=0.01)
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
     args = ap.parse_args()
+    if args.contact and args.plant != "torque":
+        ap.error("--contact requires --plant torque (the ground acts on the torque plant only)")
     if args.push:
         return push_sweep(args)
     m = load_model()
@@ -169,6 +208,8 @@ def main():
             s.set_pushes([[dict(body=0, t_start=0.0, duration=1e6, point=(0.0, 0.0, 0.0), force=(0.0, args.with_push, 0.0))]] * B)
         if args.plant:
             s.set_plant(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead)
+        if args.contact:
+            s.set_contact(**contact_args(args))
         for c in range(args.warmup + args.cycles):
             if c in changes:
                 s.loop_command(changes[c])
@@ -192,7 +233,8 @@ def main():
     q = np.percentile(cycle_ms, [25, 75])
     print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
                       "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
-                      "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None, "rollout_probe": probe,
+                      "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None,
+                      "contact": contact_args(args) if args.contact else None, "rollout_probe": probe,
                       "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),

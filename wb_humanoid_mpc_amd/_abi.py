@@ -183,6 +183,23 @@ class PlantSettings(C.Structure):   # hsqp_plant_settings
 # entry points of include/hsqp_plant.h (tests/test_plant.py checks that the library exports each of them and the binding declares it)
 PLANT_ENTRY_POINTS = ("hsqp_plant_defaults", "hsqp_plant_set", "hsqp_plant_clear", "hsqp_plant_get")
 
+# include/hsqp_contact.h
+CONTACT_FEET, CONTACT_CORNERS = 2, 4
+
+
+class ContactSettings(C.Structure):   # hsqp_contact_settings
+    _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32), ("stiffness", C.c_double), ("damping", C.c_double), ("mu", C.c_double),
+                ("slip_velocity", C.c_double), ("ground_height", C.c_double)]
+
+
+class ContactGround(C.Structure):   # hsqp_contact_ground
+    _fields_ = [("height", C.c_double), ("mu", C.c_double)]
+
+
+# entry points of include/hsqp_contact.h (tests/test_contact.py checks that the library exports each of them and the binding declares it)
+CONTACT_ENTRY_POINTS = ("hsqp_contact_defaults", "hsqp_contact_set", "hsqp_contact_set_instances", "hsqp_contact_set_instances_device", "hsqp_contact_clear",
+                        "hsqp_contact_get", "hsqp_contact_eval", "hsqp_contact_eval_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

@@ -8,6 +8,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <limits>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -997,17 +999,32 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restri
 static_assert(sizeof(RolloutWS<StageWST<false>>) <= 65536 && sizeof(RolloutWS<CentWST<false>>) <= 65536, "the rollout runs without a dynamic-LDS attribute");
 // the rollout on the torque plant (include/hsqp_plant.h, csrc/hsqp_plant.h): the instantiation of its own that a handle with HSQP_PLANT_TORQUE set launches
 // instead of k_rollout<StageWST<false>>, which does not contain it
-__global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp) {
-  RolloutWS<PlantStage>& w = *reinterpret_cast<RolloutWS<PlantStage>*>(hsqp_smem);
+// SW = PlantStage: the plant as it is without a ground (cp is not read); SW = PlantContactStage: on the resident ground of include/hsqp_contact.h.
+// Contact is a parameter of the instantiation: as a run-time branch it costs the rollout without a ground 3.6 % (measured)
+template <class SW>
+__global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp, ContactParams cp) {
+  RolloutWS<SW>& w = *reinterpret_cast<RolloutWS<SW>*>(hsqp_smem);
   const int b = blockIdx.x;
   const Ctx ctx{(int)threadIdx.x, RO_THREADS, nullptr};
   const RolloutPolicy p{a.ut + (size_t)b * a.N * NU, a.dts ? a.dts + (size_t)b * a.N : nullptr, a.N, a.dt, a.K ? a.K + (size_t)b * a.count * NU * NX : nullptr,
                         a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count, 0};
   plant_load(ctx, pp, b, a.N, w.sw.pl);
+  if constexpr (std::is_same<SW, PlantContactStage>::value) contact_load(ctx, cp, b, w.sw.ct);
   rollout_instance(ctx, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
                    a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr, a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
 static_assert(sizeof(RolloutWS<PlantStage>) <= 65536, "the rollout on the torque plant runs without a dynamic-LDS attribute");
+static_assert(sizeof(RolloutWS<PlantContactStage>) <= 65536, "the rollout on the torque plant over the ground runs without a dynamic-LDS attribute");
+// hsqp_contact_eval (include/hsqp_contact.h): one workgroup per instance — the contact model at a given state: stage topology, one stage_eval<false>
+// for the placements and the link velocities, the eight points
+__global__ __launch_bounds__(RO_THREADS) void k_contact_eval(const DevModel* __restrict__ dm, ContactParams cp, const double* __restrict__ x, double* __restrict__ force,
+                                                             double* __restrict__ pen) {
+  ContactEvalWS& w = *reinterpret_cast<ContactEvalWS*>(hsqp_smem);
+  const int b = blockIdx.x;
+  contact_eval_instance(Ctx{(int)threadIdx.x, RO_THREADS, nullptr}, *dm, w, cp, b, x + (size_t)b * NX, force ? force + (size_t)b * CT_PTS * 3 : nullptr,
+                        pen ? pen + (size_t)b * CT_PTS : nullptr);
+}
+static_assert(sizeof(ContactEvalWS) <= 65536, "hsqp_contact_eval runs without a dynamic-LDS attribute");
 
 // ---- per-instance performance index from per-node {ne, dt*cost, dt*eq^2, dt*dyn^2} + terminal cost
 __device__ inline void perf_reduce_instance(int b, const DevModel* __restrict__ dm, const double* __restrict__ misc, int misc_stride, const double* __restrict__ x,
@@ -1141,6 +1158,12 @@ struct hsqp_handle {
   // the resident plant setting (include/hsqp_plant.h): kind FLOW = none; d_plant: kp, kd, armature [23] each
   hsqp_plant_settings plant = [] { hsqp_plant_settings p; hsqp_plant_defaults(&p); p.kind = HSQP_PLANT_FLOW; return p; }();
   DevBuf<double> d_plant;
+  // the resident ground of the torque plant (include/hsqp_contact.h): enabled = 0 until hsqp_contact_set.  d_contact (contact_layout): the ground of every
+  // instance [max_batch] — the first contact_B entries the per-instance table's, the rest the setting's values; contact_current: it holds that
+  hsqp_contact_settings contact = {};
+  DevBuf<char> d_contact, d_contact_stage;   // d_contact_stage: staging of hsqp_contact_eval's host arrays (contact_stage_layout)
+  int contact_B = 0;
+  bool contact_current = false;
   bool stamps_resident = false;   // d_stamps[stamps_cur] holds the raw stamps of the resident problem (it came through hsqp_upload_reference or the loop): the pushes' clock
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
@@ -1263,6 +1286,14 @@ static size_t episode_layout(Carve c, hsqp_handle::Loop& L, size_t B) {
 // d_push: n_pushes [B], then pushes [B][max_pushes]
 struct PushBuf { int32_t* n; hsqp_push* p; size_t bytes; };
 static PushBuf push_layout(Carve c, size_t B, size_t max_pushes) { return {c.take<int32_t>(B), c.take<hsqp_push>(B * max_pushes), c.bytes()}; }
+// d_contact: the ground of every instance [max_batch]
+struct ContactBuf { hsqp_contact_ground* ground; size_t bytes; };
+static ContactBuf contact_layout(Carve c, size_t max_batch) { return {c.take<hsqp_contact_ground>(max_batch), c.bytes()}; }
+// d_contact_stage, hsqp_contact_eval (host arrays): x [B][58] | force [B][8][3] | penetration [B][8]
+struct ContactStage { double* x; double* force; double* pen; size_t bytes; };
+static ContactStage contact_stage_layout(Carve c, size_t B, bool want_force, bool want_pen) {
+  return {c.take<double>(B * NX), c.take<double>(B * CT_PTS * 3, want_force), c.take<double>(B * CT_PTS, want_pen), c.bytes()};
+}
 // d_plant, and the host array uploaded to it: kp | kd | armature, [NJ] each, which PlantParams::gains reads as one array (own packing, not Carve::take)
 struct PlantGains { double* kp; double* kd; double* armature; };
 static PlantGains plant_gains(double* g) { return {g, g + NJ, g + 2 * NJ}; }
@@ -1443,6 +1474,8 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
   hsqp_linesearch_defaults(&h->ls_settings);
   const std::string e = build_dev_model(*model, h->hdm);
   if (!e.empty()) { g_create_error = e; delete h; return HSQP_ERR_BAD_ARG; }
+  hsqp_contact_defaults(h, &h->contact);   // (the model's friction_mu)
+  h->contact.enabled = 0;
   // the value pass on quads of lanes (hsqp_lqv.h) is a throughput form: a wave evaluates 16 nodes in ~100 us whatever their number, the phase form one node
   // in ~40 us — so a handle sized for fewer nodes than fill the GPU once (config 3: one instance, 100 nodes) keeps the phase form.  Decided per HANDLE, not
   // per call: every solve of a handle runs the same arithmetic (an instance of a batch equals its solo solve bit for bit)
@@ -2312,6 +2345,8 @@ static const char* rollout_settings_error(const hsqp_rollout_settings& st) {
   return nullptr;
 }
 
+static int contact_params(hsqp_handle* h, ContactParams& cp);   // (below, with the entry points of include/hsqp_contact.h)
+
 // dev: every array argument is device memory of the handle's GPU
 // per_instance (the isolated loop, include/hsqp_episode.h): an instance's status word — of the iteration, of the integration — is the instance's
 // alone: it is written to `status`, not turned into the call's return code
@@ -2373,8 +2408,16 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     pt = PushTable{pb.n, pb.p, h->push_max, h->stamps_resident ? (const double*)h->d_stamps[h->stamps_cur] : nullptr, N + 1};
   }
   const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, sg.status, d_steps, d_rej, pt};
-  if (torque)
-    HSQP_LAUNCH(k_rollout_plant, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, PlantParams{plant_gains(h->d_plant).kp, h->plant.lookahead, (const double*)h->d_xnew});
+  ContactParams cp{nullptr, 0.0, 0.0, 0.0};
+  if (torque && h->contact.enabled) {
+    const int rc = contact_params(h, cp);
+    if (rc != HSQP_OK) return rc;
+  }
+  const PlantParams pp{torque ? plant_gains(h->d_plant).kp : nullptr, h->plant.lookahead, (const double*)h->d_xnew};
+  if (torque && cp.ground)
+    HSQP_LAUNCH(k_rollout_plant<PlantContactStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactStage>), h->stream, h->d_dm, a, pp, cp);
+  else if (torque)
+    HSQP_LAUNCH(k_rollout_plant<PlantStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, pp, cp);
   else if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
   else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
   step(hipGetLastError(), "k_rollout");
@@ -2509,6 +2552,127 @@ int hsqp_plant_get(hsqp_handle* h, hsqp_plant_settings* s) {
   if (!s) { h->err = "hsqp_plant_get: null settings"; return HSQP_ERR_BAD_ARG; }
   *s = h->plant;
   return HSQP_OK;
+}
+
+// ---- the ground of the torque plant (include/hsqp_contact.h, csrc/hsqp_contact.h): the resident setting and the per-instance table
+void hsqp_contact_defaults(const hsqp_handle* h, hsqp_contact_settings* s) {
+  if (!s) return;
+  s->enabled = 1; s->reserved = 0;
+  s->stiffness = 5e4; s->damping = 10.0;
+  s->mu = h ? h->hdm.friction_mu : std::numeric_limits<double>::quiet_NaN();
+  s->slip_velocity = 0.01; s->ground_height = 0.0;
+}
+// makes d_contact hold the ground of every instance (entries from contact_B on: the setting's values) and gives the kernels' view of the setting
+static int contact_params(hsqp_handle* h, ContactParams& cp) {
+  const size_t mb = (size_t)h->st.max_batch;
+  if (!h->contact_current) {
+    HCHECK(hipSetDevice(h->device));
+    DEV_ENSURE(h->d_contact, contact_layout(Carve{}, mb).bytes, "contact ground");
+    const std::vector<hsqp_contact_ground> fill(mb - (size_t)h->contact_B, hsqp_contact_ground{h->contact.ground_height, h->contact.mu});
+    HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the entries that are replaced)
+    if (!fill.empty())
+      HCHECK(hipMemcpy(contact_layout(Carve{h->d_contact.p}, mb).ground + h->contact_B, fill.data(), fill.size() * sizeof(hsqp_contact_ground), hipMemcpyHostToDevice));
+    h->contact_current = true;
+  }
+  cp = ContactParams{contact_layout(Carve{h->d_contact.p}, mb).ground, h->contact.stiffness, h->contact.damping, h->contact.slip_velocity};
+  return HSQP_OK;
+}
+static int contact_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) { h->err = std::string(who) + ": whole-body handles only (the contact model acts on the torque plant of the whole-body tree)"; return HSQP_ERR_BAD_ARG; }
+  return HSQP_OK;
+}
+int hsqp_contact_set(hsqp_handle* h, const hsqp_contact_settings* s) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const auto bad = [&](const char* what) { h->err = std::string("hsqp_contact_set: ") + what; return HSQP_ERR_BAD_ARG; };
+  if (!s) return bad("null settings");
+  if (const int rc = contact_handle_ok(h, "hsqp_contact_set")) return rc;
+  if (s->reserved != 0) return bad("reserved must be 0");
+  if (!std::isfinite(s->stiffness) || !std::isfinite(s->damping) || !std::isfinite(s->mu) || !std::isfinite(s->slip_velocity) || !std::isfinite(s->ground_height))
+    return bad("non-finite stiffness, damping, mu, slip_velocity or ground_height");
+  if (!(s->stiffness > 0.0)) return bad("stiffness must be > 0");
+  if (s->damping < 0.0) return bad("damping must be >= 0");
+  if (s->mu < 0.0) return bad("mu must be >= 0");
+  if (!(s->slip_velocity > 0.0)) return bad("slip_velocity must be > 0");
+  h->contact = *s;
+  h->contact_current = false;
+  ContactParams cp;
+  return contact_params(h, cp);
+}
+static int contact_set_instances_impl(hsqp_handle* h, int batch, const hsqp_contact_ground* g, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_contact_set_instances_device" : "hsqp_contact_set_instances";
+  const auto bad = [&](const std::string& what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = contact_handle_ok(h, who)) return rc;
+  if (g) {
+    if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+    if (!dev)
+      for (int b = 0; b < batch; ++b) {
+        if (!std::isfinite(g[b].height) || !std::isfinite(g[b].mu)) return bad("instance " + std::to_string(b) + ": non-finite height or mu");
+        if (g[b].mu < 0.0) return bad("instance " + std::to_string(b) + ": mu must be >= 0");
+      }
+  }
+  HCHECK(hipSetDevice(h->device));
+  h->contact_B = 0;   // (a failure below leaves no table)
+  h->contact_current = false;
+  if (g) {
+    const size_t mb = (size_t)h->st.max_batch;
+    DEV_ENSURE(h->d_contact, contact_layout(Carve{}, mb).bytes, "contact ground");
+    HCHECK(hipStreamSynchronize(h->stream));
+    HCHECK(hipMemcpy(contact_layout(Carve{h->d_contact.p}, mb).ground, g, (size_t)batch * sizeof(hsqp_contact_ground), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    h->contact_B = batch;
+  }
+  ContactParams cp;
+  return contact_params(h, cp);
+}
+int hsqp_contact_set_instances(hsqp_handle* h, int batch, const hsqp_contact_ground* ground) { return contact_set_instances_impl(h, batch, ground, false); }
+int hsqp_contact_set_instances_device(hsqp_handle* h, int batch, const hsqp_contact_ground* d_ground) { return contact_set_instances_impl(h, batch, d_ground, true); }
+int hsqp_contact_clear(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  hsqp_contact_defaults(h, &h->contact);
+  h->contact.enabled = 0;
+  h->contact_B = 0;
+  h->contact_current = false;
+  return HSQP_OK;
+}
+int hsqp_contact_get(hsqp_handle* h, hsqp_contact_settings* s) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (!s) { h->err = "hsqp_contact_get: null settings"; return HSQP_ERR_BAD_ARG; }
+  *s = h->contact;
+  return HSQP_OK;
+}
+static int contact_eval_impl(hsqp_handle* h, int batch, const double* x, double* force, double* pen, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_contact_eval_device" : "hsqp_contact_eval";
+  const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (!x) return bad("null states");
+  if (const int rc = contact_handle_ok(h, who)) return rc;
+  if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+  ContactParams cp;
+  if (const int rc = contact_params(h, cp)) return rc;
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = (size_t)batch;
+  const double* d_x = x;
+  double* d_f = force;
+  double* d_p = pen;
+  StickyError step{h};
+  if (!dev) {
+    DEV_ENSURE(h->d_contact_stage, contact_stage_layout(Carve{}, B, force, pen).bytes, "contact staging");
+    const ContactStage sg = contact_stage_layout(Carve{h->d_contact_stage.p}, B, force, pen);
+    d_x = sg.x; d_f = sg.force; d_p = sg.pen;
+    step(hipMemcpyAsync(sg.x, x, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
+  }
+  HSQP_LAUNCH(k_contact_eval, dim3(batch), dim3(RO_THREADS), sizeof(ContactEvalWS), h->stream, h->d_dm, cp, d_x, d_f, d_p);
+  step(hipGetLastError(), "k_contact_eval");
+  if (!dev) {
+    if (force) step(hipMemcpyAsync(force, d_f, B * CT_PTS * 3 * 8, hipMemcpyDeviceToHost, h->stream), "download force");
+    if (pen) step(hipMemcpyAsync(pen, d_p, B * CT_PTS * 8, hipMemcpyDeviceToHost, h->stream), "download penetration");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+int hsqp_contact_eval(hsqp_handle* h, int batch, const double* x, double* force, double* penetration) { return contact_eval_impl(h, batch, x, force, penetration, false); }
+int hsqp_contact_eval_device(hsqp_handle* h, int batch, const double* d_x, double* d_force, double* d_penetration) {
+  return contact_eval_impl(h, batch, d_x, d_force, d_penetration, true);
 }
 
 static int loop_bad(hsqp_handle* h, const char* who, const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; }

@@ -1,0 +1,105 @@
+// Ground contact on the torque plant of the rollout (include/hsqp_contact.h): the resident setting as the kernel sees it, one instance's
+// parameters and the eight sole corners of one flow evaluation in the rollout workspace.  Penalty model: Hunt-Crossley normal force with exponent
+// 1, regularised Coulomb friction, a horizontal plane (assumption C1 of the public header: not the reference's MuJoCo solver).
+//   contact_load     instance b of the setting into the workspace (the contact instantiation of the rollout kernel only: the handle launches it
+//                    when contact is on, so the set carries no switch and the plant's own instantiation carries no set)
+//   contact_forces   from what stage_eval<false> leaves at the plant's own (q, v): the placements R / r relative to the base origin O and the
+//                    spatial velocity vl = {omega, v_O} of the foot link about O.  P = r_b + R_b p_fc, Pdot = v_O + omega x P; the height of the
+//                    point adds the base position q[2].  The eight points are eight work items; each leaves P, d, the force and its wrench
+//                    {P x f, f} about O, which plant_forward_dynamics picks up per coordinate by the subtree test of the pushes.
+// A point without normal force stores +0 in every entry of force and wrench: subtracting it changes no bit of the right-hand side.
+// Everything is uniform across the workgroup; the same source builds for the host with a one-lane context (tests/contact/contact_emu.cpp).
+#pragma once
+#include "hsqp_model.h"
+#include "../../include/hsqp_contact.h"
+
+namespace hsqp {
+
+constexpr int CT_PTS = HSQP_CONTACT_FEET * HSQP_CONTACT_CORNERS;
+
+// The resident setting, as the kernels that have a ground see it
+struct ContactParams {
+  const hsqp_contact_ground* ground;   // [max_batch] the ground of every instance: the table's entry, or the setting's values
+  double k, c, vs;                     // stiffness, damping, slip velocity
+};
+
+// ONE instance's ground and the points of one flow evaluation
+struct ContactSet {
+  double k, c, vs, height, mu;
+  double P[CT_PTS][3];          // the points relative to the base origin O, world axes
+  double d[CT_PTS];             // penetration (negative: above the ground)
+  double f[CT_PTS][3];          // force on the foot, world axes (ft_x, ft_y, fn)
+  double wr[CT_PTS][6];         // its wrench about O {moment, force}
+};
+
+// instance b of the setting into the workspace.  Ends with a barrier.
+HSQP_HD void contact_load(const Ctx& ctx, const ContactParams& cp, int b, ContactSet& ct) {
+  WG_FOR(ctx, i, 1) {
+    ct.k = cp.k; ct.c = cp.c; ct.vs = cp.vs;
+    ct.height = cp.ground[b].height; ct.mu = cp.ground[b].mu;
+  }
+  WG_SYNC(ctx);
+}
+
+// corner c of the contact rectangle of foot f, in the axes of the foot's body
+HSQP_HD void contact_corner(const DevModel& dm, int f, int c, double* p) {
+  p[0] = dm.contact_p[f][0] + ((c == 1 || c == 2) ? dm.rect_x_max : dm.rect_x_min);
+  p[1] = dm.contact_p[f][1] + (c >= 2 ? dm.rect_y_max : dm.rect_y_min);
+  p[2] = dm.contact_p[f][2];
+}
+
+// point i of the set at the evaluation stage_eval<false> has just run on ws (its q, v).  One work item; no barrier.
+HSQP_HD void contact_point(const DevModel& dm, const StageWST<false>& ws, ContactSet& ct, int i) {
+  const int f = i / HSQP_CONTACT_CORNERS, b = dm.contact_body[f];
+  double p[3], P[3], wxP[3];
+  contact_corner(dm, f, i % HSQP_CONTACT_CORNERS, p);
+  m3_mulv(ws.R[b], p, P);
+  for (int k = 0; k < 3; ++k) P[k] += ws.r[b][k];
+  const double* vl = ws.vl[b + 2];
+  v3_cross(vl, P, wxP);
+  const double vx = vl[3] + wxP[0], vy = vl[4] + wxP[1], vz = vl[5] + wxP[2];
+  const double d = ct.height - (ws.q[2] + P[2]), ddot = -vz;
+  double fn = d > 0.0 ? ct.k * d * (1.0 + ct.c * ddot) : 0.0;
+  if (!(fn > 0.0) && fn == fn) fn = 0.0;   // (a NaN stays: the instance ends non-finite)
+  double F[3] = {0.0, 0.0, 0.0}, mom[3] = {0.0, 0.0, 0.0};
+  if (fn != 0.0) {
+    const double s = -ct.mu * fn / sqrt((vx * vx + vy * vy) + ct.vs * ct.vs);
+    F[0] = s * vx; F[1] = s * vy; F[2] = fn;
+    v3_cross(P, F, mom);
+  }
+  ct.d[i] = d;
+  for (int k = 0; k < 3; ++k) { ct.P[i][k] = P[k]; ct.f[i][k] = F[k]; ct.wr[i][k] = mom[k]; ct.wr[i][3 + k] = F[k]; }
+}
+
+HSQP_HD void contact_forces(const Ctx& ctx, const DevModel& dm, const StageWST<false>& ws, ContactSet& ct) {
+  WG_FOR(ctx, i, CT_PTS) contact_point(dm, ws, ct, i);
+  WG_SYNC(ctx);
+}
+
+// The workspace of hsqp_contact_eval: the stage's, and the set
+struct ContactEvalWS {
+  StageWST<false> st;
+  ContactSet ct;
+};
+
+// hsqp_contact_eval for one instance: the model at state x [58] with instance b of the setting; force [8][3], pen [8] (either may be null)
+HSQP_HD void contact_eval_instance(const Ctx& ctx, const DevModel& dm, ContactEvalWS& w, const ContactParams& cp, int b, const double* x, double* force,
+                                   double* pen) {
+  stage_topology(ctx, dm, w.st, false);
+  WG_FOR(ctx, i, NV + NV + NJ + 12) {
+    if (i < NV) w.st.q[i] = x[i];
+    else if (i < 2 * NV) w.st.v[i - NV] = x[i];
+    else if (i < 2 * NV + NJ) w.st.qddj[i - 2 * NV] = 0.0;
+    else w.st.W[i - 2 * NV - NJ] = 0.0;
+  }
+  contact_load(ctx, cp, b, w.ct);   // (its barrier closes the topology and the inputs)
+  stage_eval<false>(ctx, dm, w.st);
+  contact_forces(ctx, dm, w.st, w.ct);
+  WG_FOR(ctx, i, CT_PTS * 4) {
+    const int pt = i / 4, k = i % 4;
+    if (k < 3) { if (force) force[pt * 3 + k] = w.ct.f[pt][k]; }
+    else if (pen) pen[pt] = w.ct.d[pt];
+  }
+}
+
+}  // namespace hsqp

@@ -9,10 +9,13 @@
 //   bias:        nle_c = S_c . f^c_c;  the generalised force of a wrench {moment, force} about O on a body below c is S_c . wrench
 //   solve:       Cholesky of the system bordered by the right-hand side as row 29 (the forward substitution rides on the trailing updates),
 //                then one back substitution.  A pivot that is not positive makes the solution non-finite (HSQP_ROLLOUT_NONFINITE).
+// Ground contact (include/hsqp_contact.h, hsqp_contact.h): with the instance's ContactSet on, the prescribed contact wrenches Fx are dropped and the
+// wrenches of the eight sole corners, formed beside the push wrenches at the plant's own (q, v), take their place in the right-hand side.
 // Phase style of hsqp_common.h: the same source builds for the host with a one-lane context (tests/plant/plant_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
 #include "hsqp_push.h"
+#include "hsqp_contact.h"
 #include "../../include/hsqp_plant.h"
 
 namespace hsqp {
@@ -46,6 +49,13 @@ struct PlantStage {
   StageWST<false> st;
   PlantWS pl;
 };
+// ... and of the torque plant on the ground of include/hsqp_contact.h: contact is a parameter of the instantiation, not a run-time branch — the plant
+// without a ground is the code and the workspace it was before there was one
+struct PlantContactStage {
+  StageWST<false> st;
+  PlantWS pl;
+  ContactSet ct;                    // the instance's ground and the contact points of one evaluation
+};
 
 // instance b of the setting into the workspace
 HSQP_HD void plant_load(const Ctx& ctx, const PlantParams& pp, int b, int N, PlantWS& pl) {
@@ -77,10 +87,12 @@ HSQP_HD int plant_body(int c) { return c < 6 ? 0 : c - 5; }
 HSQP_HD int plant_end(const StageWST<false>& ws, int c) { return c < 6 ? NB : (c - 5) + (int)ws.sub[c - 5]; }
 
 // vd [NV] (into pl.vd) of the plant at the state and the contact wrenches stage_eval<false> has just been run on (qdd_j = 0), under the joint
-// torques pl.tau and the pushes `mask` of ps (0: none).  Ends with a barrier.
-HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, PlantWS& pl, PushSet& ps, unsigned mask) {
-  // ---- composites over the subtrees; the wrench {P x f, f} about O of every active push
-  WG_FOR(ctx, it, NB * 16 + HSQP_PUSH_MAX) {
+// torques pl.tau and the pushes `mask` of ps (0: none).  ct (null: none; a constant of the caller's instantiation, folded when this is inlined) —
+// the ground of the instance: its contact forces replace the contact wrenches.  Ends with a barrier.
+HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, PlantWS& pl, PushSet& ps, unsigned mask, ContactSet* ct = nullptr) {
+  // ---- composites over the subtrees; the wrench {P x f, f} about O of every active push and of every contact point
+  WG_FOR(ctx, it, NB * 16 + HSQP_PUSH_MAX + (ct ? CT_PTS : 0)) {
+    if (it >= NB * 16 + HSQP_PUSH_MAX) { contact_point(dm, ws, *ct, it - NB * 16 - HSQP_PUSH_MAX); continue; }
     if (it >= NB * 16) {
       const int i = it - NB * 16;
       if (!((mask >> i) & 1u)) continue;
@@ -98,7 +110,7 @@ HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST
     else { for (int i = b; i < end; ++i) s += ws.f[i][e - 10]; pl.fc[b][e - 10] = s; }
   }
   WG_SYNC(ctx);
-  // ---- per coordinate: I^c S, and the right-hand side  tau - S . (f^c - contact wrenches below - push wrenches below)  into the border row
+  // ---- per coordinate: I^c S, and the right-hand side  tau - S . (f^c - contact wrenches (or contact forces) below - push wrenches below)  into the border row
   WG_FOR(ctx, c, NV + 1) {
     if (c == NV) { pl.A[NV][NV] = 0.0; continue; }   // (the border's corner: carried through the updates, never used)
     const int b = plant_body(c), end = plant_end(ws, c);
@@ -108,7 +120,10 @@ HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST
     for (int k = 0; k < 6; ++k) F[k] = pl.fc[b][k];
     for (int f = 0; f < 2; ++f) {
       const int cb = dm.contact_body[f];
-      if (cb >= b && cb < end) for (int k = 0; k < 6; ++k) F[k] -= ws.Fx[f][k];
+      if (!(cb >= b && cb < end)) continue;
+      if (!ct) { for (int k = 0; k < 6; ++k) F[k] -= ws.Fx[f][k]; continue; }
+      for (int i = HSQP_CONTACT_CORNERS * f; i < HSQP_CONTACT_CORNERS * (f + 1); ++i)
+        for (int k = 0; k < 6; ++k) F[k] -= ct->wr[i][k];
     }
     for (int i = 0; i < HSQP_PUSH_MAX; ++i) {
       if (!((mask >> i) & 1u)) continue;

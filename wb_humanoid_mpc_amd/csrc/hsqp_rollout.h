@@ -16,6 +16,9 @@
 //   plant:       with the torque plant set (include/hsqp_plant.h, hsqp_plant.h) a second instantiation of the kernel — workspace
 //                RolloutWS<PlantStage> — replaces the flow evaluation by the compliant plant: full forward dynamics under the joint PD law,
 //                the pushes acting through the whole tree.  The instantiations above do not contain it.
+//   contact:     on that plant only, the ground of include/hsqp_contact.h (hsqp_contact.h): penalty forces at the eight sole corners in place of the
+//                policy's contact wrenches, inside every flow evaluation: a third instantiation, workspace RolloutWS<PlantContactStage>.  The
+//                plant without a ground keeps its own, which does not contain any of it.
 // The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp, tests/push/push_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
@@ -60,6 +63,7 @@ HSQP_HD bool ro_finite(double v) { return v - v == 0.0; }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws) { stage_topology(ctx, dm, ws); }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, CentWST<false>& ws) { cent_ws_topology(ctx, dm, ws); }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantStage& ws) { stage_topology(ctx, dm, ws.st); }
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantContactStage& ws) { stage_topology(ctx, dm, ws.st); }
 
 HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, const double* x, const double* u, double* xdot) {
   WG_FOR(ctx, i, NV + NV + NJ + 12) {
@@ -176,9 +180,12 @@ HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, 
 
 // The same with the torque plant (include/hsqp_plant.h; the workspace's plant setting was loaded by plant_load): the policy (x_p, u_p) at
 // s + lookahead — feedback: u_p = uff + K x at the measured plant state, x_p the interpolated nominal state —, tau_ff = joint_torques at
-// (x_p, u_p), the joint law, then forward dynamics at the plant's own state under the policy's contact wrenches and the pushes `mask`.
-HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantStage>& w, const RolloutPolicy& p, int controller, double s, const double* x,
-                          double* k, unsigned mask) {
+// (x_p, u_p), the joint law, then forward dynamics at the plant's own state under the policy's contact wrenches and the pushes `mask`.  With the
+// ground of include/hsqp_contact.h (workspace RolloutWS<PlantContactStage>, an instantiation of its own) the contact model's forces at
+// the plant's own (q, v) replace the policy's wrenches in the dynamics; tau_ff keeps them.
+template <class SW>
+HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, ContactSet* ct, const RolloutPolicy& p, int controller, double s,
+                                const double* x, double* k, unsigned mask) {
   PlantWS& pl = w.sw.pl;
   const double sl = s + pl.lookahead;
   rollout_control(ctx, p, controller, sl, x, w.u);
@@ -191,9 +198,17 @@ HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantSta
   WG_FOR(ctx, j, NJ) pl.tau[j] = (pl.tau[j] + pl.kp[j] * (pl.xp[6 + j] - x[6 + j])) + pl.kd[j] * (pl.xp[NV + 6 + j] - x[NV + 6 + j]);
   plant_inputs(ctx, w.sw.st, x, w.u, true);   // (its barrier also closes the joint law)
   stage_eval<false>(ctx, dm, w.sw.st);
-  plant_forward_dynamics(ctx, dm, w.sw.st, pl, w.push, mask);
+  plant_forward_dynamics(ctx, dm, w.sw.st, pl, w.push, mask, ct);
   WG_FOR(ctx, i, NX) k[i] = i < NV ? x[NV + i] : pl.vd[i - NV];
   WG_SYNC(ctx);
+}
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantStage>& w, const RolloutPolicy& p, int controller, double s, const double* x,
+                          double* k, unsigned mask) {
+  rollout_eval_plant(ctx, dm, w, nullptr, p, controller, s, x, k, mask);
+}
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantContactStage>& w, const RolloutPolicy& p, int controller, double s,
+                          const double* x, double* k, unsigned mask) {
+  rollout_eval_plant(ctx, dm, w, &w.sw.ct, p, controller, s, x, k, mask);
 }
 
 // whether any of the first n entries of rows r0 .. r1 - 1 of v (row stride NX) is not finite: a workgroup reduction, uniform

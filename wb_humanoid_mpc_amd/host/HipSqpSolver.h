@@ -21,6 +21,7 @@
 #include "../../include/hsqp_episode.h"
 #include "../../include/hsqp_push.h"
 #include "../../include/hsqp_plant.h"
+#include "../../include/hsqp_contact.h"
 
 namespace hsqp_host {
 
@@ -208,6 +209,42 @@ class HipSqpSolver {
     const int rc = hsqp_plant_get(h_, &s);
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_plant_get failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     return s;
+  }
+
+  /** ---- the ground under the torque plant (include/hsqp_contact.h): compliant contact with Coulomb friction at the eight sole corners, inside every
+   *  flow evaluation of rolloutPolicy and of the loop's cycles while the plant kind is HSQP_PLANT_TORQUE (stored and inert otherwise).
+   *  contactDefaults: hsqp_contact_defaults (mu: the model's friction_mu).  setContactInstances: (height, mu) per instance, an empty vector: back to
+   *  the setting's values.  contactForces: the model at the given states [B][58] — force [B][2][4][3] in world axes, penetration [B][2][4].  The MPC
+   *  never sees any of it. */
+  hsqp_contact_settings contactDefaults() const {
+    hsqp_contact_settings s;
+    hsqp_contact_defaults(h_, &s);
+    return s;
+  }
+  void setContact(const hsqp_contact_settings& settings) {
+    const int rc = hsqp_contact_set(h_, &settings);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_contact_set failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void setContactInstances(const std::vector<hsqp_contact_ground>& ground) {
+    const int rc = hsqp_contact_set_instances(h_, (int)ground.size(), ground.empty() ? nullptr : ground.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_contact_set_instances failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void clearContact() {
+    const int rc = hsqp_contact_clear(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_contact_clear failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  hsqp_contact_settings contact() {
+    hsqp_contact_settings s;
+    const int rc = hsqp_contact_get(h_, &s);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_contact_get failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return s;
+  }
+  void contactForces(const std::vector<double>& x, std::vector<double>& force, std::vector<double>& penetration) {
+    if (x.empty() || x.size() % HSQP_NX != 0) throw std::runtime_error("[HipSqpSolver] contactForces: states of HSQP_NX values each expected");
+    const size_t B = x.size() / HSQP_NX, pts = HSQP_CONTACT_FEET * HSQP_CONTACT_CORNERS;
+    force.assign(B * pts * 3, 0.0); penetration.assign(B * pts, 0.0);
+    const int rc = hsqp_contact_eval(h_, (int)B, x.data(), force.data(), penetration.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_contact_eval failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
   /** ---- the closed loop resident on the device (include/hsqp_loop.h): what ProceduralMpcMotionManager::preSolverRun's target generation, MPC_BASE::run

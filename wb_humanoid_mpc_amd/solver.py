@@ -109,6 +109,17 @@ def load_library():
     lib.hsqp_plant_set.argtypes = [C.c_void_p, _pl]
     lib.hsqp_plant_clear.argtypes = [C.c_void_p]
     lib.hsqp_plant_get.argtypes = [C.c_void_p, _pl]
+    # include/hsqp_contact.h
+    _cs, _cg = C.POINTER(_abi.ContactSettings), C.POINTER(_abi.ContactGround)
+    lib.hsqp_contact_defaults.argtypes = [C.c_void_p, _cs]
+    lib.hsqp_contact_defaults.restype = None
+    lib.hsqp_contact_set.argtypes = [C.c_void_p, _cs]
+    lib.hsqp_contact_set_instances.argtypes = [C.c_void_p, C.c_int, _cg]
+    lib.hsqp_contact_set_instances_device.argtypes = [C.c_void_p, C.c_int, _cg]
+    lib.hsqp_contact_clear.argtypes = [C.c_void_p]
+    lib.hsqp_contact_get.argtypes = [C.c_void_p, _cs]
+    lib.hsqp_contact_eval.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    lib.hsqp_contact_eval_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     # include/hsqp_loop.h
     _ls = C.POINTER(_abi.LoopSettings)
     lib.hsqp_set_default_joint_state.argtypes = [C.c_void_p, _dp]
@@ -582,6 +593,53 @@ class HipSqpSolver:
         self._check(self.lib.hsqp_plant_get(self.h, C.byref(st)))
         return dict(kind="torque" if st.kind == _abi.PLANT_TORQUE else "flow", lookahead=st.lookahead, kp=np.array(st.kp[:]), kd=np.array(st.kd[:]),
                     armature=np.array(st.armature[:]))
+
+    # ---- include/hsqp_contact.h: the ground under the torque plant
+    def contact_settings(self, enabled=True, stiffness=None, damping=None, mu=None, slip_velocity=None, ground_height=None, reserved=0):
+        """hsqp_contact_defaults (mu: the model's friction_mu) with the given fields replaced."""
+        st = _abi.ContactSettings()
+        self.lib.hsqp_contact_defaults(getattr(self, "h", None), C.byref(st))
+        st.enabled, st.reserved = int(bool(enabled)), int(reserved)
+        for name, v in (("stiffness", stiffness), ("damping", damping), ("mu", mu), ("slip_velocity", slip_velocity), ("ground_height", ground_height)):
+            if v is not None:
+                setattr(st, name, float(v))
+        return st
+
+    def set_contact(self, enabled=True, stiffness=None, damping=None, mu=None, slip_velocity=None, ground_height=None):
+        """hsqp_contact_set: compliant ground contact with Coulomb friction at the eight sole corners of the torque plant (set_plant("torque")); inert
+        on the flow plant.  It stays until clear_contact() or the next set_contact(); the MPC never sees it."""
+        st = self.contact_settings(enabled, stiffness, damping, mu, slip_velocity, ground_height)
+        self._check(self.lib.hsqp_contact_set(self.h, C.byref(st)))
+
+    def set_contact_instances(self, ground):
+        """hsqp_contact_set_instances: ground [B, 2] = (height, mu) of every instance, or None: every instance back to the setting's values."""
+        if ground is None:
+            self._check(self.lib.hsqp_contact_set_instances(self.h, 0, None))
+            return
+        g = _c(ground).reshape(-1, 2)
+        self._check(self.lib.hsqp_contact_set_instances(self.h, len(g), C.cast(g.ctypes.data_as(_dp), C.POINTER(_abi.ContactGround))))
+
+    def set_contact_instances_device(self, batch, ground_ptr):
+        """hsqp_contact_set_instances_device: the table in device memory (address); its values are not checked."""
+        self._check(self.lib.hsqp_contact_set_instances_device(self.h, int(batch), C.cast(C.c_void_p(int(ground_ptr)), C.POINTER(_abi.ContactGround))))
+
+    def clear_contact(self):
+        self._check(self.lib.hsqp_contact_clear(self.h))
+
+    def get_contact(self):
+        """hsqp_contact_get: dict(enabled, stiffness, damping, mu, slip_velocity, ground_height)."""
+        st = _abi.ContactSettings()
+        self._check(self.lib.hsqp_contact_get(self.h, C.byref(st)))
+        return dict(enabled=bool(st.enabled), stiffness=st.stiffness, damping=st.damping, mu=st.mu, slip_velocity=st.slip_velocity, ground_height=st.ground_height)
+
+    def contact_forces(self, x):
+        """hsqp_contact_eval at the states x [B, 58] with the handle's setting and table: (force [B, 2, 4, 3] on the feet in world axes — (ft_x, ft_y, fn)
+        per sole corner —, penetration [B, 2, 4]).  Needs no resident solution."""
+        x = _c(np.atleast_2d(x))
+        B = x.shape[0]
+        f, d = np.zeros((B, _abi.CONTACT_FEET, _abi.CONTACT_CORNERS, 3)), np.zeros((B, _abi.CONTACT_FEET, _abi.CONTACT_CORNERS))
+        self._check(self.lib.hsqp_contact_eval(self.h, B, x.ctypes.data_as(_dp), f.ctypes.data_as(_dp), d.ctypes.data_as(_dp)))
+        return f, d
 
     # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
     def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
