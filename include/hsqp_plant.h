@@ -27,9 +27,10 @@
  *
  * Stiffness: with the reference's gains the joint law has rates up to (M^-1)_jj kd ~ 3e4 1/s on the lightest joints (smallest joint
  * inertia 3.9e-4 kg m^2), so an explicit integrator needs steps of ~0.1 ms; simulators add rotor armature to the joint diagonal of M, which is
- * what `armature` is.  The controller is continuous (evaluated at every stage).  Not modelled: a sampled control rate, effort limits, joint
- * friction and damping, the centroidal formulation.  Contact and friction on the plant: hsqp_contact.h (a ground under the feet; with it set, the
- * prescribed wrenches of step 4 give way to the contact model's forces).
+ * what `armature` is.  The controller is continuous (evaluated at every stage) unless hsqp_actuator.h says otherwise: a sampled
+ * and held joint command, effort limits, joint friction and damping are that header's (its joint law replaces step 3).  Not modelled: the
+ * centroidal formulation.  Contact and friction on the plant: hsqp_contact.h (a ground under the feet; with it set, the prescribed wrenches of
+ * step 4 give way to the contact model's forces).
  *
  * Errors: HSQP_ERR_BAD_ARG, message in hsqp_last_error, for a NULL argument, a centroidal handle, an unknown kind, reserved != 0, and a
  * negative or non-finite lookahead, kp, kd or armature entry.

@@ -10,6 +10,7 @@ iteration and the rollout, and its rollout keeps no step counters).
                                       [--commands same|spread] [--gait ladder|walk] [--isolate park|reset] [--with-push NEWTONS]
                                       [--plant flow|torque] [--kp 100] [--kd 2] [--armature 0.01] [--lookahead 0.005]
                                       [--contact] [--stiffness 5e4] [--damping 10] [--mu MODEL] [--slip-velocity 0.01]
+                                      [--actuator] [--command-period 0.002] [--effort-limits FILE] [--joint-damping 0] [--joint-friction 0]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
                                       [--plant torque [--contact ...]]
 --with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
@@ -26,6 +27,11 @@ With --plant torque --contact the feet stand on the ground of include/hsqp_conta
 also prints each instance's peak total normal force and peak tangential / normal ratio, from contact_forces at the logged states.
 --contact: the ground under the torque plant (include/hsqp_contact.h; requires --plant torque): penalty contact with Coulomb friction at the eight
 sole corners, with the given stiffness [N/m per point], damping [s/m], friction coefficient (default: the model's) and slip velocity [m/s].
+--actuator: the actuator model on the torque plant (include/hsqp_actuator.h; requires --plant torque): the joint command sampled every
+--command-period seconds and held (0: the continuous controller), the actuator torque clamped to the limits of --effort-limits (a JSON object
+joint name -> N m, mapped through the model's joint names, e.g. tests/golden/g1_effort_limits.json; default: no limits), viscous damping
+[N m s/rad] and dry friction [N m] at every joint.  The line reports the setting and `saturated_share`: the share of the instances that end the
+run with |tau_cmd| above the limit at any joint (hsqp_actuator_last; instances without a record are not counted).
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -75,6 +81,8 @@ def push_sweep(args):
             s.set_plant(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead)
         if args.contact:
             s.set_contact(**contact_args(args))
+        if args.actuator:
+            s.set_actuator(**actuator_args(args, m))
         for controller in ("feedforward", "feedback"):
             st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True, controller=controller)
             s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
@@ -120,6 +128,26 @@ def contact_args(args):
     return dict(stiffness=args.stiffness, damping=args.damping, mu=args.mu, slip_velocity=args.slip_velocity)
 
 
+def actuator_args(args, m):
+    """The keywords of HipSqpSolver.set_actuator from the command line."""
+    limits = None
+    if args.effort_limits:
+        with open(args.effort_limits) as f:
+            table = json.load(f)
+        limits = [float(table[n]) for n in m.joint_names]
+    return dict(command_period=args.command_period, effort_limit=limits, damping=args.joint_damping, friction=args.joint_friction)
+
+
+def saturated_share(s, m, args):
+    """The share of the instances whose last record has |tau_cmd| above the limit at any joint."""
+    limits = actuator_args(args, m)["effort_limit"]
+    cmd = s.actuator_torques()[0]
+    live = np.isfinite(cmd).all(axis=1)
+    if limits is None or not live.any():
+        return 0.0
+    return round(float((np.abs(cmd[live]) > np.asarray(limits)).any(axis=1).mean()), 4)
+
+
 def rollout_probe(s, args, x_end):
     """One rollout over the period from the loop's last state on the resident policy: wall-clock ms (median of five calls) and step counts."""
     from wb_humanoid_mpc_amd.solver import HsqpError
@@ -162,12 +190,19 @@ def main():
     ap.add_argument("--damping", type=float, default=10.0)
     ap.add_argument("--mu", type=float, default=None)
     ap.add_argument("--slip-velocity", type=float, default=0.01)
+    ap.add_argument("--actuator", action="store_true")
+    ap.add_argument("--command-period", type=float, default=0.002)
+    ap.add_argument("--effort-limits", default=None, metavar="FILE")
+    ap.add_argument("--joint-damping", type=float, default=0.0)
+    ap.add_argument("--joint-friction", type=float, default=0.0)
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
     args = ap.parse_args()
     if args.contact and args.plant != "torque":
         ap.error("--contact requires --plant torque (the ground acts on the torque plant only)")
+    if args.actuator and args.plant != "torque":
+        ap.error("--actuator requires --plant torque (the actuator model acts on the torque plant only)")
     if args.push:
         return push_sweep(args)
     m = load_model()
@@ -210,6 +245,8 @@ def main():
             s.set_plant(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead)
         if args.contact:
             s.set_contact(**contact_args(args))
+        if args.actuator:
+            s.set_actuator(**actuator_args(args, m))
         for c in range(args.warmup + args.cycles):
             if c in changes:
                 s.loop_command(changes[c])
@@ -226,6 +263,7 @@ def main():
         rungs = np.bincount(s.gait_state()["rung"], minlength=7).tolist() if args.gait else None
         ep = s.loop_episodes() if args.isolate else None
         heights.append(x_end[:, 2].copy())
+        saturated = saturated_share(s, m, args) if args.actuator else None
         probe = rollout_probe(s, args, x_end) if args.plant else None
     finally:
         s.close()
@@ -234,7 +272,8 @@ def main():
     print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
                       "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
                       "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None,
-                      "contact": contact_args(args) if args.contact else None, "rollout_probe": probe,
+                      "contact": contact_args(args) if args.contact else None,
+                      "actuator": dict(actuator_args(args, m), effort_limits=args.effort_limits, saturated_share=saturated) if args.actuator else None, "rollout_probe": probe,
                       "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),

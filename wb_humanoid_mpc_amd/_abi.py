@@ -200,6 +200,17 @@ class ContactGround(C.Structure):   # hsqp_contact_ground
 CONTACT_ENTRY_POINTS = ("hsqp_contact_defaults", "hsqp_contact_set", "hsqp_contact_set_instances", "hsqp_contact_set_instances_device", "hsqp_contact_clear",
                         "hsqp_contact_get", "hsqp_contact_eval", "hsqp_contact_eval_device")
 
+
+# include/hsqp_actuator.h
+class ActuatorSettings(C.Structure):   # hsqp_actuator_settings
+    _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32), ("command_period", C.c_double), ("effort_limit", C.c_double * NJ),
+                ("damping", C.c_double * NJ), ("friction", C.c_double * NJ), ("friction_velocity", C.c_double)]
+
+
+# entry points of include/hsqp_actuator.h (tests/test_actuator.py checks that the library exports each of them and the binding declares it)
+ACTUATOR_ENTRY_POINTS = ("hsqp_actuator_defaults", "hsqp_actuator_set", "hsqp_actuator_clear", "hsqp_actuator_get", "hsqp_actuator_last",
+                         "hsqp_actuator_last_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

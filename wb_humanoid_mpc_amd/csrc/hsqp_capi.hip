@@ -1001,20 +1001,24 @@ static_assert(sizeof(RolloutWS<StageWST<false>>) <= 65536 && sizeof(RolloutWS<Ce
 // instead of k_rollout<StageWST<false>>, which does not contain it
 // SW = PlantStage: the plant as it is without a ground (cp is not read); SW = PlantContactStage: on the resident ground of include/hsqp_contact.h.
 // Contact is a parameter of the instantiation: as a run-time branch it costs the rollout without a ground 3.6 % (measured)
+// SW = PlantActStage / PlantContactActStage: either of them under the actuator model of include/hsqp_actuator.h (ap is read by these two only), again a
+// parameter of the instantiation; whether the command is held (ap.period > 0) is a run-time, workgroup-uniform branch inside them
 template <class SW>
-__global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp, ContactParams cp) {
+__global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp, ContactParams cp, ActuatorParams ap) {
   RolloutWS<SW>& w = *reinterpret_cast<RolloutWS<SW>*>(hsqp_smem);
   const int b = blockIdx.x;
   const Ctx ctx{(int)threadIdx.x, RO_THREADS, nullptr};
   const RolloutPolicy p{a.ut + (size_t)b * a.N * NU, a.dts ? a.dts + (size_t)b * a.N : nullptr, a.N, a.dt, a.K ? a.K + (size_t)b * a.count * NU * NX : nullptr,
                         a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count, 0};
   plant_load(ctx, pp, b, a.N, w.sw.pl);
-  if constexpr (std::is_same<SW, PlantContactStage>::value) contact_load(ctx, cp, b, w.sw.ct);
+  if constexpr (std::is_same<SW, PlantContactStage>::value || std::is_same<SW, PlantContactActStage>::value) contact_load(ctx, cp, b, w.sw.ct);
+  if constexpr (RolloutActuated<SW>::value) actuator_load(ctx, ap, b, w.sw.act);
   rollout_instance(ctx, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
                    a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr, a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
 static_assert(sizeof(RolloutWS<PlantStage>) <= 65536, "the rollout on the torque plant runs without a dynamic-LDS attribute");
 static_assert(sizeof(RolloutWS<PlantContactStage>) <= 65536, "the rollout on the torque plant over the ground runs without a dynamic-LDS attribute");
+static_assert(sizeof(RolloutWS<PlantActStage>) <= 65536 && sizeof(RolloutWS<PlantContactActStage>) <= 65536, "... and under the actuator model");
 // hsqp_contact_eval (include/hsqp_contact.h): one workgroup per instance — the contact model at a given state: stage topology, one stage_eval<false>
 // for the placements and the link velocities, the eight points
 __global__ __launch_bounds__(RO_THREADS) void k_contact_eval(const DevModel* __restrict__ dm, ContactParams cp, const double* __restrict__ x, double* __restrict__ force,
@@ -1164,6 +1168,11 @@ struct hsqp_handle {
   DevBuf<char> d_contact, d_contact_stage;   // d_contact_stage: staging of hsqp_contact_eval's host arrays (contact_stage_layout)
   int contact_B = 0;
   bool contact_current = false;
+  // the resident actuator model of the torque plant (include/hsqp_actuator.h): enabled = 0 until hsqp_actuator_set.  d_actuator (actuator_layout): the
+  // setting's table, and the record of the last torques; actuator_last_B: the batch of the rollout the record is of (0: none since the setting was made)
+  hsqp_actuator_settings actuator = [] { hsqp_actuator_settings a; hsqp_actuator_defaults(&a); a.enabled = 0; return a; }();
+  DevBuf<char> d_actuator;
+  int actuator_last_B = 0;
   bool stamps_resident = false;   // d_stamps[stamps_cur] holds the raw stamps of the resident problem (it came through hsqp_upload_reference or the loop): the pushes' clock
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
@@ -1289,6 +1298,9 @@ static PushBuf push_layout(Carve c, size_t B, size_t max_pushes) { return {c.tak
 // d_contact: the ground of every instance [max_batch]
 struct ContactBuf { hsqp_contact_ground* ground; size_t bytes; };
 static ContactBuf contact_layout(Carve c, size_t max_batch) { return {c.take<hsqp_contact_ground>(max_batch), c.bytes()}; }
+// d_actuator: effort_limit | damping | friction [NJ] each (one array: ActuatorParams::table), then the record tau_cmd | tau_act | tau_pas [NJ] each of every instance
+struct ActuatorBuf { double* table; double* last; size_t bytes; };
+static ActuatorBuf actuator_layout(Carve c, size_t max_batch) { return {c.take<double>(3 * NJ), c.take<double>(max_batch * 3 * NJ), c.bytes()}; }
 // d_contact_stage, hsqp_contact_eval (host arrays): x [B][58] | force [B][8][3] | penetration [B][8]
 struct ContactStage { double* x; double* force; double* pen; size_t bytes; };
 static ContactStage contact_stage_layout(Carve c, size_t B, bool want_force, bool want_pen) {
@@ -2414,10 +2426,20 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     if (rc != HSQP_OK) return rc;
   }
   const PlantParams pp{torque ? plant_gains(h->d_plant).kp : nullptr, h->plant.lookahead, (const double*)h->d_xnew};
-  if (torque && cp.ground)
-    HSQP_LAUNCH(k_rollout_plant<PlantContactStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactStage>), h->stream, h->d_dm, a, pp, cp);
+  ActuatorParams ap{nullptr, 0.0, 0.0, nullptr};
+  if (torque && h->actuator.enabled) {   // (hsqp_actuator_set made d_actuator)
+    const ActuatorBuf ab = actuator_layout(Carve{h->d_actuator.p}, (size_t)h->st.max_batch);
+    ap = ActuatorParams{ab.table, h->actuator.command_period, h->actuator.friction_velocity, ab.last};
+    h->actuator_last_B = 0;              // (a failure below leaves no record)
+  }
+  if (ap.table && cp.ground)
+    HSQP_LAUNCH(k_rollout_plant<PlantContactActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactActStage>), h->stream, h->d_dm, a, pp, cp, ap);
+  else if (ap.table)
+    HSQP_LAUNCH(k_rollout_plant<PlantActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantActStage>), h->stream, h->d_dm, a, pp, cp, ap);
+  else if (torque && cp.ground)
+    HSQP_LAUNCH(k_rollout_plant<PlantContactStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactStage>), h->stream, h->d_dm, a, pp, cp, ap);
   else if (torque)
-    HSQP_LAUNCH(k_rollout_plant<PlantStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, pp, cp);
+    HSQP_LAUNCH(k_rollout_plant<PlantStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, pp, cp, ap);
   else if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
   else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
   step(hipGetLastError(), "k_rollout");
@@ -2432,6 +2454,7 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
   }
   step(hipStreamSynchronize(h->stream), "sync");
   if (step.rc != HSQP_OK) return step.rc;
+  if (ap.table) h->actuator_last_B = (int)B;
   if (!dev) memcpy(status, hs.data(), B * 4);
   if (per_instance) return HSQP_OK;
   int nonfinite = -1, capped = -1;
@@ -2552,6 +2575,71 @@ int hsqp_plant_get(hsqp_handle* h, hsqp_plant_settings* s) {
   if (!s) { h->err = "hsqp_plant_get: null settings"; return HSQP_ERR_BAD_ARG; }
   *s = h->plant;
   return HSQP_OK;
+}
+
+// ---- the actuator model of the torque plant (include/hsqp_actuator.h, csrc/hsqp_actuator.h): the resident setting and the record of the last torques
+void hsqp_actuator_defaults(hsqp_actuator_settings* s) {
+  if (!s) return;
+  s->enabled = 1; s->reserved = 0;
+  s->command_period = 0.002;
+  for (int j = 0; j < NJ; ++j) { s->effort_limit[j] = std::numeric_limits<double>::infinity(); s->damping[j] = 0.0; s->friction[j] = 0.0; }
+  s->friction_velocity = 0.01;
+}
+int hsqp_actuator_set(hsqp_handle* h, const hsqp_actuator_settings* s) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const auto bad = [&](const std::string& what) { h->err = "hsqp_actuator_set: " + what; return HSQP_ERR_BAD_ARG; };
+  if (!s) return bad("null settings");
+  if (h->hdm.formulation != HSQP_FORM_WB) return bad("whole-body handles only (the actuator model acts on the torque plant of the whole-body tree)");
+  if (s->reserved != 0) return bad("reserved must be 0");
+  const auto ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
+  if (!ok(s->command_period)) return bad("negative or non-finite command_period");
+  for (int j = 0; j < NJ; ++j) {
+    if (!(s->effort_limit[j] > 0.0)) return bad("joint " + std::to_string(j) + ": effort_limit <= 0 or NaN");
+    if (!ok(s->damping[j])) return bad("joint " + std::to_string(j) + ": negative or non-finite damping");
+    if (!ok(s->friction[j])) return bad("joint " + std::to_string(j) + ": negative or non-finite friction");
+  }
+  if (!(s->friction_velocity > 0.0) || !std::isfinite(s->friction_velocity)) return bad("friction_velocity <= 0 or non-finite");
+  HCHECK(hipSetDevice(h->device));
+  const size_t mb = (size_t)h->st.max_batch;
+  double t[3 * NJ];
+  for (int j = 0; j < NJ; ++j) { t[j] = s->effort_limit[j]; t[NJ + j] = s->damping[j]; t[2 * NJ + j] = s->friction[j]; }
+  DEV_ENSURE(h->d_actuator, actuator_layout(Carve{}, mb).bytes, "actuator table and record");
+  HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the table that is replaced)
+  HCHECK(hipMemcpy(actuator_layout(Carve{h->d_actuator.p}, mb).table, t, sizeof(t), hipMemcpyHostToDevice));
+  h->actuator = *s;
+  h->actuator_last_B = 0;
+  return HSQP_OK;
+}
+int hsqp_actuator_clear(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  hsqp_actuator_defaults(&h->actuator);
+  h->actuator.enabled = 0;
+  h->actuator_last_B = 0;
+  return HSQP_OK;
+}
+int hsqp_actuator_get(hsqp_handle* h, hsqp_actuator_settings* s) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (!s) { h->err = "hsqp_actuator_get: null settings"; return HSQP_ERR_BAD_ARG; }
+  *s = h->actuator;
+  return HSQP_OK;
+}
+static int actuator_last_impl(hsqp_handle* h, int batch, double* cmd, double* act, double* pas, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_actuator_last_device" : "hsqp_actuator_last";
+  const auto bad = [&](const std::string& what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (!h->actuator_last_B) return bad("no rollout has run on the actuator model since it was set");
+  if (batch != h->actuator_last_B) return bad("batch " + std::to_string(batch) + ", the last rollout on the actuator model had " + std::to_string(h->actuator_last_B));
+  HCHECK(hipSetDevice(h->device));
+  const double* last = actuator_layout(Carve{h->d_actuator.p}, (size_t)h->st.max_batch).last;
+  double* const out[3] = {cmd, act, pas};
+  for (int r = 0; r < 3; ++r)   // row r of every instance's record [3][NJ] into its own array [batch][NJ]
+    if (out[r]) HCHECK(hipMemcpy2DAsync(out[r], NJ * 8, last + r * NJ, 3 * NJ * 8, NJ * 8, (size_t)batch, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_actuator_last(hsqp_handle* h, int batch, double* tau_cmd, double* tau_act, double* tau_passive) { return actuator_last_impl(h, batch, tau_cmd, tau_act, tau_passive, false); }
+int hsqp_actuator_last_device(hsqp_handle* h, int batch, double* d_tau_cmd, double* d_tau_act, double* d_tau_passive) {
+  return actuator_last_impl(h, batch, d_tau_cmd, d_tau_act, d_tau_passive, true);
 }
 
 // ---- the ground of the torque plant (include/hsqp_contact.h, csrc/hsqp_contact.h): the resident setting and the per-instance table

@@ -11,11 +11,14 @@
 //                then one back substitution.  A pivot that is not positive makes the solution non-finite (HSQP_ROLLOUT_NONFINITE).
 // Ground contact (include/hsqp_contact.h, hsqp_contact.h): with the instance's ContactSet on, the prescribed contact wrenches Fx are dropped and the
 // wrenches of the eight sole corners, formed beside the push wrenches at the plant's own (q, v), take their place in the right-hand side.
+// Actuator model (include/hsqp_actuator.h, hsqp_actuator.h): two more stage workspaces carry the instance's ActuatorWS — the held command, the limits and
+// the passive torques — beside the plant's; the forward dynamics below are the same under either joint law.
 // Phase style of hsqp_common.h: the same source builds for the host with a one-lane context (tests/plant/plant_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
 #include "hsqp_push.h"
 #include "hsqp_contact.h"
+#include "hsqp_actuator.h"
 #include "../../include/hsqp_plant.h"
 
 namespace hsqp {
@@ -55,6 +58,20 @@ struct PlantContactStage {
   StageWST<false> st;
   PlantWS pl;
   ContactSet ct;                    // the instance's ground and the contact points of one evaluation
+};
+
+// ... and either of them under the actuator model of include/hsqp_actuator.h: again a parameter of the instantiation — the two above are the code and
+// the workspace they were before there was one
+struct PlantActStage {
+  StageWST<false> st;
+  PlantWS pl;
+  ActuatorWS act;                   // the instance's actuator setting and the joint command in force
+};
+struct PlantContactActStage {
+  StageWST<false> st;
+  PlantWS pl;
+  ContactSet ct;
+  ActuatorWS act;
 };
 
 // instance b of the setting into the workspace

@@ -19,6 +19,10 @@
 //   contact:     on that plant only, the ground of include/hsqp_contact.h (hsqp_contact.h): penalty forces at the eight sole corners in place of the
 //                policy's contact wrenches, inside every flow evaluation: a third instantiation, workspace RolloutWS<PlantContactStage>.  The
 //                plant without a ground keeps its own, which does not contain any of it.
+//   actuator:    on that plant only, the actuator model of include/hsqp_actuator.h (hsqp_actuator.h): the joint command sampled at ticks and held, effort
+//                limits and passive joint torques.  Two more instantiations (RolloutWS<PlantActStage>, RolloutWS<PlantContactActStage>): in them
+//                rollout_instance drives the ticks — break points beside the events and the push edges — and writes the record of the last torques.
+//                No other instantiation contains any of it.
 // The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp, tests/push/push_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
@@ -64,6 +68,13 @@ HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, StageWST<false
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, CentWST<false>& ws) { cent_ws_topology(ctx, dm, ws); }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantStage& ws) { stage_topology(ctx, dm, ws.st); }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantContactStage& ws) { stage_topology(ctx, dm, ws.st); }
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantActStage& ws) { stage_topology(ctx, dm, ws.st); }
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantContactActStage& ws) { stage_topology(ctx, dm, ws.st); }
+
+// whether the stage workspace carries the actuator model (ws.act)
+template <class SW> struct RolloutActuated { static constexpr bool value = false; };
+template <> struct RolloutActuated<PlantActStage> { static constexpr bool value = true; };
+template <> struct RolloutActuated<PlantContactActStage> { static constexpr bool value = true; };
 
 HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, const double* x, const double* u, double* xdot) {
   WG_FOR(ctx, i, NV + NV + NJ + 12) {
@@ -183,9 +194,10 @@ HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, 
 // (x_p, u_p), the joint law, then forward dynamics at the plant's own state under the policy's contact wrenches and the pushes `mask`.  With the
 // ground of include/hsqp_contact.h (workspace RolloutWS<PlantContactStage>, an instantiation of its own) the contact model's forces at
 // the plant's own (q, v) replace the policy's wrenches in the dynamics; tau_ff keeps them.
+// rollout_plant_command: steps 1-2 of include/hsqp_plant.h at time s and the measured state x — (x_p, u_p) into pl.xp / w.u, tau_ff into pl.tau (no
+// barrier behind it); the plant's own joint law and the actuator model's command (below) both start from it.
 template <class SW>
-HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, ContactSet* ct, const RolloutPolicy& p, int controller, double s,
-                                const double* x, double* k, unsigned mask) {
+HSQP_HD void rollout_plant_command(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, int controller, double s, const double* x) {
   PlantWS& pl = w.sw.pl;
   const double sl = s + pl.lookahead;
   rollout_control(ctx, p, controller, sl, x, w.u);
@@ -195,6 +207,12 @@ HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW
   plant_inputs(ctx, w.sw.st, pl.xp, w.u, false);
   stage_eval<false>(ctx, dm, w.sw.st);
   joint_torques(ctx, dm, w.sw.st, pl.tau);
+}
+template <class SW>
+HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, ContactSet* ct, const RolloutPolicy& p, int controller, double s,
+                                const double* x, double* k, unsigned mask) {
+  PlantWS& pl = w.sw.pl;
+  rollout_plant_command(ctx, dm, w, p, controller, s, x);
   WG_FOR(ctx, j, NJ) pl.tau[j] = (pl.tau[j] + pl.kp[j] * (pl.xp[6 + j] - x[6 + j])) + pl.kd[j] * (pl.xp[NV + 6 + j] - x[NV + 6 + j]);
   plant_inputs(ctx, w.sw.st, x, w.u, true);   // (its barrier also closes the joint law)
   stage_eval<false>(ctx, dm, w.sw.st);
@@ -209,6 +227,54 @@ HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantSta
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantContactStage>& w, const RolloutPolicy& p, int controller, double s,
                           const double* x, double* k, unsigned mask) {
   rollout_eval_plant(ctx, dm, w, &w.sw.ct, p, controller, s, x, k, mask);
+}
+
+// The same under the actuator model (include/hsqp_actuator.h; the workspace's setting was loaded by actuator_load).
+// rollout_actuator_sample: the joint command of time s and the measured state x — steps 1-2 above — into the workspace, where it is held: at a
+// tick of a sampled command (rollout_instance), or at every evaluation of a continuous one.  Ends with a barrier.
+template <class SW>
+HSQP_HD void rollout_actuator_sample(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, int controller, double s, const double* x) {
+  PlantWS& pl = w.sw.pl;
+  ActuatorWS& ac = w.sw.act;
+  rollout_plant_command(ctx, dm, w, p, controller, s, x);
+  WG_FOR(ctx, j, NJ) { ac.tff[j] = pl.tau[j]; ac.qp[j] = pl.xp[6 + j]; ac.vp[j] = pl.xp[NV + 6 + j]; }
+  WG_FOR(ctx, i, 12) ac.Wp[i] = w.u[i];   // (w.u itself is the sample outputs' too: rollout_instance overwrites it)
+  WG_SYNC(ctx);
+}
+// one evaluation: the command in force (a continuous one is formed here), the joint law at the plant's own state, forward dynamics
+template <class SW>
+HSQP_HD void rollout_eval_actuated(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, ContactSet* ct, const RolloutPolicy& p, int controller, double s,
+                                   const double* x, double* k, unsigned mask) {
+  PlantWS& pl = w.sw.pl;
+  ActuatorWS& ac = w.sw.act;
+  if (!(ac.period > 0.0)) rollout_actuator_sample(ctx, dm, w, p, controller, s, x);
+  actuator_law(ctx, ac, pl.kp, pl.kd, x, pl.tau, nullptr);
+  plant_inputs(ctx, w.sw.st, x, ac.Wp, true);   // (reads the twelve wrenches only; its barrier also closes the joint law)
+  stage_eval<false>(ctx, dm, w.sw.st);
+  plant_forward_dynamics(ctx, dm, w.sw.st, pl, w.push, mask, ct);
+  WG_FOR(ctx, i, NX) k[i] = i < NV ? x[NV + i] : pl.vd[i - NV];
+  WG_SYNC(ctx);
+}
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantActStage>& w, const RolloutPolicy& p, int controller, double s, const double* x,
+                          double* k, unsigned mask) {
+  rollout_eval_actuated(ctx, dm, w, nullptr, p, controller, s, x, k, mask);
+}
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantContactActStage>& w, const RolloutPolicy& p, int controller, double s,
+                          const double* x, double* k, unsigned mask) {
+  rollout_eval_actuated(ctx, dm, w, &w.sw.ct, p, controller, s, x, k, mask);
+}
+// the record of include/hsqp_actuator.h at the instance's final state w.x (time s): the joint law once more under the command in force, or NaN rows
+template <class SW>
+HSQP_HD void rollout_actuator_record(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutPolicy& p, int controller, double s, bool ok) {
+  PlantWS& pl = w.sw.pl;
+  ActuatorWS& ac = w.sw.act;
+  WG_SYNC(ctx);   // (the sample outputs have been read from w.u)
+  if (!ok) {
+    WG_FOR(ctx, i, 3 * NJ) ac.rec[i] = __builtin_nan("");
+    return;
+  }
+  if (!(ac.period > 0.0)) rollout_actuator_sample(ctx, dm, w, p, controller, s, w.x);
+  actuator_law(ctx, ac, pl.kp, pl.kd, w.x, pl.tau, ac.rec);
 }
 
 // whether any of the first n entries of rows r0 .. r1 - 1 of v (row stride NX) is not finite: a workgroup reduction, uniform
@@ -366,6 +432,10 @@ HSQP_HD double rollout_next_event(const RolloutPolicy& p, const PushSet& ps, dou
   }
   return ps.n ? push_next_edge(ps, t, te) : te;
 }
+// ... or the next tick of a sampled joint command (include/hsqp_actuator.h; tick > t), whichever comes first
+HSQP_HD double rollout_next_event(const RolloutPolicy& p, const PushSet& ps, double t, double tb, double tick) {
+  return rollout_next_event(p, ps, t, tick < tb ? tick : tb);
+}
 
 // sample j of n: s0 + duration (j + 1) / n, the last one s0 + duration exactly
 HSQP_HD double rollout_sample_time(double s0, double duration, int j, int n) { return j + 1 == n ? s0 + duration : s0 + duration * (double)(j + 1) / (double)n; }
@@ -391,7 +461,20 @@ HSQP_HD void rollout_instance(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>&
       int acc = 0;
       double t = ta;
       while (stat == HSQP_ROLLOUT_OK && t < tb) {
-        const double te = rollout_next_event(p, w.push, t, tb);
+        double te;
+        if constexpr (RolloutActuated<SW>::value) {
+          // a sampled command: the command is taken where the segment starts on a tick (the call's start is tick 0), the next tick ends the segment
+          double tick = tb;
+          if (w.sw.act.period > 0.0) {
+            const ActuatorTick tk = actuator_tick(s0, w.sw.act.period, t);
+            if (!(tk.next > t) || !ro_finite(tk.next)) { stat = HSQP_ROLLOUT_MAX_STEPS; break; }
+            if (tk.on) rollout_actuator_sample(ctx, dm, w, p, st.controller, t, w.x);
+            tick = tk.next;
+          }
+          te = rollout_next_event(p, w.push, t, tb, tick);
+        } else {
+          te = rollout_next_event(p, w.push, t, tb);
+        }
         stat = rollout_segment(ctx, dm, w, p, st, t, te, cap, acc, nacc, nrej);
         t = te;
       }
@@ -406,6 +489,7 @@ HSQP_HD void rollout_instance(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>&
     if (uo) WG_FOR(ctx, r, NU) uo[(size_t)j * NU + r] = ok ? w.u[r] : nan;
     ta = tb;
   }
+  if constexpr (RolloutActuated<SW>::value) rollout_actuator_record(ctx, dm, w, p, st.controller, s0 + duration, stat == HSQP_ROLLOUT_OK);
   WG_FOR(ctx, i, 1) {
     *status = stat;
     if (steps) *steps = nacc;

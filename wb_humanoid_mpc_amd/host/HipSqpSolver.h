@@ -22,6 +22,7 @@
 #include "../../include/hsqp_push.h"
 #include "../../include/hsqp_plant.h"
 #include "../../include/hsqp_contact.h"
+#include "../../include/hsqp_actuator.h"
 
 namespace hsqp_host {
 
@@ -245,6 +246,38 @@ class HipSqpSolver {
     force.assign(B * pts * 3, 0.0); penetration.assign(B * pts, 0.0);
     const int rc = hsqp_contact_eval(h_, (int)B, x.data(), force.data(), penetration.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_contact_eval failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** ---- the actuator model on the torque plant (include/hsqp_actuator.h): the joint command sampled at a control rate and held, effort limits,
+   *  joint damping and dry friction, inside every flow evaluation of rolloutPolicy and of the loop's cycles while the plant is HSQP_PLANT_TORQUE.
+   *  actuatorDefaults: hsqp_actuator_defaults.  actuatorTorques: tau_cmd, tau_act, tau_passive [batch][23] each at the final state of the most
+   *  recent rollout (or loop cycle) on the model; NaN rows for an instance that did not end OK.  The MPC never sees any of it. */
+  static hsqp_actuator_settings actuatorDefaults() {
+    hsqp_actuator_settings s;
+    hsqp_actuator_defaults(&s);
+    return s;
+  }
+  void setActuator(const hsqp_actuator_settings& settings) {
+    const int rc = hsqp_actuator_set(h_, &settings);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_actuator_set failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void clearActuator() {
+    const int rc = hsqp_actuator_clear(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_actuator_clear failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  hsqp_actuator_settings actuator() {
+    hsqp_actuator_settings s;
+    const int rc = hsqp_actuator_get(h_, &s);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_actuator_get failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return s;
+  }
+  void actuatorTorques(int batch, std::vector<double>& tauCmd, std::vector<double>& tauAct, std::vector<double>& tauPassive) {
+    if (batch < 1) throw std::runtime_error("[HipSqpSolver] actuatorTorques: batch < 1");
+    tauCmd.resize((size_t)batch * HSQP_NJ);
+    tauAct.resize((size_t)batch * HSQP_NJ);
+    tauPassive.resize((size_t)batch * HSQP_NJ);
+    const int rc = hsqp_actuator_last(h_, batch, tauCmd.data(), tauAct.data(), tauPassive.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_actuator_last failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
   /** ---- the closed loop resident on the device (include/hsqp_loop.h): what ProceduralMpcMotionManager::preSolverRun's target generation, MPC_BASE::run

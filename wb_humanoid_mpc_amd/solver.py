@@ -120,6 +120,15 @@ def load_library():
     lib.hsqp_contact_get.argtypes = [C.c_void_p, _cs]
     lib.hsqp_contact_eval.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.hsqp_contact_eval_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    # include/hsqp_actuator.h
+    _as = C.POINTER(_abi.ActuatorSettings)
+    lib.hsqp_actuator_defaults.argtypes = [_as]
+    lib.hsqp_actuator_defaults.restype = None
+    lib.hsqp_actuator_set.argtypes = [C.c_void_p, _as]
+    lib.hsqp_actuator_clear.argtypes = [C.c_void_p]
+    lib.hsqp_actuator_get.argtypes = [C.c_void_p, _as]
+    lib.hsqp_actuator_last.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    lib.hsqp_actuator_last_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     # include/hsqp_loop.h
     _ls = C.POINTER(_abi.LoopSettings)
     lib.hsqp_set_default_joint_state.argtypes = [C.c_void_p, _dp]
@@ -640,6 +649,48 @@ class HipSqpSolver:
         f, d = np.zeros((B, _abi.CONTACT_FEET, _abi.CONTACT_CORNERS, 3)), np.zeros((B, _abi.CONTACT_FEET, _abi.CONTACT_CORNERS))
         self._check(self.lib.hsqp_contact_eval(self.h, B, x.ctypes.data_as(_dp), f.ctypes.data_as(_dp), d.ctypes.data_as(_dp)))
         return f, d
+
+    # ---- include/hsqp_actuator.h: the actuator model on the torque plant
+    def actuator_settings(self, enabled=True, command_period=None, effort_limit=None, damping=None, friction=None, friction_velocity=None, reserved=0):
+        """hsqp_actuator_defaults with the given fields replaced (effort_limit, damping, friction: a scalar for every joint or 23 values)."""
+        st = _abi.ActuatorSettings()
+        self.lib.hsqp_actuator_defaults(C.byref(st))
+        st.enabled, st.reserved = int(bool(enabled)), int(reserved)
+        if command_period is not None:
+            st.command_period = float(command_period)
+        if friction_velocity is not None:
+            st.friction_velocity = float(friction_velocity)
+        for name, v in (("effort_limit", effort_limit), ("damping", damping), ("friction", friction)):
+            if v is not None:
+                getattr(st, name)[:] = [float(e) for e in np.broadcast_to(np.asarray(v, dtype=float), (_abi.NJ,))]
+        return st
+
+    def set_actuator(self, enabled=True, command_period=None, effort_limit=None, damping=None, friction=None, friction_velocity=None):
+        """hsqp_actuator_set: the actuator model of the torque plant (set_plant("torque")) — the joint command sampled every command_period seconds
+        and held (0: continuous), the actuator torque clamped to +-effort_limit, viscous damping and regularised dry friction at the joints; inert
+        on the flow plant.  It stays until clear_actuator() or the next set_actuator(); the MPC never sees it."""
+        st = self.actuator_settings(enabled, command_period, effort_limit, damping, friction, friction_velocity)
+        self._check(self.lib.hsqp_actuator_set(self.h, C.byref(st)))
+
+    def clear_actuator(self):
+        self._check(self.lib.hsqp_actuator_clear(self.h))
+
+    def get_actuator(self):
+        """hsqp_actuator_get: dict(enabled, command_period, effort_limit [23], damping [23], friction [23], friction_velocity)."""
+        st = _abi.ActuatorSettings()
+        self._check(self.lib.hsqp_actuator_get(self.h, C.byref(st)))
+        return dict(enabled=bool(st.enabled), command_period=st.command_period, effort_limit=np.array(st.effort_limit[:]), damping=np.array(st.damping[:]),
+                    friction=np.array(st.friction[:]), friction_velocity=st.friction_velocity)
+
+    def actuator_torques(self, batch=None):
+        """hsqp_actuator_last: (tau_cmd, tau_act, tau_passive) [batch, 23] each at the final state of the most recent rollout (or loop cycle) on the
+        actuator model (batch None: the resident problem's); NaN rows for an instance that did not end OK.  |tau_cmd| > effort_limit: the joint
+        is saturated."""
+        if batch is None:
+            batch = self._shape[0] if self._shape else 1
+        out = [np.zeros((int(batch), _abi.NJ)) for _ in range(3)]
+        self._check(self.lib.hsqp_actuator_last(self.h, int(batch), *(o.ctypes.data_as(_dp) for o in out)))
+        return tuple(out)
 
     # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
     def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
