@@ -29,7 +29,8 @@
  * inertia 3.9e-4 kg m^2), so an explicit integrator needs steps of ~0.1 ms; simulators add rotor armature to the joint diagonal of M, which is
  * what `armature` is.  The controller is continuous (evaluated at every stage) unless hsqp_actuator.h says otherwise: a sampled
  * and held joint command, effort limits, joint friction and damping are that header's (its joint law replaces step 3).  Not modelled: the
- * centroidal formulation.  Contact and friction on the plant: hsqp_contact.h (a ground under the feet; with it set, the prescribed wrenches of
+ * centroidal formulation.  The plant's inertial parameters are the model's unless hsqp_inertia.h gives an instance its own (link mass scales,
+ * payloads).  Contact and friction on the plant: hsqp_contact.h (a ground under the feet; with it set, the prescribed wrenches of
  * step 4 give way to the contact model's forces).
  *
  * Errors: HSQP_ERR_BAD_ARG, message in hsqp_last_error, for a NULL argument, a centroidal handle, an unknown kind, reserved != 0, and a

@@ -11,8 +11,9 @@ iteration and the rollout, and its rollout keeps no step counters).
                                       [--plant flow|torque] [--kp 100] [--kd 2] [--armature 0.01] [--lookahead 0.005]
                                       [--contact] [--stiffness 5e4] [--damping 10] [--mu MODEL] [--slip-velocity 0.01]
                                       [--actuator] [--command-period 0.002] [--effort-limits FILE] [--joint-damping 0] [--joint-friction 0]
+                                      [--inertia] [--mass-spread 0.15] [--payload KG]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
-                                      [--plant torque [--contact ...]]
+                                      [--plant torque [--contact ...] [--actuator ...] [--inertia ...]]
 --with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
 --plant: the plant of the loop's rollout (include/hsqp_plant.h).  torque: full forward dynamics under the joint PD law with the given gains
 (defaults: the gains of the tests); flow: the MPC's own flow map, set explicitly.  With --plant the line also carries `rollout_probe`: after the
@@ -32,6 +33,10 @@ sole corners, with the given stiffness [N/m per point], damping [s/m], friction 
 joint name -> N m, mapped through the model's joint names, e.g. tests/golden/g1_effort_limits.json; default: no limits), viscous damping
 [N m s/rad] and dry friction [N m] at every joint.  The line reports the setting and `saturated_share`: the share of the instances that end the
 run with |tau_cmd| above the limit at any joint (hsqp_actuator_last; instances without a record are not counted).
+--inertia: per-instance inertial variations of the torque PLANT (include/hsqp_inertia.h; requires --plant torque): instance b has every link's mass and
+rotational inertia scaled by 1 + spread (2 b / (B - 1) - 1), spread = --mass-spread (0: no scaling), and with --payload KG carries a point mass of
+KG kilograms at the origin of the torso link.  The MPC keeps the nominal model: this is the model mismatch.  The timing mode and the --push sweep
+both honour it; either prints, per instance, the plant's total mass (plant_dynamics) and whether the instance finished the run.
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -83,6 +88,9 @@ def push_sweep(args):
             s.set_contact(**contact_args(args))
         if args.actuator:
             s.set_actuator(**actuator_args(args, m))
+        if args.inertia:
+            s.set_inertia_instances(*inertia_args(args, B))
+            masses = s.plant_dynamics(x_init)[2]
         for controller in ("feedforward", "feedback"):
             st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True, controller=controller)
             s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
@@ -110,6 +118,9 @@ def push_sweep(args):
         print(f"plant {args.plant}: kp {args.kp} kd {args.kd} armature {args.armature} lookahead {args.lookahead}" + (f"; contact {contact_args(args)}" if args.contact else ""))
     extra = f" {'peak fn [N]':>12} {'peak ft/fn':>10}" if args.contact else ""
     print(f"{'instance':>8} {'force [N]':>10} | " + " | ".join(f"{c + ': state':>20} {'cycle':>6} {'sway [m]':>9}" + extra for c in rows))
+    if args.inertia:
+        for b in range(B):
+            print(f"instance {b}: total mass {masses[b]:.3f} kg, finished " + ", ".join(f"{c}: {'no' if ep['n_failures'][b] else 'yes'}" for c, (ep, _) in rows.items()))
     for b in range(B):
         cells = []
         for c, (ep, sway) in rows.items():
@@ -118,6 +129,7 @@ def push_sweep(args):
         print(f"{b:8d} {force[b]:10.1f} | " + " | ".join(cells))
     print(json.dumps({"metric": "push_sweep", "batch": B, "nodes": N, "cycles": cycles, "forces": [round(float(f), 2) for f in force],
                       "plant": args.plant, "contact": contact_args(args) if args.contact else None,
+                      "inertia": dict(mass_spread=args.mass_spread, payload=args.payload, total_mass=[round(float(v), 3) for v in masses]) if args.inertia else None,
                       **({"peak_normal_force": {c: [round(float(v), 1) for v in g[0]] for c, g in ground.items()},
                           "peak_tangential_ratio": {c: [round(float(v), 3) for v in g[1]] for c, g in ground.items()}} if args.contact else {}),
                       **{c: {"failed": [int(b) for b in np.nonzero(ep["n_failures"])[0]], "fail_cycle": [int(v) for v in ep["fail_cycle"]]} for c, (ep, _) in rows.items()}}))
@@ -136,6 +148,16 @@ def actuator_args(args, m):
             table = json.load(f)
         limits = [float(table[n]) for n in m.joint_names]
     return dict(command_period=args.command_period, effort_limit=limits, damping=args.joint_damping, friction=args.joint_friction)
+
+
+TORSO_LINK = 15   # the torso of the G1 tree (data/g1_wb.json)
+
+
+def inertia_args(args, B):
+    """(mass_scale [B], payloads) of HipSqpSolver.set_inertia_instances from the command line."""
+    scale = 1.0 + args.mass_spread * (2.0 * np.arange(B) / max(B - 1, 1) - 1.0) if B > 1 else np.ones(1)
+    payloads = [[dict(body=TORSO_LINK, mass=args.payload)] for _ in range(B)] if args.payload is not None else None
+    return scale, payloads
 
 
 def saturated_share(s, m, args):
@@ -195,6 +217,9 @@ def main():
     ap.add_argument("--effort-limits", default=None, metavar="FILE")
     ap.add_argument("--joint-damping", type=float, default=0.0)
     ap.add_argument("--joint-friction", type=float, default=0.0)
+    ap.add_argument("--inertia", action="store_true")
+    ap.add_argument("--mass-spread", type=float, default=0.15)
+    ap.add_argument("--payload", type=float, default=None, metavar="KG")
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -203,6 +228,11 @@ def main():
         ap.error("--contact requires --plant torque (the ground acts on the torque plant only)")
     if args.actuator and args.plant != "torque":
         ap.error("--actuator requires --plant torque (the actuator model acts on the torque plant only)")
+    given = {a.split("=")[0] for a in sys.argv[1:]}
+    if not args.inertia and given & {"--mass-spread", "--payload"}:
+        ap.error("--mass-spread and --payload belong to --inertia (without it nothing is varied)")
+    if args.inertia and args.plant != "torque":
+        ap.error("--inertia requires --plant torque (the inertial variations act on the torque plant only)")
     if args.push:
         return push_sweep(args)
     m = load_model()
@@ -247,6 +277,10 @@ def main():
             s.set_contact(**contact_args(args))
         if args.actuator:
             s.set_actuator(**actuator_args(args, m))
+        masses = None
+        if args.inertia:
+            s.set_inertia_instances(*inertia_args(args, B))
+            masses = s.plant_dynamics(x_init)[2]
         for c in range(args.warmup + args.cycles):
             if c in changes:
                 s.loop_command(changes[c])
@@ -269,11 +303,17 @@ def main():
         s.close()
     heights = np.concatenate(heights)
     q = np.percentile(cycle_ms, [25, 75])
+    finished = np.isfinite(x_end).all(axis=1) & ((ep["state"] == 0) if ep else True)
+    if args.inertia:
+        for b in range(B):
+            print(f"instance {b}: total mass {masses[b]:.3f} kg, finished {'yes' if finished[b] else 'no'}")
     print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
                       "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
                       "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None,
                       "contact": contact_args(args) if args.contact else None,
-                      "actuator": dict(actuator_args(args, m), effort_limits=args.effort_limits, saturated_share=saturated) if args.actuator else None, "rollout_probe": probe,
+                      "actuator": dict(actuator_args(args, m), effort_limits=args.effort_limits, saturated_share=saturated) if args.actuator else None,
+                      "inertia": dict(mass_spread=args.mass_spread, payload=args.payload, total_mass_range=[round(float(masses.min()), 3), round(float(masses.max()), 3)],
+                                      finished=int(finished.sum())) if args.inertia else None, "rollout_probe": probe,
                       "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),

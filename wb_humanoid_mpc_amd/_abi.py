@@ -211,6 +211,23 @@ class ActuatorSettings(C.Structure):   # hsqp_actuator_settings
 ACTUATOR_ENTRY_POINTS = ("hsqp_actuator_defaults", "hsqp_actuator_set", "hsqp_actuator_clear", "hsqp_actuator_get", "hsqp_actuator_last",
                          "hsqp_actuator_last_device")
 
+
+# include/hsqp_inertia.h
+INERTIA_PAYLOADS = 2
+
+
+class InertiaPayload(C.Structure):   # hsqp_inertia_payload
+    _fields_ = [("body", C.c_int32), ("reserved", C.c_int32), ("mass", C.c_double), ("com", C.c_double * 3), ("inertia", C.c_double * 6)]
+
+
+class InertiaInstance(C.Structure):   # hsqp_inertia_instance
+    _fields_ = [("mass_scale", C.c_double * NB), ("n_payloads", C.c_int32), ("reserved", C.c_int32), ("payload", InertiaPayload * INERTIA_PAYLOADS)]
+
+
+# entry points of include/hsqp_inertia.h (tests/test_inertia.py checks that the library exports each of them and the binding declares it)
+INERTIA_ENTRY_POINTS = ("hsqp_inertia_defaults", "hsqp_inertia_set_instances", "hsqp_inertia_set_instances_device", "hsqp_inertia_clear",
+                        "hsqp_inertia_get_instances", "hsqp_inertia_eval", "hsqp_inertia_eval_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

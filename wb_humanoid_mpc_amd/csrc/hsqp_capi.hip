@@ -1003,22 +1003,38 @@ static_assert(sizeof(RolloutWS<StageWST<false>>) <= 65536 && sizeof(RolloutWS<Ce
 // Contact is a parameter of the instantiation: as a run-time branch it costs the rollout without a ground 3.6 % (measured)
 // SW = PlantActStage / PlantContactActStage: either of them under the actuator model of include/hsqp_actuator.h (ap is read by these two only), again a
 // parameter of the instantiation; whether the command is held (ap.period > 0) is a run-time, workgroup-uniform branch inside them
+// SW = PlantVaried<...> of any of the four: on the per-instance inertial variations of include/hsqp_inertia.h (ip is read by these four only), once more a
+// parameter of the instantiation: the handle launches them only while a table is set
 template <class SW>
-__global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp, ContactParams cp, ActuatorParams ap) {
+__global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp, ContactParams cp, ActuatorParams ap,
+                                                              InertiaParams ip) {
   RolloutWS<SW>& w = *reinterpret_cast<RolloutWS<SW>*>(hsqp_smem);
   const int b = blockIdx.x;
   const Ctx ctx{(int)threadIdx.x, RO_THREADS, nullptr};
   const RolloutPolicy p{a.ut + (size_t)b * a.N * NU, a.dts ? a.dts + (size_t)b * a.N : nullptr, a.N, a.dt, a.K ? a.K + (size_t)b * a.count * NU * NX : nullptr,
                         a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count, 0};
   plant_load(ctx, pp, b, a.N, w.sw.pl);
-  if constexpr (std::is_same<SW, PlantContactStage>::value || std::is_same<SW, PlantContactActStage>::value) contact_load(ctx, cp, b, w.sw.ct);
+  if constexpr (PlantGrounded<SW>::value) contact_load(ctx, cp, b, w.sw.ct);
   if constexpr (RolloutActuated<SW>::value) actuator_load(ctx, ap, b, w.sw.act);
+  if constexpr (PlantIsVaried<SW>::value) inertia_load(ctx, ip, b, w.sw.iw);
   rollout_instance(ctx, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
                    a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr, a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
 static_assert(sizeof(RolloutWS<PlantStage>) <= 65536, "the rollout on the torque plant runs without a dynamic-LDS attribute");
 static_assert(sizeof(RolloutWS<PlantContactStage>) <= 65536, "the rollout on the torque plant over the ground runs without a dynamic-LDS attribute");
 static_assert(sizeof(RolloutWS<PlantActStage>) <= 65536 && sizeof(RolloutWS<PlantContactActStage>) <= 65536, "... and under the actuator model");
+static_assert(sizeof(RolloutWS<PlantVaried<PlantStage>>) <= 65536 && sizeof(RolloutWS<PlantVaried<PlantContactStage>>) <= 65536 &&
+              sizeof(RolloutWS<PlantVaried<PlantActStage>>) <= 65536 && sizeof(RolloutWS<PlantVaried<PlantContactActStage>>) <= 65536, "... and on a varied plant");
+// hsqp_inertia_eval (include/hsqp_inertia.h): one workgroup per instance — the plant's mass matrix, bias forces and total mass at a given state: stage
+// topology, one stage_eval<false>, the instance's variation, the assembly of the plant's bordered system
+__global__ __launch_bounds__(RO_THREADS) void k_inertia_eval(const DevModel* __restrict__ dm, InertiaParams ip, const double* __restrict__ x, double* __restrict__ M,
+                                                             double* __restrict__ nle, double* __restrict__ mass) {
+  InertiaEvalWS& w = *reinterpret_cast<InertiaEvalWS*>(hsqp_smem);
+  const int b = blockIdx.x;
+  const Ctx ctx{(int)threadIdx.x, RO_THREADS, nullptr};
+  inertia_eval_instance(ctx, *dm, w, ip, b, x + (size_t)b * NX, M ? M + (size_t)b * NV * NV : nullptr, nle ? nle + (size_t)b * NV : nullptr, mass ? mass + b : nullptr);
+}
+static_assert(sizeof(InertiaEvalWS) <= 65536, "hsqp_inertia_eval runs without a dynamic-LDS attribute");
 // hsqp_contact_eval (include/hsqp_contact.h): one workgroup per instance — the contact model at a given state: stage topology, one stage_eval<false>
 // for the placements and the link velocities, the eight points
 __global__ __launch_bounds__(RO_THREADS) void k_contact_eval(const DevModel* __restrict__ dm, ContactParams cp, const double* __restrict__ x, double* __restrict__ force,
@@ -1173,6 +1189,10 @@ struct hsqp_handle {
   hsqp_actuator_settings actuator = [] { hsqp_actuator_settings a; hsqp_actuator_defaults(&a); a.enabled = 0; return a; }();
   DevBuf<char> d_actuator;
   int actuator_last_B = 0;
+  // the resident inertial variations of the torque plant (include/hsqp_inertia.h).  d_inertia (inertia_layout): the entry of every instance [max_batch] — the
+  // first inertia_B the table's, the rest neutral; inertia_B = 0: no table.  d_inertia_stage: staging of hsqp_inertia_eval's host arrays (inertia_stage_layout)
+  DevBuf<char> d_inertia, d_inertia_stage;
+  int inertia_B = 0;
   bool stamps_resident = false;   // d_stamps[stamps_cur] holds the raw stamps of the resident problem (it came through hsqp_upload_reference or the loop): the pushes' clock
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
@@ -1301,6 +1321,14 @@ static ContactBuf contact_layout(Carve c, size_t max_batch) { return {c.take<hsq
 // d_actuator: effort_limit | damping | friction [NJ] each (one array: ActuatorParams::table), then the record tau_cmd | tau_act | tau_pas [NJ] each of every instance
 struct ActuatorBuf { double* table; double* last; size_t bytes; };
 static ActuatorBuf actuator_layout(Carve c, size_t max_batch) { return {c.take<double>(3 * NJ), c.take<double>(max_batch * 3 * NJ), c.bytes()}; }
+// d_inertia: the inertial variation of every instance [max_batch]
+struct InertiaBuf { hsqp_inertia_instance* table; size_t bytes; };
+static InertiaBuf inertia_layout(Carve c, size_t max_batch) { return {c.take<hsqp_inertia_instance>(max_batch), c.bytes()}; }
+// d_inertia_stage, hsqp_inertia_eval (host arrays): x [B][58] | M [B][29][29] | nle [B][29] | mass [B]
+struct InertiaStage { double* x; double* M; double* nle; double* mass; size_t bytes; };
+static InertiaStage inertia_stage_layout(Carve c, size_t B, bool want_M, bool want_nle, bool want_mass) {
+  return {c.take<double>(B * NX), c.take<double>(B * NV * NV, want_M), c.take<double>(B * NV, want_nle), c.take<double>(B, want_mass), c.bytes()};
+}
 // d_contact_stage, hsqp_contact_eval (host arrays): x [B][58] | force [B][8][3] | penetration [B][8]
 struct ContactStage { double* x; double* force; double* pen; size_t bytes; };
 static ContactStage contact_stage_layout(Carve c, size_t B, bool want_force, bool want_pen) {
@@ -2432,14 +2460,24 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     ap = ActuatorParams{ab.table, h->actuator.command_period, h->actuator.friction_velocity, ab.last};
     h->actuator_last_B = 0;              // (a failure below leaves no record)
   }
-  if (ap.table && cp.ground)
-    HSQP_LAUNCH(k_rollout_plant<PlantContactActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactActStage>), h->stream, h->d_dm, a, pp, cp, ap);
+  // (hsqp_inertia_set_instances* made d_inertia; the table acts on the torque plant only)
+  const InertiaParams ip{torque && h->inertia_B ? inertia_layout(Carve{h->d_inertia.p}, (size_t)h->st.max_batch).table : nullptr};
+  if (ip.table && ap.table && cp.ground)
+    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantContactActStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantContactActStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
+  else if (ip.table && ap.table)
+    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantActStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantActStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
+  else if (ip.table && cp.ground)
+    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantContactStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantContactStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
+  else if (ip.table)
+    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
+  else if (ap.table && cp.ground)
+    HSQP_LAUNCH(k_rollout_plant<PlantContactActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactActStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
   else if (ap.table)
-    HSQP_LAUNCH(k_rollout_plant<PlantActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantActStage>), h->stream, h->d_dm, a, pp, cp, ap);
+    HSQP_LAUNCH(k_rollout_plant<PlantActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantActStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
   else if (torque && cp.ground)
-    HSQP_LAUNCH(k_rollout_plant<PlantContactStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactStage>), h->stream, h->d_dm, a, pp, cp, ap);
+    HSQP_LAUNCH(k_rollout_plant<PlantContactStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
   else if (torque)
-    HSQP_LAUNCH(k_rollout_plant<PlantStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, pp, cp, ap);
+    HSQP_LAUNCH(k_rollout_plant<PlantStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
   else if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
   else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
   step(hipGetLastError(), "k_rollout");
@@ -2761,6 +2799,131 @@ static int contact_eval_impl(hsqp_handle* h, int batch, const double* x, double*
 int hsqp_contact_eval(hsqp_handle* h, int batch, const double* x, double* force, double* penetration) { return contact_eval_impl(h, batch, x, force, penetration, false); }
 int hsqp_contact_eval_device(hsqp_handle* h, int batch, const double* d_x, double* d_force, double* d_penetration) {
   return contact_eval_impl(h, batch, d_x, d_force, d_penetration, true);
+}
+
+// ---- per-instance inertial variations of the torque plant (include/hsqp_inertia.h, csrc/hsqp_inertia.h): the resident table and the evaluation
+void hsqp_inertia_defaults(hsqp_inertia_instance* v) {
+  if (!v) return;
+  memset(v, 0, sizeof(*v));
+  for (int i = 0; i < NB; ++i) v->mass_scale[i] = 1.0;
+}
+static int inertia_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) { h->err = std::string(who) + ": whole-body handles only (the variations act on the torque plant of the whole-body tree)"; return HSQP_ERR_BAD_ARG; }
+  return HSQP_OK;
+}
+// what is wrong with one entry ("" : nothing)
+static std::string inertia_entry_error(const hsqp_inertia_instance& e) {
+  for (int i = 0; i < NB; ++i)
+    if (!(e.mass_scale[i] > 0.0) || !std::isfinite(e.mass_scale[i])) return "mass_scale[" + std::to_string(i) + "] <= 0 or non-finite";
+  if (e.reserved != 0) return "reserved must be 0";
+  if (e.n_payloads < 0 || e.n_payloads > HSQP_INERTIA_PAYLOADS) return "n_payloads outside [0, " + std::to_string(HSQP_INERTIA_PAYLOADS) + "]";
+  for (int p = 0; p < e.n_payloads; ++p) {
+    const hsqp_inertia_payload& pl = e.payload[p];
+    const std::string at = "payload " + std::to_string(p) + ": ";
+    if (pl.reserved != 0) return at + "reserved must be 0";
+    if (pl.body < 0 || pl.body >= NB) return at + "body outside [0, " + std::to_string(NB) + ")";
+    if (!(pl.mass >= 0.0) || !std::isfinite(pl.mass)) return at + "mass negative or non-finite";
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(pl.com[k])) return at + "com non-finite";
+    for (int k = 0; k < 6; ++k) if (!std::isfinite(pl.inertia[k])) return at + "inertia non-finite";
+    // positive semidefinite: every principal minor of [xx xy xz; xy yy yz; xz yz zz] is >= 0, up to the rounding of a rank-deficient tensor (a rod, a
+    // plate) that was rotated into the link's axes: 16 eps of the scale tr^2 of a 2 x 2 minor, tr^3 of the determinant
+    const double xx = pl.inertia[0], xy = pl.inertia[1], xz = pl.inertia[2], yy = pl.inertia[3], yz = pl.inertia[4], zz = pl.inertia[5];
+    const double det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
+    const double tr = xx + yy + zz, slack = 16.0 * std::numeric_limits<double>::epsilon();
+    const double m2 = -slack * tr * tr, m3 = -slack * tr * tr * tr;
+    if (xx < 0.0 || yy < 0.0 || zz < 0.0 || xx * yy - xy * xy < m2 || xx * zz - xz * xz < m2 || yy * zz - yz * yz < m2 || det < m3)
+      return at + "inertia not positive semidefinite";
+  }
+  return "";
+}
+static int inertia_set_instances_impl(hsqp_handle* h, int batch, const hsqp_inertia_instance* t, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_inertia_set_instances_device" : "hsqp_inertia_set_instances";
+  const auto bad = [&](const std::string& what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = inertia_handle_ok(h, who)) return rc;
+  if (!t) {
+    if (batch < 0 || batch > h->st.max_batch) return bad("batch outside [0, max_batch]");
+    h->inertia_B = 0;
+    return HSQP_OK;
+  }
+  if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+  if (!dev)
+    for (int b = 0; b < batch; ++b) {
+      const std::string what = inertia_entry_error(t[b]);
+      if (!what.empty()) return bad("instance " + std::to_string(b) + ": " + what);
+    }
+  HCHECK(hipSetDevice(h->device));
+  const size_t mb = (size_t)h->st.max_batch;
+  DEV_ENSURE(h->d_inertia, inertia_layout(Carve{}, mb).bytes, "inertia table");
+  hsqp_inertia_instance* d = inertia_layout(Carve{h->d_inertia.p}, mb).table;
+  hsqp_inertia_instance neutral;
+  hsqp_inertia_defaults(&neutral);
+  const std::vector<hsqp_inertia_instance> fill(mb - (size_t)batch, neutral);
+  HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the entries that are replaced)
+  h->inertia_B = 0;                          // (a failure below leaves no table)
+  HCHECK(hipMemcpy(d, t, (size_t)batch * sizeof(hsqp_inertia_instance), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  if (!fill.empty()) HCHECK(hipMemcpy(d + batch, fill.data(), fill.size() * sizeof(hsqp_inertia_instance), hipMemcpyHostToDevice));
+  h->inertia_B = batch;
+  return HSQP_OK;
+}
+int hsqp_inertia_set_instances(hsqp_handle* h, int batch, const hsqp_inertia_instance* table) { return inertia_set_instances_impl(h, batch, table, false); }
+int hsqp_inertia_set_instances_device(hsqp_handle* h, int batch, const hsqp_inertia_instance* d_table) { return inertia_set_instances_impl(h, batch, d_table, true); }
+int hsqp_inertia_clear(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (const int rc = inertia_handle_ok(h, "hsqp_inertia_clear")) return rc;
+  h->inertia_B = 0;
+  return HSQP_OK;
+}
+int hsqp_inertia_get_instances(hsqp_handle* h, int batch, hsqp_inertia_instance* table) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_inertia_get_instances";
+  const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = inertia_handle_ok(h, who)) return rc;
+  if (!table) return bad("null table");
+  if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+  const int have = batch < h->inertia_B ? batch : h->inertia_B;
+  if (have) {
+    HCHECK(hipSetDevice(h->device));
+    HCHECK(hipStreamSynchronize(h->stream));
+    HCHECK(hipMemcpy(table, inertia_layout(Carve{h->d_inertia.p}, (size_t)h->st.max_batch).table, (size_t)have * sizeof(hsqp_inertia_instance), hipMemcpyDeviceToHost));
+  }
+  for (int b = have; b < batch; ++b) hsqp_inertia_defaults(table + b);
+  return HSQP_OK;
+}
+static int inertia_eval_impl(hsqp_handle* h, int batch, const double* x, double* M, double* nle, double* mass, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_inertia_eval_device" : "hsqp_inertia_eval";
+  const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = inertia_handle_ok(h, who)) return rc;
+  if (!x) return bad("null states");
+  if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+  HCHECK(hipSetDevice(h->device));
+  const InertiaParams ip{h->inertia_B ? inertia_layout(Carve{h->d_inertia.p}, (size_t)h->st.max_batch).table : nullptr};
+  const size_t B = (size_t)batch;
+  const double* d_x = x;
+  double* d_M = M;
+  double* d_n = nle;
+  double* d_m = mass;
+  StickyError step{h};
+  if (!dev) {
+    DEV_ENSURE(h->d_inertia_stage, inertia_stage_layout(Carve{}, B, M, nle, mass).bytes, "inertia staging");
+    const InertiaStage sg = inertia_stage_layout(Carve{h->d_inertia_stage.p}, B, M, nle, mass);
+    d_x = sg.x; d_M = sg.M; d_n = sg.nle; d_m = sg.mass;
+    step(hipMemcpyAsync(sg.x, x, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
+  }
+  HSQP_LAUNCH(k_inertia_eval, dim3(batch), dim3(RO_THREADS), sizeof(InertiaEvalWS), h->stream, h->d_dm, ip, d_x, d_M, d_n, d_m);
+  step(hipGetLastError(), "k_inertia_eval");
+  if (!dev) {
+    if (M) step(hipMemcpyAsync(M, d_M, B * NV * NV * 8, hipMemcpyDeviceToHost, h->stream), "download M");
+    if (nle) step(hipMemcpyAsync(nle, d_n, B * NV * 8, hipMemcpyDeviceToHost, h->stream), "download nle");
+    if (mass) step(hipMemcpyAsync(mass, d_m, B * 8, hipMemcpyDeviceToHost, h->stream), "download mass");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+int hsqp_inertia_eval(hsqp_handle* h, int batch, const double* x, double* M, double* nle, double* mass) { return inertia_eval_impl(h, batch, x, M, nle, mass, false); }
+int hsqp_inertia_eval_device(hsqp_handle* h, int batch, const double* d_x, double* d_M, double* d_nle, double* d_mass) {
+  return inertia_eval_impl(h, batch, d_x, d_M, d_nle, d_mass, true);
 }
 
 static int loop_bad(hsqp_handle* h, const char* who, const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; }

@@ -13,12 +13,17 @@
 // wrenches of the eight sole corners, formed beside the push wrenches at the plant's own (q, v), take their place in the right-hand side.
 // Actuator model (include/hsqp_actuator.h, hsqp_actuator.h): two more stage workspaces carry the instance's ActuatorWS — the held command, the limits and
 // the passive torques — beside the plant's; the forward dynamics below are the same under either joint law.
+// Inertial variations (include/hsqp_inertia.h, hsqp_inertia.h): four more stage workspaces, PlantVaried<...> of the four above, carry the instance's
+// InertiaWS; in them inertia_apply runs between stage_eval<false> and the composites.  plant_forward_dynamics<false> stops behind the assembly (the
+// filled bordered system), which is what hsqp_inertia_eval reads; it is ONE function body with a compile-time flag, not two functions: split in two,
+// the four rollout kernels that existed before compiled to another schedule of the right-hand-side phase and measured 3.8 % slower.
 // Phase style of hsqp_common.h: the same source builds for the host with a one-lane context (tests/plant/plant_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
 #include "hsqp_push.h"
 #include "hsqp_contact.h"
 #include "hsqp_actuator.h"
+#include "hsqp_inertia.h"
 #include "../../include/hsqp_plant.h"
 
 namespace hsqp {
@@ -74,6 +79,20 @@ struct PlantContactActStage {
   ActuatorWS act;
 };
 
+// ... and any of the four under the per-instance inertial variations of include/hsqp_inertia.h: once more a parameter of the instantiation — the four
+// above are the code and the workspace they were before there was a table
+template <class Base>
+struct PlantVaried : Base {
+  InertiaWS iw;                     // the instance's link scales and payloads
+};
+// whether the stage workspace carries the ground (ws.ct), the inertial variation (ws.iw)
+template <class SW> struct PlantGrounded { static constexpr bool value = false; };
+template <> struct PlantGrounded<PlantContactStage> { static constexpr bool value = true; };
+template <> struct PlantGrounded<PlantContactActStage> { static constexpr bool value = true; };
+template <class Base> struct PlantGrounded<PlantVaried<Base>> : PlantGrounded<Base> {};
+template <class SW> struct PlantIsVaried { static constexpr bool value = false; };
+template <class Base> struct PlantIsVaried<PlantVaried<Base>> { static constexpr bool value = true; };
+
 // instance b of the setting into the workspace
 HSQP_HD void plant_load(const Ctx& ctx, const PlantParams& pp, int b, int N, PlantWS& pl) {
   WG_FOR(ctx, i, 3 * NJ + 1) {
@@ -106,6 +125,9 @@ HSQP_HD int plant_end(const StageWST<false>& ws, int c) { return c < 6 ? NB : (c
 // vd [NV] (into pl.vd) of the plant at the state and the contact wrenches stage_eval<false> has just been run on (qdd_j = 0), under the joint
 // torques pl.tau and the pushes `mask` of ps (0: none).  ct (null: none; a constant of the caller's instantiation, folded when this is inlined) —
 // the ground of the instance: its contact forces replace the contact wrenches.  Ends with a barrier.
+// SOLVE = false: the assembly only — the bordered system pl.A is left as it is filled: rows 0 .. NV - 1 the mass matrix with the armature pl.arm, both
+// triangles; row NV the right-hand side; pl.Ic[0][0] the total mass.
+template <bool SOLVE = true>
 HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, PlantWS& pl, PushSet& ps, unsigned mask, ContactSet* ct = nullptr) {
   // ---- composites over the subtrees; the wrench {P x f, f} about O of every active push and of every contact point
   WG_FOR(ctx, it, NB * 16 + HSQP_PUSH_MAX + (ct ? CT_PTS : 0)) {
@@ -166,6 +188,7 @@ HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST
     pl.A[i][j] = m;
   }
   WG_SYNC(ctx);
+  if (!SOLVE) return;
   // ---- Cholesky of the leading NV x NV block, the border row eliminated along: after step k the border holds y_k = (L^-1 rhs)_k
   for (int k = 0; k < NV; ++k) {
     WG_FOR(ctx, i, PL_N - k) {
@@ -193,6 +216,38 @@ HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST
     }
   }
   WG_SYNC(ctx);
+}
+
+// The workspace of hsqp_inertia_eval: the stage's, the plant's and the instance's variation (push: never read, the assembly runs with no push active)
+struct InertiaEvalWS {
+  StageWST<false> st;
+  PlantWS pl;
+  InertiaWS iw;
+  PushSet push;
+};
+
+// hsqp_inertia_eval for one instance: the plant's inertial model at state x [58] with instance b of the table (null: the nominal model) — M [29][29]
+// without armature, nle [29] (the right-hand side under tau = 0, no wrenches, no pushes, negated), mass [1]; any may be null
+HSQP_HD void inertia_eval_instance(const Ctx& ctx, const DevModel& dm, InertiaEvalWS& w, const InertiaParams& ip, int b, const double* x, double* M, double* nle,
+                                   double* mass) {
+  stage_topology(ctx, dm, w.st, false);
+  WG_FOR(ctx, i, NV + NV + NJ + 12 + 2 * NJ) {
+    if (i < NV) w.st.q[i] = x[i];
+    else if (i < 2 * NV) w.st.v[i - NV] = x[i];
+    else if (i < 2 * NV + NJ) w.st.qddj[i - 2 * NV] = 0.0;
+    else if (i < 2 * NV + NJ + 12) w.st.W[i - 2 * NV - NJ] = 0.0;
+    else if (i < 2 * NV + 2 * NJ + 12) w.pl.tau[i - 2 * NV - NJ - 12] = 0.0;
+    else w.pl.arm[i - 2 * NV - 2 * NJ - 12] = 0.0;
+  }
+  inertia_load(ctx, ip, b, w.iw);   // (its barrier closes the topology and the inputs)
+  stage_eval<false>(ctx, dm, w.st);
+  inertia_apply(ctx, w.st, w.iw);
+  plant_forward_dynamics<false>(ctx, dm, w.st, w.pl, w.push, 0u);
+  WG_FOR(ctx, it, NV * NV + NV + 1) {
+    if (it < NV * NV) { if (M) M[it] = w.pl.A[it / NV][it % NV]; }
+    else if (it < NV * NV + NV) { if (nle) nle[it - NV * NV] = -w.pl.A[NV][it - NV * NV]; }
+    else if (mass) *mass = w.pl.Ic[0][0];
+  }
 }
 
 }  // namespace hsqp

@@ -23,6 +23,9 @@
 //                limits and passive joint torques.  Two more instantiations (RolloutWS<PlantActStage>, RolloutWS<PlantContactActStage>): in them
 //                rollout_instance drives the ticks — break points beside the events and the push edges — and writes the record of the last torques.
 //                No other instantiation contains any of it.
+//   inertia:     on that plant only, the per-instance link scales and payloads of include/hsqp_inertia.h (hsqp_inertia.h): four more instantiations,
+//                RolloutWS<PlantVaried<...>> of the four plant workspaces, in which inertia_apply follows the stage_eval<false> at the plant's own
+//                state in every flow evaluation; the policy and tau_ff stay on the nominal model.  No other instantiation contains any of it.
 // The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp, tests/push/push_emu.cpp).
 #pragma once
 #include "hsqp_policy.h"
@@ -75,6 +78,7 @@ HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantContactAc
 template <class SW> struct RolloutActuated { static constexpr bool value = false; };
 template <> struct RolloutActuated<PlantActStage> { static constexpr bool value = true; };
 template <> struct RolloutActuated<PlantContactActStage> { static constexpr bool value = true; };
+template <class Base> struct RolloutActuated<PlantVaried<Base>> : RolloutActuated<Base> {};
 
 HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, const double* x, const double* u, double* xdot) {
   WG_FOR(ctx, i, NV + NV + NJ + 12) {
@@ -216,6 +220,7 @@ HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW
   WG_FOR(ctx, j, NJ) pl.tau[j] = (pl.tau[j] + pl.kp[j] * (pl.xp[6 + j] - x[6 + j])) + pl.kd[j] * (pl.xp[NV + 6 + j] - x[NV + 6 + j]);
   plant_inputs(ctx, w.sw.st, x, w.u, true);   // (its barrier also closes the joint law)
   stage_eval<false>(ctx, dm, w.sw.st);
+  if constexpr (PlantIsVaried<SW>::value) inertia_apply(ctx, w.sw.st, w.sw.iw);   // (the plant's own body: include/hsqp_inertia.h)
   plant_forward_dynamics(ctx, dm, w.sw.st, pl, w.push, mask, ct);
   WG_FOR(ctx, i, NX) k[i] = i < NV ? x[NV + i] : pl.vd[i - NV];
   WG_SYNC(ctx);
@@ -251,6 +256,7 @@ HSQP_HD void rollout_eval_actuated(const Ctx& ctx, const DevModel& dm, RolloutWS
   actuator_law(ctx, ac, pl.kp, pl.kd, x, pl.tau, nullptr);
   plant_inputs(ctx, w.sw.st, x, ac.Wp, true);   // (reads the twelve wrenches only; its barrier also closes the joint law)
   stage_eval<false>(ctx, dm, w.sw.st);
+  if constexpr (PlantIsVaried<SW>::value) inertia_apply(ctx, w.sw.st, w.sw.iw);   // (the plant's own body: include/hsqp_inertia.h)
   plant_forward_dynamics(ctx, dm, w.sw.st, pl, w.push, mask, ct);
   WG_FOR(ctx, i, NX) k[i] = i < NV ? x[NV + i] : pl.vd[i - NV];
   WG_SYNC(ctx);
@@ -262,6 +268,15 @@ HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantAct
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantContactActStage>& w, const RolloutPolicy& p, int controller, double s,
                           const double* x, double* k, unsigned mask) {
   rollout_eval_actuated(ctx, dm, w, &w.sw.ct, p, controller, s, x, k, mask);
+}
+// ... and any of the four on a varied plant (include/hsqp_inertia.h; the workspace's entry was loaded by inertia_load)
+template <class Base>
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantVaried<Base>>& w, const RolloutPolicy& p, int controller, double s, const double* x,
+                          double* k, unsigned mask) {
+  ContactSet* ct = nullptr;
+  if constexpr (PlantGrounded<Base>::value) ct = &w.sw.ct;
+  if constexpr (RolloutActuated<Base>::value) rollout_eval_actuated(ctx, dm, w, ct, p, controller, s, x, k, mask);
+  else rollout_eval_plant(ctx, dm, w, ct, p, controller, s, x, k, mask);
 }
 // the record of include/hsqp_actuator.h at the instance's final state w.x (time s): the joint law once more under the command in force, or NaN rows
 template <class SW>

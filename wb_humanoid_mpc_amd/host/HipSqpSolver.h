@@ -23,6 +23,7 @@
 #include "../../include/hsqp_plant.h"
 #include "../../include/hsqp_contact.h"
 #include "../../include/hsqp_actuator.h"
+#include "../../include/hsqp_inertia.h"
 
 namespace hsqp_host {
 
@@ -278,6 +279,39 @@ class HipSqpSolver {
     tauPassive.resize((size_t)batch * HSQP_NJ);
     const int rc = hsqp_actuator_last(h_, batch, tauCmd.data(), tauAct.data(), tauPassive.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_actuator_last failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** ---- per-instance inertial variations of the torque PLANT (include/hsqp_inertia.h): link mass scales and up to HSQP_INERTIA_PAYLOADS rigid payloads per
+   *  instance, inside every flow evaluation of rolloutPolicy and of the loop's cycles while the plant is HSQP_PLANT_TORQUE (stored and inert otherwise).
+   *  inertiaDefaults: the neutral entry.  setInertiaInstances: one entry per instance, an empty vector: no table.  inertiaInstances: the entries in
+   *  force (past the table: neutral).  plantDynamics: at the states [B][58] with instance b's entry — M [B][29][29] without armature, nle [B][29],
+   *  mass [B].  The MPC, jointTorques and tau_ff keep the nominal model: that is the mismatch being modelled. */
+  static hsqp_inertia_instance inertiaDefaults() {
+    hsqp_inertia_instance v;
+    hsqp_inertia_defaults(&v);
+    return v;
+  }
+  void setInertiaInstances(const std::vector<hsqp_inertia_instance>& table) {
+    const int rc = hsqp_inertia_set_instances(h_, (int)table.size(), table.empty() ? nullptr : table.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_inertia_set_instances failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void clearInertia() {
+    const int rc = hsqp_inertia_clear(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_inertia_clear failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  std::vector<hsqp_inertia_instance> inertiaInstances(int batch) {
+    if (batch < 1) throw std::runtime_error("[HipSqpSolver] inertiaInstances: batch < 1");
+    std::vector<hsqp_inertia_instance> table((size_t)batch);
+    const int rc = hsqp_inertia_get_instances(h_, batch, table.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_inertia_get_instances failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return table;
+  }
+  void plantDynamics(const std::vector<double>& x, std::vector<double>& M, std::vector<double>& nle, std::vector<double>& mass) {
+    if (x.empty() || x.size() % HSQP_NX != 0) throw std::runtime_error("[HipSqpSolver] plantDynamics: states of HSQP_NX values each expected");
+    const size_t B = x.size() / HSQP_NX;
+    M.assign(B * HSQP_NV * HSQP_NV, 0.0); nle.assign(B * HSQP_NV, 0.0); mass.assign(B, 0.0);
+    const int rc = hsqp_inertia_eval(h_, (int)B, x.data(), M.data(), nle.data(), mass.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_inertia_eval failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
   /** ---- the closed loop resident on the device (include/hsqp_loop.h): what ProceduralMpcMotionManager::preSolverRun's target generation, MPC_BASE::run

@@ -129,6 +129,16 @@ def load_library():
     lib.hsqp_actuator_get.argtypes = [C.c_void_p, _as]
     lib.hsqp_actuator_last.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.hsqp_actuator_last_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    # include/hsqp_inertia.h
+    _ii = C.POINTER(_abi.InertiaInstance)
+    lib.hsqp_inertia_defaults.argtypes = [_ii]
+    lib.hsqp_inertia_defaults.restype = None
+    lib.hsqp_inertia_set_instances.argtypes = [C.c_void_p, C.c_int, _ii]
+    lib.hsqp_inertia_set_instances_device.argtypes = [C.c_void_p, C.c_int, _ii]
+    lib.hsqp_inertia_clear.argtypes = [C.c_void_p]
+    lib.hsqp_inertia_get_instances.argtypes = [C.c_void_p, C.c_int, _ii]
+    lib.hsqp_inertia_eval.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+    lib.hsqp_inertia_eval_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     # include/hsqp_loop.h
     _ls = C.POINTER(_abi.LoopSettings)
     lib.hsqp_set_default_joint_state.argtypes = [C.c_void_p, _dp]
@@ -691,6 +701,69 @@ class HipSqpSolver:
         out = [np.zeros((int(batch), _abi.NJ)) for _ in range(3)]
         self._check(self.lib.hsqp_actuator_last(self.h, int(batch), *(o.ctypes.data_as(_dp) for o in out)))
         return tuple(out)
+
+    # ---- include/hsqp_inertia.h: per-instance link mass scales and rigid payloads of the torque plant
+    @staticmethod
+    def pack_inertia(mass_scale, payloads=None):
+        """The table of hsqp_inertia_set_instances as a ctypes array: mass_scale [B, 24], or [B] broadcast over the links; payloads: per instance a list
+        of dict(body, mass, com [3], inertia [6] = xx, xy, xz, yy, yz, zz about its own centre of mass; com and inertia default to zero), or None."""
+        ms = np.asarray(mass_scale, dtype=float)
+        if ms.ndim == 1:
+            ms = np.repeat(ms[:, None], _abi.NB, axis=1)
+        if ms.ndim != 2 or ms.shape[1] != _abi.NB:
+            raise ValueError("mass_scale: [B, %d] or [B]" % _abi.NB)
+        B = ms.shape[0]
+        if payloads is not None and len(payloads) != B:
+            raise ValueError("payloads: one list per instance")
+        tab = (_abi.InertiaInstance * B)()
+        for b in range(B):
+            tab[b].mass_scale[:] = [float(v) for v in ms[b]]
+            mine = list(payloads[b]) if payloads is not None else []
+            if len(mine) > _abi.INERTIA_PAYLOADS:
+                raise ValueError("instance %d: more than %d payloads" % (b, _abi.INERTIA_PAYLOADS))
+            tab[b].n_payloads = len(mine)
+            for i, p in enumerate(mine):
+                q = tab[b].payload[i]
+                q.body, q.reserved, q.mass = int(p["body"]), int(p.get("reserved", 0)), float(p["mass"])
+                q.com[:] = [float(v) for v in p.get("com", (0.0, 0.0, 0.0))]
+                q.inertia[:] = [float(v) for v in p.get("inertia", (0.0,) * 6)]
+        return tab
+
+    def set_inertia_instances(self, mass_scale, payloads=None):
+        """hsqp_inertia_set_instances: the inertial variation of every instance's torque PLANT (set_plant("torque")) — link i's mass and rotational
+        inertia times mass_scale[b, i], and up to two rigid payloads per instance (pack_inertia); None: no table.  Inert on the flow plant.  It
+        stays until clear_inertia() or the next call; the MPC never sees it."""
+        if mass_scale is None:
+            self._check(self.lib.hsqp_inertia_set_instances(self.h, 0, None))
+            return
+        tab = self.pack_inertia(mass_scale, payloads)
+        self._check(self.lib.hsqp_inertia_set_instances(self.h, len(tab), tab))
+
+    def set_inertia_instances_device(self, batch, table_ptr):
+        """hsqp_inertia_set_instances_device: the table in device memory (address); its values are not checked."""
+        self._check(self.lib.hsqp_inertia_set_instances_device(self.h, int(batch), C.cast(C.c_void_p(int(table_ptr)), C.POINTER(_abi.InertiaInstance))))
+
+    def clear_inertia(self):
+        self._check(self.lib.hsqp_inertia_clear(self.h))
+
+    def get_inertia_instances(self, batch):
+        """hsqp_inertia_get_instances: (mass_scale [batch, 24], payloads: per instance a list of dict(body, mass, com, inertia)); instances past the
+        table are neutral."""
+        tab = (_abi.InertiaInstance * int(batch))()
+        self._check(self.lib.hsqp_inertia_get_instances(self.h, int(batch), tab))
+        ms = np.array([list(t.mass_scale) for t in tab])
+        pay = [[dict(body=int(t.payload[i].body), mass=t.payload[i].mass, com=list(t.payload[i].com), inertia=list(t.payload[i].inertia))
+                for i in range(min(max(int(t.n_payloads), 0), _abi.INERTIA_PAYLOADS))] for t in tab]   # (an unchecked device table: clamped as the kernels do)
+        return ms, pay
+
+    def plant_dynamics(self, x):
+        """hsqp_inertia_eval at the states x [B, 58] with instance b's entry of the table (none: the nominal model): (M [B, 29, 29] the plant's mass
+        matrix without armature, nle [B, 29] its bias forces, mass [B] its total mass).  Needs no resident solution."""
+        x = _c(np.atleast_2d(x))
+        B = x.shape[0]
+        M, nle, mass = np.zeros((B, _abi.NV, _abi.NV)), np.zeros((B, _abi.NV)), np.zeros(B)
+        self._check(self.lib.hsqp_inertia_eval(self.h, B, x.ctypes.data_as(_dp), M.ctypes.data_as(_dp), nle.ctypes.data_as(_dp), mass.ctypes.data_as(_dp)))
+        return M, nle, mass
 
     # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
     def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
