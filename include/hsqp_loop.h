@@ -52,6 +52,8 @@
  *
  * The gait auto-transition of preSolverRun (transitionToFasterGait / ...Slower...) and the re-tiling of the schedule in every cycle are in
  * include/hsqp_gait.h: hsqp_loop_start_gait starts this loop with a per-instance gait schedule and ladder resident on the device.
+ * The measured state x of steps 1 and 2 IS the plant's state unless include/hsqp_observe.h says otherwise: a resident observation model (bias,
+ * noise, sensor and compute delay) between the plant's state and everything the MPC reads; with none set the cycle is exactly the one above.
  * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, event grids (hsqp_reference::node_times), the
  * centroidal formulation, several GPUs.
  *

@@ -12,6 +12,7 @@ iteration and the rollout, and its rollout keeps no step counters).
                                       [--contact] [--stiffness 5e4] [--damping 10] [--mu MODEL] [--slip-velocity 0.01]
                                       [--actuator] [--command-period 0.002] [--effort-limits FILE] [--joint-damping 0] [--joint-friction 0]
                                       [--inertia] [--mass-spread 0.15] [--payload KG]
+                                      [--observe] [--obs-noise 0.005] [--obs-bias 0.02] [--sensor-delay 1] [--compute-delay 1] [--obs-seed 2026]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
                                       [--plant torque [--contact ...] [--actuator ...] [--inertia ...]]
 --with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
@@ -37,6 +38,13 @@ run with |tau_cmd| above the limit at any joint (hsqp_actuator_last; instances w
 rotational inertia scaled by 1 + spread (2 b / (B - 1) - 1), spread = --mass-spread (0: no scaling), and with --payload KG carries a point mass of
 KG kilograms at the origin of the torso link.  The MPC keeps the nominal model: this is the model mismatch.  The timing mode and the --push sweep
 both honour it; either prints, per instance, the plant's total mass (plant_dynamics) and whether the instance finished the run.
+--observe: the observation model of the loop (include/hsqp_observe.h): the MPC measures the plant with white noise of standard deviation --obs-noise
+on every state entry (rad, m, rad/s, m/s), a bias of --obs-bias metres on the base height, --sensor-delay periods it does not know about and
+--compute-delay periods it does.  The timed run has the model on; the same run is then repeated with the model off, and the line carries, side by
+side, the tracking of the commanded planar velocity (`tracking_on`, `tracking_off`: the error |v_base - R(yaw) v_cmd| in m/s, mean over the instances
+and the timed cycles, and over the instances at the end) and the cycle times of both runs.
+It reports; it asserts nothing (profiles/observe_loop_ab.txt: with the feed-forward controller one period of compute delay is enough to lose the walk
+on the flow plant, with --controller feedback the defaults walk).
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -220,6 +228,12 @@ def main():
     ap.add_argument("--inertia", action="store_true")
     ap.add_argument("--mass-spread", type=float, default=0.15)
     ap.add_argument("--payload", type=float, default=None, metavar="KG")
+    ap.add_argument("--observe", action="store_true")
+    ap.add_argument("--obs-noise", type=float, default=5e-3)
+    ap.add_argument("--obs-bias", type=float, default=0.02)
+    ap.add_argument("--sensor-delay", type=int, default=1)
+    ap.add_argument("--compute-delay", type=int, default=1)
+    ap.add_argument("--obs-seed", type=int, default=2026)
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -233,8 +247,29 @@ def main():
         ap.error("--mass-spread and --payload belong to --inertia (without it nothing is varied)")
     if args.inertia and args.plant != "torque":
         ap.error("--inertia requires --plant torque (the inertial variations act on the torque plant only)")
+    if not args.observe and given & {"--obs-noise", "--obs-bias", "--sensor-delay", "--compute-delay", "--obs-seed"}:
+        ap.error("--obs-noise, --obs-bias, --sensor-delay, --compute-delay and --obs-seed belong to --observe (without it the MPC measures the plant exactly)")
     if args.push:
         return push_sweep(args)
+    line = timed_run(args, args.observe)
+    if args.observe:
+        off = timed_run(args, False)
+        line["observe"].update(tracking_off=off["tracking"], cycle_ms_median_off=off["cycle_ms_median"], run_ms_per_cycle_off=off["run_ms_per_cycle"],
+                               base_height_range_off=off["base_height_range"])
+        line["observe"]["tracking_on"] = line["tracking"]
+    del line["tracking"]
+    print(json.dumps(line))
+
+
+def tracking_error(m, x, cmd):
+    """|v_base - R(yaw) v_cmd| of the planar base velocity, per instance: x [B][58], cmd [B][4]"""
+    c, sn = np.cos(x[:, 3]), np.sin(x[:, 3])
+    want = np.column_stack([c * cmd[:, 0] - sn * cmd[:, 1], sn * cmd[:, 0] + c * cmd[:, 1]])
+    return np.linalg.norm(x[:, 6 + m.nj:8 + m.nj] - want, axis=1)
+
+
+def timed_run(args, observe):
+    """The timed loop (with the observation model of --observe on or off): the fields of the JSON line."""
     m = load_model()
     B, N, dt = args.batch, args.nodes, m.sqp["dt"]
     t_final = (2 * args.warmup + 2 * args.cycles) * args.period + N * dt + 1.0
@@ -252,7 +287,7 @@ def main():
     s.set_scan_backoff_persistent(True)
     st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True,
                          controller=args.controller)
-    cycle_ms, heights = [], []
+    cycle_ms, heights, track = [], [], []
     changes = {}
     if args.gait == "ladder":
         zero = np.tile((0.0, 0.0, 0.7925, 0.0), (B, 1))
@@ -263,6 +298,11 @@ def main():
         stop[k == 2, 0] = 0.0
         cmd, changes = zero, {10: go, 40: stop}
     try:
+        if observe:                                               # before the start: a started loop holds its delays
+            sigma, bias = np.full((B, 58), args.obs_noise), np.zeros((B, 58))
+            bias[:, 2] = args.obs_bias
+            s.set_observation(sensor_delay=args.sensor_delay, compute_delay=args.compute_delay, seed=args.obs_seed)
+            s.set_observation_instances(bias, sigma)
         if args.gait:
             s.loop_start(st, 0.0, x_init, cmd, gait=gait_settings(m))
         else:
@@ -284,12 +324,14 @@ def main():
         for c in range(args.warmup + args.cycles):
             if c in changes:
                 s.loop_command(changes[c])
+                cmd = changes[c]
             t_a = time.perf_counter()
             r = s.loop_run(1)
             t_b = time.perf_counter()
             heights.append(r["x"][0, :, 2].copy())
             if c >= args.warmup:
                 cycle_ms.append(1e3 * (t_b - t_a))
+                track.append(np.nanmean(tracking_error(m, r["x"][0], cmd)))
         t_a = time.perf_counter()
         r = s.loop_run(args.cycles, log=False)
         run_ms = 1e3 * (time.perf_counter() - t_a) / args.cycles
@@ -307,7 +349,7 @@ def main():
     if args.inertia:
         for b in range(B):
             print(f"instance {b}: total mass {masses[b]:.3f} kg, finished {'yes' if finished[b] else 'no'}")
-    print(json.dumps({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
+    return dict({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
                       "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
                       "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None,
                       "contact": contact_args(args) if args.contact else None,
@@ -320,7 +362,10 @@ def main():
                       "run_ms_per_cycle": round(float(run_ms), 3), "t_end": round(float(t_end), 6),
                       "status_counts": {"ok": int(B * (args.warmup + 2 * args.cycles)), "max_steps": 0, "nonfinite": 0},
                       "forward_speed_range": [round(float(x_end[:, 6 + m.nj].min()), 4), round(float(x_end[:, 6 + m.nj].max()), 4)],
-                      "base_height_range": [round(float(heights.min()), 5), round(float(heights.max()), 5)]}))
+                      "base_height_range": [round(float(heights.min()), 5), round(float(heights.max()), 5)],
+                      "observe": dict(noise=args.obs_noise, height_bias=args.obs_bias, sensor_delay=args.sensor_delay, compute_delay=args.compute_delay,
+                                      seed=args.obs_seed) if observe else None,
+                      "tracking": dict(mean=round(float(np.mean(track)), 5), end=round(float(np.nanmean(tracking_error(m, x_end, cmd))), 5))})
 
 
 if __name__ == "__main__":

@@ -228,6 +228,24 @@ class InertiaInstance(C.Structure):   # hsqp_inertia_instance
 INERTIA_ENTRY_POINTS = ("hsqp_inertia_defaults", "hsqp_inertia_set_instances", "hsqp_inertia_set_instances_device", "hsqp_inertia_clear",
                         "hsqp_inertia_get_instances", "hsqp_inertia_eval", "hsqp_inertia_eval_device")
 
+
+# include/hsqp_observe.h
+OBS_MAX_DELAY = 8
+
+
+class ObserveSettings(C.Structure):   # hsqp_observe_settings
+    _fields_ = [("sensor_delay", C.c_int32), ("compute_delay", C.c_int32), ("seed", C.c_uint64)]
+
+
+class ObserveInstance(C.Structure):   # hsqp_observe_instance
+    _fields_ = [("bias", C.c_double * NX), ("sigma", C.c_double * NX)]
+
+
+# entry points of include/hsqp_observe.h (tests/test_observe.py checks that the library exports each of them and the binding declares it)
+OBSERVE_ENTRY_POINTS = ("hsqp_observe_defaults", "hsqp_observe_instance_defaults", "hsqp_observe_set", "hsqp_observe_set_instances",
+                        "hsqp_observe_set_instances_device", "hsqp_observe_clear", "hsqp_observe_get", "hsqp_observe_eval", "hsqp_observe_eval_device",
+                        "hsqp_observe_last", "hsqp_observe_last_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

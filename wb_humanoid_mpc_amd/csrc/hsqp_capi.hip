@@ -25,6 +25,7 @@
 #include "../../include/hsqp_loop.h"
 #include "hsqp_gait.h"
 #include "hsqp_episode.h"
+#include "hsqp_observe.h"
 #include "hsqp_warm.h"
 #include "hsqp_cent.h"
 #include "hsqp_cent_lq.h"
@@ -820,6 +821,12 @@ __global__ __launch_bounds__(64) void k_gait_update(const hsqp_gait_settings* __
 
 // ---- failure isolation and episode reset of the resident loop (hsqp_episode.h): one wave per instance
 __global__ __launch_bounds__(64) void k_loop_triage(TriageArgs a) { triage_instance(Ctx{(int)threadIdx.x, 64, nullptr}, a, blockIdx.x); }
+// step 0 of a cycle with the observation model in force, and hsqp_observe_eval (include/hsqp_observe.h, csrc/hsqp_observe.h): OBS_THREADS items
+// (instance, block of four entries) per workgroup
+__global__ __launch_bounds__(OBS_THREADS) void k_observe(ObserveArgs a) {
+  const Ctx ctx{(int)threadIdx.x, OBS_THREADS, nullptr};
+  observe_group(ctx, a, blockIdx.x);
+}
 // entry blockIdx.x of a hsqp_loop_reset_instances request
 __global__ __launch_bounds__(64) void k_episode_host_reset(HostResetArgs a) { host_reset_instance(Ctx{(int)threadIdx.x, 64, nullptr}, a, blockIdx.x); }
 // the command in use of every instance from its state (behind hsqp_loop_isolate and hsqp_loop_command): one thread per entry
@@ -1193,6 +1200,13 @@ struct hsqp_handle {
   // first inertia_B the table's, the rest neutral; inertia_B = 0: no table.  d_inertia_stage: staging of hsqp_inertia_eval's host arrays (inertia_stage_layout)
   DevBuf<char> d_inertia, d_inertia_stage;
   int inertia_B = 0;
+  // the resident observation model of the loop (include/hsqp_observe.h).  observe_set: hsqp_observe_set made settings; d_observe_table (observe_table_layout):
+  // the entry of every instance [max_batch] — the first observe_B the table's, the rest neutral; observe_B = 0: no table.  d_observe (observe_layout): the
+  // loop's ring and its two observation rows; d_observe_stage: staging of hsqp_observe_eval's host arrays (observe_stage_layout)
+  hsqp_observe_settings observe = {};
+  bool observe_set = false;
+  int observe_B = 0;
+  DevBuf<char> d_observe_table, d_observe, d_observe_stage;
   bool stamps_resident = false;   // d_stamps[stamps_cur] holds the raw stamps of the resident problem (it came through hsqp_upload_reference or the loop): the pushes' clock
   // raw time stamps of the resident grid (hsqp_reference::warm_start): two [max_batch][max_nodes + 1] buffers, d_stamps[stamps_cur] belongs to the
   // resident problem; a SHIFT upload reads it while it writes the other one.  have_stamps: the resident problem came through hsqp_upload_reference
@@ -1217,6 +1231,11 @@ struct hsqp_handle {
     EpisodeState ep = {};
     double* x_reset = nullptr; double* v_use = nullptr;
     int* req_ids = nullptr; double* req_x0 = nullptr; double* req_v = nullptr;
+    // the observation model (include/hsqp_observe.h): the ring [delay + 1][B][58] (null without a delay) and the observations of the even and the odd
+    // cycles [B][58] in d_observe (observe_layout); obs_last: a cycle with the model in force has completed since the start, obs_tp its problem time
+    double* obs_ring = nullptr; double* obs_y[2] = {nullptr, nullptr};
+    bool obs_last = false;
+    double obs_tp = 0.0;
   } loop;
   // the resident gait state (include/hsqp_gait.h): two copies in d_gait (gait_layout), s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
   struct Gait {
@@ -1312,6 +1331,17 @@ static size_t episode_layout(Carve c, hsqp_handle::Loop& L, size_t B) {
   L.req_ids = c.take<int>(B); L.req_x0 = c.take<double>(B * NX); L.req_v = c.take<double>(B * CMD_N);
   return c.bytes();
 }
+// d_observe: the loop's ring of plant states (absent without a delay) and the observations of the even and the odd cycles
+static size_t observe_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t slots) {
+  L.obs_ring = c.take<double>(slots * B * NX, slots > 1); L.obs_y[0] = c.take<double>(B * NX); L.obs_y[1] = c.take<double>(B * NX);
+  return c.bytes();
+}
+// d_observe_table: the observation entry of every instance [max_batch]
+struct ObserveBuf { hsqp_observe_instance* table; size_t bytes; };
+static ObserveBuf observe_table_layout(Carve c, size_t max_batch) { return {c.take<hsqp_observe_instance>(max_batch), c.bytes()}; }
+// d_observe_stage, hsqp_observe_eval (host arrays): x [B][58] | y [B][58]
+struct ObserveStage { double* x; double* y; size_t bytes; };
+static ObserveStage observe_stage_layout(Carve c, size_t B) { return {c.take<double>(B * NX), c.take<double>(B * NX), c.bytes()}; }
 // d_push: n_pushes [B], then pushes [B][max_pushes]
 struct PushBuf { int32_t* n; hsqp_push* p; size_t bytes; };
 static PushBuf push_layout(Carve c, size_t B, size_t max_pushes) { return {c.take<int32_t>(B), c.take<hsqp_push>(B * max_pushes), c.bytes()}; }
@@ -3011,6 +3041,7 @@ void hsqp_loop_defaults(const hsqp_handle* h, hsqp_loop_settings* s) {
 }
 
 static int gait_reset_impl(hsqp_handle* h, const char* who, const hsqp_gait_settings* gs, int batch, double t0);
+static bool observe_in_force(const hsqp_handle* h);
 
 // hsqp_loop_start (schedules uploaded once) and hsqp_loop_start_gait (gait != null: the resident gait state owns the schedule, max_events is its capacity)
 static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_settings* st, const hsqp_gait_settings* gait, int batch, double t0, const double* x0,
@@ -3036,7 +3067,9 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
       if (n_events[b] < 1 || n_events[b] > max_events) return loop_bad(h, who, "n_events outside [1, max_events]");
   if (!all_finite(v_cmd, B * CMD_N)) return loop_bad(h, who, "non-finite command");
   HCHECK(hipSetDevice(h->device));
-  if (gait) { const int rc = gait_reset_impl(h, who, gait, batch, t0); if (rc != HSQP_OK) return rc; }
+  // the gait's clock is the problem time (include/hsqp_observe.h): compute_delay periods behind the loop's time
+  const double t_gait = observe_in_force(h) ? observe_problem_time(t0, observe_policy_time(h->observe.compute_delay, st->period)) : t0;
+  if (gait) { const int rc = gait_reset_impl(h, who, gait, batch, t_gait); if (rc != HSQP_OK) return rc; }
   hsqp_handle::Loop& L = h->loop;
   DEV_ENSURE(h->d_loop, loop_layout(Carve{}, L, B, E), "loop buffers");
   loop_layout(Carve{h->d_loop.p}, L, B, E);
@@ -3055,6 +3088,7 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
   L.st = *st; L.B = batch; L.E = max_events; L.t = t0;
   L.have_cycle = false;
   L.cycle = 0;
+  L.obs_last = false;
   L.isolate = false;
   L.gait = gait != nullptr;
   L.started = true;
@@ -3274,41 +3308,64 @@ int hsqp_loop_start_gait(hsqp_handle* h, const hsqp_loop_settings* settings, con
 // One cycle from the resident buffers (include/hsqp_loop.h, steps 1 to 5).  d_xlog / d_ulog: this cycle's log rows (device) or null.  On a failure the
 // loop's own state (t, x, v_filt) is that of the last completed cycle: the filter state is advanced on a copy and committed with the state.
 // Under isolation (include/hsqp_episode.h): the command in use, the warm start per instance, the status words left to the triage behind step 5.
+static bool observe_in_force(const hsqp_handle* h) { return h->observe_set || h->observe_B > 0; }
+static void launch_observe(hsqp_handle* h, const ObserveArgs& a) {
+  HSQP_LAUNCH(k_observe, dim3((a.B * OBS_BLOCKS + OBS_THREADS - 1) / OBS_THREADS), dim3(OBS_THREADS), 0, h->stream, a);
+}
+
 static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   hsqp_handle::Loop& L = h->loop;
   const hsqp_loop_settings& st = L.st;
   const size_t B = L.B;
   const bool iso = L.isolate;
   const int warm = L.have_cycle ? HSQP_WARM_SHIFT : HSQP_WARM_COLD;
+  // the observation model (include/hsqp_observe.h): with it in force the MPC reads y at the problem time tp; without it the plant's state at the loop's time
+  const bool obs = observe_in_force(h);
+  const double lag = obs ? observe_policy_time(h->observe.compute_delay, st.period) : 0.0;
+  const double tp = obs ? observe_problem_time(L.t, lag) : L.t;
+  const double* xm = obs ? L.obs_y[L.cycle & 1] : L.x;
   hsqp_problem p{};
-  p.batch = L.B; p.n_nodes = st.n_nodes; p.dt = st.dt; p.x_init = L.x;
+  p.batch = L.B; p.n_nodes = st.n_nodes; p.dt = st.dt; p.x_init = xm;
   // step 2's checks come first, as in hsqp_upload_reference: a rejected cycle leaves the resident solution as it was
   h->have_policy = false;
   const int N_prev = h->N;
   if (warm == HSQP_WARM_SHIFT) { const int rc = warm_shift_ready(h, L.B, true, iso); if (rc != HSQP_OK) return rc; }
   StickyError step{h};
+  // 0. the observation: the plant's state into the ring, y from the delayed slot, the policy time of step 4 into s0
+  if (obs) {
+    ObserveArgs a{};
+    a.table = h->observe_B ? observe_table_layout(Carve{h->d_observe_table.p}, (size_t)h->st.max_batch).table : nullptr;
+    a.key0 = (uint32_t)(h->observe.seed & 0xffffffffu); a.key1 = (uint32_t)(h->observe.seed >> 32);
+    a.draw = (uint32_t)L.cycle; a.B = L.B;
+    observe_cycle_slots(L.cycle, h->observe.sensor_delay + h->observe.compute_delay, a);
+    a.fresh_all = L.have_cycle ? 0 : 1;
+    a.mode_b = iso && L.have_cycle ? L.ep.mode : nullptr;
+    a.x = L.x; a.ring = L.obs_ring; a.y = L.obs_y[L.cycle & 1]; a.s0 = L.s0; a.s0_value = lag;
+    launch_observe(h, a);
+    step(hipGetLastError(), "k_observe");
+  }
   // 1. the targets; the filter state advances in the second half of its buffer
   double* vf_next = L.v_filt + B * CMD_N;
   step(hipMemcpyAsync(vf_next, L.v_filt, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream), "copy v_filt");
-  launch_command_targets(h, L.B, iso ? L.v_use : L.v_cmd, vf_next, st.filter_alpha, L.x, L.t, st.n_nodes * st.dt, L.tt, L.ts);
+  launch_command_targets(h, L.B, iso ? L.v_use : L.v_cmd, vf_next, st.filter_alpha, xm, tp, st.n_nodes * st.dt, L.tt, L.ts);
   step(hipGetLastError(), "k_command_targets");
   // the gait update between steps 1 and 2 (include/hsqp_gait.h): this cycle's schedule into ne / ev / seq; the shadow state becomes the live one with step 5
   if (L.gait) {
     if (step.rc != HSQP_OK) return step.rc;
-    const int rc = gait_launch_and_check(h, "hsqp_loop_run", L.B, L.t, st.n_nodes * st.dt, vf_next, L.x, L.ne, L.ev, L.seq);
+    const int rc = gait_launch_and_check(h, "hsqp_loop_run", L.B, tp, st.n_nodes * st.dt, vf_next, xm, L.ne, L.ev, L.seq);
     if (rc != HSQP_OK) return rc;
   }
   // 2. hsqp_upload_reference's work on the resident arrays
   h->have_problem = false; h->have_solution = false; h->have_stamps = false;
   { const int rc = set_grid(h, &p, false); if (rc != HSQP_OK) return rc; }
   step(hipMemsetAsync(L.bad, 0, 4, h->stream), "memset");
-  step(hipMemcpyAsync(h->d_xinit, L.x, B * NX * 8, hipMemcpyDeviceToDevice, h->stream), "copy x_init");
-  RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, nullptr, L.bad, L.t, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
+  step(hipMemcpyAsync(h->d_xinit, xm, B * NX * 8, hipMemcpyDeviceToDevice, h->stream), "copy x_init");
+  RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, nullptr, L.bad, tp, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
   if (iso && warm == HSQP_WARM_SHIFT) rd.warm_b = L.ep.mode;
   { const int rc = reference_build(h, &p, rd, step); if (rc != HSQP_OK) return rc; }
   // 3. the iteration
   { const int rc = hsqp_iterate_device(h, st.iterations, st.iterate_flags); if (rc != HSQP_OK) return rc; }
-  // 4. the plant under the policy over one period
+  // 4. the plant under the policy over one period, from its true state (with the model in force at s0 = compute_delay periods in the policy's frame)
   { const int rc = rollout_impl(h, &st.rollout, L.s0, L.x, st.period, 1, L.xs, L.us, L.ro_status, nullptr, nullptr, true, iso); if (rc != HSQP_OK) return rc; }
   // 5. the rolled-out state is the next measured state
   HCHECK(hipMemcpyAsync(L.x, L.xs, B * NX * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -3321,9 +3378,11 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
     const TriageArgs a{L.ep_st, L.cycle, h->d_status, h->d_perf_after, L.ro_status, L.xs, L.x_reset, L.v_cmd, L.ep, L.x, L.v_filt, L.v_use, d_xlog, d_ulog};
     HSQP_LAUNCH(k_loop_triage, dim3(L.B), dim3(64), 0, h->stream, a);
     if (L.gait)
-      HSQP_LAUNCH(k_gait_reset_instances, dim3(L.B), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)nullptr, (const int*)L.ep.reset, L.t);
+      HSQP_LAUNCH(k_gait_reset_instances, dim3(L.B), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)nullptr, (const int*)L.ep.reset,
+                  obs ? observe_problem_time(L.t, lag) : L.t);   // the gait's clock is the problem time of the next cycle
     HCHECK(hipGetLastError());
   }
+  if (obs) { L.obs_last = true; L.obs_tp = tp; }
   ++L.cycle;
   L.have_cycle = true;
   return HSQP_OK;
@@ -3337,6 +3396,19 @@ static int loop_run_impl(hsqp_handle* h, int n_cycles, double* x_log, double* u_
   if (n_cycles < 1) return loop_bad(h, who, "n_cycles < 1");
   if (h->push_B && h->push_B != h->loop.B)
     return loop_bad(h, who, ("the push table holds " + std::to_string(h->push_B) + " instances, the loop " + std::to_string(h->loop.B) + " (hsqp_push_set / hsqp_push_clear)").c_str());
+  if (observe_in_force(h)) {
+    hsqp_handle::Loop& L = h->loop;
+    if (h->observe_B && h->observe_B != L.B)
+      return loop_bad(h, who, ("the observation table holds " + std::to_string(h->observe_B) + " instances, the loop " + std::to_string(L.B) +
+                               " (hsqp_observe_set_instances / hsqp_observe_clear)").c_str());
+    if (!observe_horizon_ok(h->observe.compute_delay, L.st.period, L.st.n_nodes, L.st.dt))
+      return loop_bad(h, who, ("(compute_delay + 1) period = " + std::to_string((h->observe.compute_delay + 1) * L.st.period) + " s exceeds the horizon n_nodes dt = " +
+                               std::to_string(L.st.n_nodes * L.st.dt) + " s: the policy would be evaluated past its horizon (hsqp_observe_set)").c_str());
+    HCHECK(hipSetDevice(h->device));
+    const size_t slots = (size_t)(h->observe.sensor_delay + h->observe.compute_delay + 1);
+    DEV_ENSURE(h->d_observe, observe_layout(Carve{}, L, (size_t)L.B, slots), "observation ring");
+    observe_layout(Carve{h->d_observe.p}, L, (size_t)L.B, slots);
+  }
   HCHECK(hipSetDevice(h->device));
   const size_t B = h->loop.B, nx = B * NX, nu = B * NU, n = n_cycles;
   double* d_xl = x_log;
@@ -3380,6 +3452,130 @@ static int loop_state_impl(hsqp_handle* h, double* t, double* x, double* v_filt,
 }
 int hsqp_loop_state(hsqp_handle* h, double* t, double* x, double* v_filt) { return loop_state_impl(h, t, x, v_filt, false); }
 int hsqp_loop_state_device(hsqp_handle* h, double* t, double* d_x, double* d_v_filt) { return loop_state_impl(h, t, d_x, d_v_filt, true); }
+
+// ---- the observation model of the loop (include/hsqp_observe.h, csrc/hsqp_observe.h): the resident settings and table, the evaluation, the last observation
+void hsqp_observe_defaults(hsqp_observe_settings* s) { if (s) memset(s, 0, sizeof(*s)); }
+void hsqp_observe_instance_defaults(hsqp_observe_instance* v) { if (v) memset(v, 0, sizeof(*v)); }
+static int observe_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) return loop_bad(h, who, "whole-body handles only (the model acts on the whole-body state row of the resident loop)");
+  return HSQP_OK;
+}
+int hsqp_observe_set(hsqp_handle* h, const hsqp_observe_settings* s) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_observe_set";
+  if (const int rc = observe_handle_ok(h, who)) return rc;
+  if (!s) return loop_bad(h, who, "null settings");
+  if (const char* what = observe_settings_error(*s)) return loop_bad(h, who, what);
+  if (h->loop.started && (s->sensor_delay != h->observe.sensor_delay || s->compute_delay != h->observe.compute_delay))
+    return loop_bad(h, who, "the delays differ from those in force while a loop is started (the ring and the problem clock would lose their meaning): restart the loop");
+  h->observe = *s;
+  h->observe_set = true;
+  return HSQP_OK;
+}
+static int observe_set_instances_impl(hsqp_handle* h, int batch, const hsqp_observe_instance* t, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_observe_set_instances_device" : "hsqp_observe_set_instances";
+  if (const int rc = observe_handle_ok(h, who)) return rc;
+  if (!t) {
+    if (batch < 0 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [0, max_batch]");
+    h->observe_B = 0;
+    return HSQP_OK;
+  }
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (!dev)
+    for (int b = 0; b < batch; ++b)
+      if (const int f = observe_entry_error(t[b]))
+        return loop_bad(h, who, ("instance " + std::to_string(b) + (f > 0 ? ": bias[" + std::to_string(f - 1) + "] non-finite" : ": sigma[" + std::to_string(-f - 1) + "] negative or non-finite")).c_str());
+  HCHECK(hipSetDevice(h->device));
+  const size_t mb = (size_t)h->st.max_batch;
+  DEV_ENSURE(h->d_observe_table, observe_table_layout(Carve{}, mb).bytes, "observation table");
+  hsqp_observe_instance* d = observe_table_layout(Carve{h->d_observe_table.p}, mb).table;
+  HCHECK(hipStreamSynchronize(h->stream));   // (no cycle in flight reads the entries that are replaced)
+  h->observe_B = 0;                          // (a failure below leaves no table)
+  HCHECK(hipMemcpy(d, t, (size_t)batch * sizeof(hsqp_observe_instance), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  if (mb > (size_t)batch) HCHECK(hipMemset(d + batch, 0, (mb - (size_t)batch) * sizeof(hsqp_observe_instance)));   // neutral: all bits zero
+  h->observe_B = batch;
+  return HSQP_OK;
+}
+int hsqp_observe_set_instances(hsqp_handle* h, int batch, const hsqp_observe_instance* table) { return observe_set_instances_impl(h, batch, table, false); }
+int hsqp_observe_set_instances_device(hsqp_handle* h, int batch, const hsqp_observe_instance* d_table) { return observe_set_instances_impl(h, batch, d_table, true); }
+int hsqp_observe_clear(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (const int rc = observe_handle_ok(h, "hsqp_observe_clear")) return rc;
+  const bool was = observe_in_force(h);
+  h->observe_set = false;
+  h->observe_B = 0;
+  hsqp_observe_defaults(&h->observe);
+  h->loop.obs_last = false;
+  if (was && h->loop.started) {   // the policy time of step 4 is zero again
+    HCHECK(hipSetDevice(h->device));
+    HCHECK(hipMemsetAsync(h->loop.s0, 0, (size_t)h->loop.B * 8, h->stream));
+    HCHECK(hipStreamSynchronize(h->stream));
+  }
+  return HSQP_OK;
+}
+int hsqp_observe_get(hsqp_handle* h, hsqp_observe_settings* s, int batch, hsqp_observe_instance* table) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_observe_get";
+  if (const int rc = observe_handle_ok(h, who)) return rc;
+  if (table && (batch < 1 || batch > h->st.max_batch)) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (s) *s = h->observe;
+  if (!table) return HSQP_OK;
+  const int have = batch < h->observe_B ? batch : h->observe_B;
+  if (have) {
+    HCHECK(hipSetDevice(h->device));
+    HCHECK(hipStreamSynchronize(h->stream));
+    HCHECK(hipMemcpy(table, observe_table_layout(Carve{h->d_observe_table.p}, (size_t)h->st.max_batch).table, (size_t)have * sizeof(hsqp_observe_instance), hipMemcpyDeviceToHost));
+  }
+  for (int b = have; b < batch; ++b) hsqp_observe_instance_defaults(table + b);
+  return HSQP_OK;
+}
+static int observe_eval_impl(hsqp_handle* h, int batch, uint32_t draw, const double* x, double* y, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_observe_eval_device" : "hsqp_observe_eval";
+  if (const int rc = observe_handle_ok(h, who)) return rc;
+  if (!x || !y) return loop_bad(h, who, "null x or y");
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = (size_t)batch;
+  ObserveArgs a{};
+  a.table = h->observe_B ? observe_table_layout(Carve{h->d_observe_table.p}, (size_t)h->st.max_batch).table : nullptr;
+  a.key0 = (uint32_t)(h->observe.seed & 0xffffffffu); a.key1 = (uint32_t)(h->observe.seed >> 32);
+  a.draw = draw; a.B = batch; a.slots = 1;
+  a.x = x; a.y = y;
+  StickyError step{h};
+  if (!dev) {
+    DEV_ENSURE(h->d_observe_stage, observe_stage_layout(Carve{}, B).bytes, "observation staging");
+    const ObserveStage sg = observe_stage_layout(Carve{h->d_observe_stage.p}, B);
+    a.x = sg.x; a.y = sg.y;
+    step(hipMemcpyAsync(sg.x, x, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
+  }
+  if (step.rc == HSQP_OK) {
+    launch_observe(h, a);
+    step(hipGetLastError(), "k_observe");
+  }
+  if (!dev) step(hipMemcpyAsync(y, a.y, B * NX * 8, hipMemcpyDeviceToHost, h->stream), "download y");
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+int hsqp_observe_eval(hsqp_handle* h, int batch, uint32_t draw, const double* x, double* y) { return observe_eval_impl(h, batch, draw, x, y, false); }
+int hsqp_observe_eval_device(hsqp_handle* h, int batch, uint32_t draw, const double* d_x, double* d_y) { return observe_eval_impl(h, batch, draw, d_x, d_y, true); }
+static int observe_last_impl(hsqp_handle* h, double* y, double* t_p, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_observe_last_device" : "hsqp_observe_last";
+  if (const int rc = observe_handle_ok(h, who)) return rc;
+  const hsqp_handle::Loop& L = h->loop;
+  if (!L.started || !L.obs_last) return loop_bad(h, who, "no completed cycle of a started loop with the observation model in force (hsqp_observe_set, hsqp_loop_run)");
+  if (t_p) *t_p = L.obs_tp;
+  if (y) {
+    HCHECK(hipSetDevice(h->device));
+    HCHECK(hipMemcpyAsync(y, L.obs_y[(L.cycle - 1) & 1], (size_t)L.B * NX * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HCHECK(hipStreamSynchronize(h->stream));
+  }
+  return HSQP_OK;
+}
+int hsqp_observe_last(hsqp_handle* h, double* y, double* t_p) { return observe_last_impl(h, y, t_p, false); }
+int hsqp_observe_last_device(hsqp_handle* h, double* d_y, double* t_p) { return observe_last_impl(h, d_y, t_p, true); }
 
 // ---- per-instance failure isolation and episode reset (include/hsqp_episode.h, csrc/hsqp_episode.h)
 void hsqp_episode_defaults(hsqp_episode_settings* s) {
@@ -3459,8 +3655,11 @@ int hsqp_loop_reset_instances(hsqp_handle* h, int n, const int32_t* ids, const d
   if (step.rc == HSQP_OK) {
     const HostResetArgs a{L.req_ids, x0 ? L.req_x0 : nullptr, v_cmd ? L.req_v : nullptr, L.x_reset, L.ep, L.x, L.v_cmd, L.v_filt, L.v_use};
     HSQP_LAUNCH(k_episode_host_reset, dim3(n), dim3(64), 0, h->stream, a);
-    if (L.gait)
-      HSQP_LAUNCH(k_gait_reset_instances, dim3(n), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)L.req_ids, (const int*)nullptr, L.t);
+    const bool obs = observe_in_force(h);
+    const double lag = obs ? observe_policy_time(h->observe.compute_delay, L.st.period) : 0.0;
+    if (L.gait)   // the gait's clock: the problem time of the next cycle (include/hsqp_observe.h)
+      HSQP_LAUNCH(k_gait_reset_instances, dim3(n), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)L.req_ids, (const int*)nullptr,
+                  obs ? observe_problem_time(L.t, lag) : L.t);
     step(hipGetLastError(), "k_episode_host_reset");
   }
   step(hipStreamSynchronize(h->stream), "sync");

@@ -24,6 +24,7 @@
 #include "../../include/hsqp_contact.h"
 #include "../../include/hsqp_actuator.h"
 #include "../../include/hsqp_inertia.h"
+#include "../../include/hsqp_observe.h"
 
 namespace hsqp_host {
 
@@ -312,6 +313,53 @@ class HipSqpSolver {
     M.assign(B * HSQP_NV * HSQP_NV, 0.0); nle.assign(B * HSQP_NV, 0.0); mass.assign(B, 0.0);
     const int rc = hsqp_inertia_eval(h_, (int)B, x.data(), M.data(), nle.data(), mass.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_inertia_eval failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** ---- the observation model of the resident loop (include/hsqp_observe.h): what the MPC measures of the plant — a per-instance bias and white noise
+   *  on the state row, a sensor delay the controller does not know about and a compute delay it does (the problem is posed compute_delay periods back
+   *  and the plant enters the policy at that offset).  setObservation: the delays (whole MPC periods) and the seed.  setObservationInstances: one entry
+   *  per instance, an empty vector: no table.  observation: the settings and the entries in force (past the table: neutral).  observe: bias and noise of
+   *  instance b's entry on x [B][58] at a draw index, no delay.  lastObservation: what the last completed cycle of the loop used, [B][58], and its
+   *  problem time.  The plant, the rollout and the iteration are untouched. */
+  void setObservation(int sensor_delay = 0, int compute_delay = 0, uint64_t seed = 0) {
+    hsqp_observe_settings st;
+    hsqp_observe_defaults(&st);
+    st.sensor_delay = sensor_delay; st.compute_delay = compute_delay; st.seed = seed;
+    const int rc = hsqp_observe_set(h_, &st);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_observe_set failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void setObservationInstances(const std::vector<hsqp_observe_instance>& table) {
+    const int rc = hsqp_observe_set_instances(h_, (int)table.size(), table.empty() ? nullptr : table.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_observe_set_instances failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void clearObservation() {
+    const int rc = hsqp_observe_clear(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_observe_clear failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  hsqp_observe_settings observation(int batch, std::vector<hsqp_observe_instance>& table) {
+    if (batch < 1) throw std::runtime_error("[HipSqpSolver] observation: batch < 1");
+    hsqp_observe_settings st;
+    table.resize((size_t)batch);
+    const int rc = hsqp_observe_get(h_, &st, batch, table.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_observe_get failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return st;
+  }
+  std::vector<double> observe(const std::vector<double>& x, uint32_t draw) {
+    const size_t B = x.size() / HSQP_NX;
+    if (B < 1 || x.size() != B * HSQP_NX) throw std::runtime_error("[HipSqpSolver] observe: x must hold [B][58] states");
+    std::vector<double> y(x.size());
+    const int rc = hsqp_observe_eval(h_, (int)B, draw, x.data(), y.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_observe_eval failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return y;
+  }
+  /** y: [batch][58], batch the loop's; returns the problem time */
+  double lastObservation(int batch, std::vector<double>& y) {
+    if (batch < 1) throw std::runtime_error("[HipSqpSolver] lastObservation: batch < 1");
+    y.assign((size_t)batch * HSQP_NX, 0.0);
+    double tp = 0.0;
+    const int rc = hsqp_observe_last(h_, y.data(), &tp);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_observe_last failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return tp;
   }
 
   /** ---- the closed loop resident on the device (include/hsqp_loop.h): what ProceduralMpcMotionManager::preSolverRun's target generation, MPC_BASE::run

@@ -139,6 +139,21 @@ def load_library():
     lib.hsqp_inertia_get_instances.argtypes = [C.c_void_p, C.c_int, _ii]
     lib.hsqp_inertia_eval.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     lib.hsqp_inertia_eval_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+    # include/hsqp_observe.h
+    _os, _oi = C.POINTER(_abi.ObserveSettings), C.POINTER(_abi.ObserveInstance)
+    lib.hsqp_observe_defaults.argtypes = [_os]
+    lib.hsqp_observe_defaults.restype = None
+    lib.hsqp_observe_instance_defaults.argtypes = [_oi]
+    lib.hsqp_observe_instance_defaults.restype = None
+    lib.hsqp_observe_set.argtypes = [C.c_void_p, _os]
+    lib.hsqp_observe_set_instances.argtypes = [C.c_void_p, C.c_int, _oi]
+    lib.hsqp_observe_set_instances_device.argtypes = [C.c_void_p, C.c_int, _oi]
+    lib.hsqp_observe_clear.argtypes = [C.c_void_p]
+    lib.hsqp_observe_get.argtypes = [C.c_void_p, _os, C.c_int, _oi]
+    lib.hsqp_observe_eval.argtypes = [C.c_void_p, C.c_int, C.c_uint32, _dp, _dp]
+    lib.hsqp_observe_eval_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, _dp, _dp]
+    lib.hsqp_observe_last.argtypes = [C.c_void_p, _dp, _dp]
+    lib.hsqp_observe_last_device.argtypes = [C.c_void_p, _dp, _dp]
     # include/hsqp_loop.h
     _ls = C.POINTER(_abi.LoopSettings)
     lib.hsqp_set_default_joint_state.argtypes = [C.c_void_p, _dp]
@@ -764,6 +779,72 @@ class HipSqpSolver:
         M, nle, mass = np.zeros((B, _abi.NV, _abi.NV)), np.zeros((B, _abi.NV)), np.zeros(B)
         self._check(self.lib.hsqp_inertia_eval(self.h, B, x.ctypes.data_as(_dp), M.ctypes.data_as(_dp), nle.ctypes.data_as(_dp), mass.ctypes.data_as(_dp)))
         return M, nle, mass
+
+    # ---- include/hsqp_observe.h: what the MPC of the resident loop measures of the plant — bias, noise, sensor and compute delay
+    def set_observation(self, sensor_delay=0, compute_delay=0, seed=0):
+        """hsqp_observe_set: the measurement is sensor_delay + compute_delay MPC periods old when its policy takes over; the controller knows of
+        compute_delay only (it poses the problem at t - compute_delay * period and the plant enters the policy at that offset).  seed: the key of
+        the noise stream of set_observation_instances.  Delays cannot change under a started loop."""
+        st = _abi.ObserveSettings()
+        st.sensor_delay, st.compute_delay, st.seed = int(sensor_delay), int(compute_delay), int(seed)
+        self._check(self.lib.hsqp_observe_set(self.h, C.byref(st)))
+
+    @staticmethod
+    def pack_observation(bias, sigma):
+        """The table of hsqp_observe_set_instances as a ctypes array: bias and sigma [B, 58], each broadcast from [B], [58] or a scalar against the other."""
+        bias, sigma = np.asarray(bias, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+        if bias.ndim == 1 and bias.shape[0] != _abi.NX:
+            bias = bias[:, None]
+        if sigma.ndim == 1 and sigma.shape[0] != _abi.NX:
+            sigma = sigma[:, None]
+        B = max([a.shape[0] for a in (bias, sigma) if a.ndim == 2] + [1])
+        bias, sigma = _c(np.broadcast_to(bias, (B, _abi.NX))), _c(np.broadcast_to(sigma, (B, _abi.NX)))
+        tab = (_abi.ObserveInstance * B)()
+        for b in range(B):
+            tab[b].bias[:] = bias[b].tolist()
+            tab[b].sigma[:] = sigma[b].tolist()
+        return tab
+
+    def set_observation_instances(self, bias, sigma):
+        """hsqp_observe_set_instances: per instance a constant bias and the standard deviation of white Gaussian noise on every entry of the state
+        the MPC measures (pack_observation); bias None: no table.  The plant never sees it."""
+        if bias is None:
+            self._check(self.lib.hsqp_observe_set_instances(self.h, 0, None))
+            return
+        tab = self.pack_observation(bias, sigma)
+        self._check(self.lib.hsqp_observe_set_instances(self.h, len(tab), tab))
+
+    def set_observation_instances_device(self, batch, table_ptr):
+        """hsqp_observe_set_instances_device: the table in device memory (address); its values are not checked."""
+        self._check(self.lib.hsqp_observe_set_instances_device(self.h, int(batch), C.cast(C.c_void_p(int(table_ptr)), C.POINTER(_abi.ObserveInstance))))
+
+    def clear_observation(self):
+        self._check(self.lib.hsqp_observe_clear(self.h))
+
+    def get_observation(self, batch):
+        """hsqp_observe_get: dict(sensor_delay, compute_delay, seed, bias [batch, 58], sigma [batch, 58]); instances past the table are neutral."""
+        st, tab = _abi.ObserveSettings(), (_abi.ObserveInstance * int(batch))()
+        self._check(self.lib.hsqp_observe_get(self.h, C.byref(st), int(batch), tab))
+        return dict(sensor_delay=int(st.sensor_delay), compute_delay=int(st.compute_delay), seed=int(st.seed),
+                    bias=np.array([list(t.bias) for t in tab]), sigma=np.array([list(t.sigma) for t in tab]))
+
+    def observe(self, x, draw):
+        """hsqp_observe_eval: y [B, 58], what instance b's entry of the table makes of x[b] at draw index `draw` (bias and noise, no delay)."""
+        x = _c(np.atleast_2d(x))
+        y = np.zeros_like(x)
+        self._check(self.lib.hsqp_observe_eval(self.h, x.shape[0], C.c_uint32(int(draw)), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp)))
+        return y
+
+    def observe_device(self, batch, draw, x_ptr, y_ptr):
+        """hsqp_observe_eval_device: the same with both arrays in device memory (addresses)."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp)  # noqa: E731
+        self._check(self.lib.hsqp_observe_eval_device(self.h, int(batch), C.c_uint32(int(draw)), cast(x_ptr), cast(y_ptr)))
+
+    def last_observation(self):
+        """hsqp_observe_last: (y [B, 58], t_p) — the observation the last completed cycle of the loop used and its problem time."""
+        y, tp = np.zeros((max(self._loop_batch, 1), _abi.NX)), C.c_double(0.0)
+        self._check(self.lib.hsqp_observe_last(self.h, y.ctypes.data_as(_dp), C.byref(tp)))
+        return y, tp.value
 
     # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
     def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
