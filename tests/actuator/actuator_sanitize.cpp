@@ -7,20 +7,8 @@
 #include <cstdio>
 #include <vector>
 
-#include "../../include/hsqp_actuator.h"
-#include "../../include/hsqp_contact.h"
-#include "../../include/hsqp_plant.h"
-#include "../../include/hsqp_push.h"
-#include "../../include/hsqp_rollout.h"
-
-extern "C" {
-void* ace_create(const hsqp_model_desc* md, char* err, int errlen);
-void ace_destroy(void* h);
-void ace_rollout(void* h, const hsqp_plant_settings* ps, const hsqp_actuator_settings* as, const hsqp_contact_settings* cs, const hsqp_rollout_settings* st, int N,
-                 const double* dts, double dt, const double* xt, const double* ut, const double* K, const double* uff, int first, int count, int B, const double* s0,
-                 const double* x0, double duration, int n, const int32_t* n_pushes, const hsqp_push* pushes, int max_pushes, const double* stamp0, double* x, double* u,
-                 int32_t* status, int32_t* steps, int32_t* rejected, double* last);
-}
+#define ROLLOUT_EMU_DECLARATIONS_ONLY
+#include "../rollout/rollout_emu.h"
 
 int main(int argc, char** argv) {
   if (argc != 2) { fprintf(stderr, "usage: actuator_sanitize DESC_FILE\n"); return 2; }
@@ -29,7 +17,7 @@ int main(int argc, char** argv) {
   if (!f || fread(image.data(), 1, image.size(), f) != image.size()) { fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
   fclose(f);
   char err[256] = "";
-  void* h = ace_create(reinterpret_cast<const hsqp_model_desc*>(image.data()), err, sizeof err);
+  void* h = emu_create(reinterpret_cast<const hsqp_model_desc*>(image.data()), err, sizeof err);
   if (!h) { fprintf(stderr, "%s\n", err); return 1; }
   const int N = 4, B = 2, n = 2, NX = HSQP_NX, NU = HSQP_NU, NJ = HSQP_NJ;
   std::vector<double> xt((size_t)B * (N + 1) * NX, 0.0), ut((size_t)B * N * NU, 0.0), x0((size_t)B * NX, 0.0);
@@ -48,9 +36,11 @@ int main(int argc, char** argv) {
   const double s0[2] = {0.0, 0.003};
   std::vector<double> x((size_t)B * n * NX), u((size_t)B * n * NU), last((size_t)B * 3 * NJ);
   int32_t status[2], steps[2], rejected[2];
-  ace_rollout(h, &ps, &as, nullptr, &st, N, nullptr, 0.01, xt.data(), ut.data(), nullptr, nullptr, 0, 0, B, s0, x0.data(), 1.0 / 64.0, n, nullptr, nullptr, 0, nullptr,
-              x.data(), u.data(), status, steps, rejected, last.data());
-  ace_destroy(h);
+  emu_rollout_call c = {};
+  c.ut = ut.data(); c.xt = xt.data(); c.dt = 0.01; c.N = N; c.B = B; c.st = &st; c.s0 = s0; c.x0 = x0.data(); c.duration = 1.0 / 64.0; c.n = n;
+  c.x = x.data(); c.u = u.data(); c.status = status; c.steps = steps; c.rejected = rejected; c.last = last.data(); c.plant = &ps; c.actuator = &as;
+  emu_rollout(h, &c);
+  emu_destroy(h);
   bool ok = true;
   for (int b = 0; b < B; ++b) ok = ok && status[b] == HSQP_ROLLOUT_OK && steps[b] >= 6;
   for (double v : x) ok = ok && std::isfinite(v);

@@ -1,65 +1,23 @@
 // TEST INFRASTRUCTURE: the host build of the ground contact of the torque plant (wb_humanoid_mpc_amd/csrc/hsqp_contact.h, hsqp_plant.h, hsqp_rollout.h,
 // k_rollout_plant, k_contact_eval) with a one-lane context, for tests/test_contact.py (compiled by the test with -ffp-contract=off, also with
-// -DHSQP_EMU_REVERSE).  A shared library loaded through ctypes (the model image comes from the binding's hsqp_model_desc).  cs: the contact setting
-// (null or enabled = 0: no contact), ground: the per-instance table [B] (null: the setting's values).
-//   cte_create(desc, err, len) / cte_destroy(h)
+// -DHSQP_EMU_REVERSE).  A shared library loaded through ctypes: the shared entries of tests/rollout/rollout_emu.h (the rollout itself), and the point-wise
+// ones below.  cs: the contact setting (null or enabled = 0: no contact), ground: the per-instance table [1] (null: the setting's values).
 //   cte_eval(h, cs, ground [1] or null, x [58], force [8][3], pen [8]): hsqp_contact_eval for one instance
 //   cte_accel(h, cs, ground [1] or null, x [58], W [12], tau [23], armature [23], n_push, pushes, vd [29]): forward dynamics at the state x under the
 //              joint torques tau, every given push and — contact on — the contact forces, else the contact wrenches W
-//   cte_rollout(h, plant, cs, ground [B] or null, settings, N, dts, dt, xt, ut, K, uff, first, count, B, s0, x0, duration, n, n_pushes, pushes, max_pushes,
-//               stamp0, x, u, status, steps, rejected): ple_rollout of tests/plant/plant_emu.cpp with the ground
-//   cte_ws_bytes() / cte_ws_bytes_plain(): sizeof of the rollout workspace (the kernel's LDS) on the ground / of the plant's own instantiation
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "hsqp_host.h"
-#include "hsqp_rollout.h"
-
-using namespace hsqp;
+#include "../rollout/rollout_emu.h"
 
 using WS = RolloutWS<PlantContactStage>;   // the instantiation on the ground
-using WS0 = RolloutWS<PlantStage>;        // the plant's own (contact off)
-
-template <class T>
-static std::unique_ptr<T> fresh() {
-  // the workspace starts as NaN bit patterns, like the device's uninitialised LDS: a read of something never written shows
-  std::unique_ptr<T> w(new T);
-  std::memset(static_cast<void*>(w.get()), 0xFF, sizeof(T));
-  return w;
-}
-
-static void gains_of(const hsqp_plant_settings& ps, double* g) {
-  for (int j = 0; j < NJ; ++j) { g[j] = ps.kp[j]; g[NJ + j] = ps.kd[j]; g[2 * NJ + j] = ps.armature[j]; }
-}
 
 // the kernels' view of the setting: the ground of B instances in `store`
 static ContactParams params_of(const hsqp_contact_settings* cs, const hsqp_contact_ground* ground, int B, std::vector<hsqp_contact_ground>& store) {
   if (!cs || !cs->enabled) return ContactParams{nullptr, 0.0, 0.0, 0.0};
-  store.assign(B, hsqp_contact_ground{cs->ground_height, cs->mu});
-  if (ground) for (int b = 0; b < B; ++b) store[b] = ground[b];
+  store.resize(B);
+  contact_fill_ground(*cs, ground, B, B, store.data());
   return ContactParams{store.data(), cs->stiffness, cs->damping, cs->slip_velocity};
 }
 
-// every push active from 0 for one second; the segment starts at 0
-static unsigned load_pushes(const Ctx& ctx, int n_push, const hsqp_push* pushes, PushSet& set) {
-  std::unique_ptr<hsqp_push[]> tab(new hsqp_push[n_push > 0 ? n_push : 1]);
-  for (int i = 0; i < n_push; ++i) { tab[i] = pushes[i]; tab[i].t_start = 0.0; tab[i].duration = 1.0; }
-  const int32_t np = n_push;
-  push_load(ctx, PushTable{&np, tab.get(), n_push > 0 ? n_push : 1, nullptr, 0}, 0, set);
-  return push_active(set, 0.0);
-}
-
 extern "C" {
-
-void* cte_create(const hsqp_model_desc* md, char* err, int errlen) {
-  auto* dm = new DevModel;
-  const std::string e = build_dev_model(*md, *dm);
-  if (!e.empty()) { snprintf(err, errlen, "%s", e.c_str()); delete dm; return nullptr; }
-  return dm;
-}
-void cte_destroy(void* h) { delete static_cast<DevModel*>(h); }
 
 void cte_eval(void* h, const hsqp_contact_settings* cs, const hsqp_contact_ground* ground, const double* x, double* force, double* pen) {
   const DevModel& dm = *static_cast<DevModel*>(h);
@@ -88,39 +46,5 @@ void cte_accel(void* h, const hsqp_contact_settings* cs, const hsqp_contact_grou
   plant_forward_dynamics(ctx, dm, w->sw.st, w->sw.pl, w->push, mask, cp.ground ? &w->sw.ct : nullptr);
   for (int i = 0; i < NV; ++i) vd[i] = w->sw.pl.vd[i];
 }
-
-void cte_rollout(void* h, const hsqp_plant_settings* ps, const hsqp_contact_settings* cs, const hsqp_contact_ground* ground, const hsqp_rollout_settings* st, int N,
-                 const double* dts, double dt, const double* xt, const double* ut, const double* K, const double* uff, int first, int count, int B, const double* s0,
-                 const double* x0, double duration, int n, const int32_t* n_pushes, const hsqp_push* pushes, int max_pushes, const double* stamp0, double* x, double* u,
-                 int32_t* status, int32_t* steps, int32_t* rejected) {
-  const DevModel& dm = *static_cast<DevModel*>(h);
-  const PushTable tbl{n_pushes, pushes, max_pushes, stamp0, 1};
-  auto w = fresh<WS>();
-  auto w0 = fresh<WS0>();
-  const Ctx ctx{0, 1, nullptr};
-  double g[3 * NJ];
-  gains_of(*ps, g);
-  const PlantParams pp{g, ps->lookahead, xt};
-  std::vector<hsqp_contact_ground> store;
-  const ContactParams cp = params_of(cs, ground, B, store);
-  for (int b = 0; b < B; ++b) {
-    const RolloutPolicy p{ut + (size_t)b * N * NU, dts ? dts + (size_t)b * N : nullptr, N, dt, K ? K + (size_t)b * count * NU * NX : nullptr,
-                          uff ? uff + (size_t)b * count * NU : nullptr, first, count, 0};
-    // the instantiation the handle launches: on the ground, or the plant's own
-    if (cp.ground) {
-      plant_load(ctx, pp, b, N, w->sw.pl);
-      contact_load(ctx, cp, b, w->sw.ct);
-      rollout_instance(ctx, dm, *w, p, *st, s0[b], x0 + (size_t)b * NX, duration, n, x ? x + (size_t)b * n * NX : nullptr, u ? u + (size_t)b * n * NU : nullptr,
-                       status + b, steps ? steps + b : nullptr, rejected ? rejected + b : nullptr, tbl, b);
-    } else {
-      plant_load(ctx, pp, b, N, w0->sw.pl);
-      rollout_instance(ctx, dm, *w0, p, *st, s0[b], x0 + (size_t)b * NX, duration, n, x ? x + (size_t)b * n * NX : nullptr, u ? u + (size_t)b * n * NU : nullptr,
-                       status + b, steps ? steps + b : nullptr, rejected ? rejected + b : nullptr, tbl, b);
-    }
-  }
-}
-
-int cte_ws_bytes() { return (int)sizeof(WS); }
-int cte_ws_bytes_plain() { return (int)sizeof(WS0); }
 
 }  // extern "C"

@@ -12,6 +12,7 @@ import actuator_ref as A
 import contact_ref as CR
 import plant_ref as PL
 import push_ref as P
+import rollout_emu as E
 import rollout_ref as R
 from test_contact import contact_struct, grounded
 from test_plant import L_ELBOW, plant_case, settings_struct
@@ -99,29 +100,18 @@ def test_defaults_and_null_arguments():
 
 # ---------------------------------------------------------------------------------------------- host build of the kernel source
 def build_emu(path, *defines):
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Werror", "-fPIC", "-shared",
-                           *defines, "-I", CSRC, os.path.join(ROOT, "tests", "actuator", "actuator_emu.cpp"), "-o", str(path)])
-    lib = C.CDLL(str(path))
-    lib.ace_create.restype = C.c_void_p
-    lib.ace_create.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.ace_destroy.argtypes = [C.c_void_p]
+    lib = E.build(path, os.path.join("actuator", "actuator_emu.cpp"), "-ffp-contract=off", *defines)
     lib.ace_law.argtypes = [_as, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     lib.ace_tick.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), _dp]
-    lib.ace_rollout.argtypes = [C.c_void_p, _pl, _as, _cs, C.POINTER(_abi.RolloutSettings), C.c_int, _dp, C.c_double, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
-                                _dp, _dp, C.c_double, C.c_int, _ip, _pp, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _dp]
-    lib.ace_ws_bytes.argtypes = [C.c_int]
     return lib
 
 
 class Emu:
     def __init__(self, lib, model):
-        err = C.create_string_buffer(256)
-        h = lib.ace_create(C.byref(model.desc), err, 256)
-        assert h, err.value
-        self.lib, self.h = lib, C.c_void_p(h)
+        self.lib, self.h = lib, E.create(lib, model)
 
     def close(self):
-        self.lib.ace_destroy(self.h)
+        self.lib.emu_destroy(self.h)
 
     def law(self, ac, pl, cmd, x):
         out = np.zeros((4, NJ))
@@ -137,21 +127,8 @@ class Emu:
 
     def rollout(self, pl, ac, st, case, s0, x0, duration, n, pushes=None, ct=None, enabled=1):
         """(x, u, status, steps, rejected, last [B][3][23]); ac None: no actuator set; ct: a contact_ref setting (None: no ground)."""
-        B = len(s0)
-        rep = lambda a: None if a is None else np.ascontiguousarray(np.repeat(a[None], B, axis=0))   # noqa: E731
-        xt, ut, dts, K, uff = rep(case["xt"]), rep(case["ut"]), rep(case["dts"]), rep(case["K"]), rep(case["uff"])
-        s = _abi.RolloutSettings(**st)
-        ps = settings_struct(pl)
-        a = None if ac is None else C.byref(actuator_struct(ac, enabled))
-        c = None if ct is None else C.byref(contact_struct(ct))
-        x, u, last = np.zeros((B, n, NX)), np.zeros((B, n, NU)), np.full((B, 3, NJ), -7.0)
-        status, steps, rej = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        s0, x0 = np.ascontiguousarray(s0, dtype=float), np.ascontiguousarray(x0, dtype=float)
-        npush, tab, mp = (None, None, 0) if pushes is None else solver.HipSqpSolver.pack_pushes(pushes)
-        self.lib.ace_rollout(self.h, C.byref(ps), a, c, C.byref(s), len(case["ut"]), _p(dts), case["dt"], _p(xt), _p(ut), _p(K), _p(uff), 0, len(case["K"]), B,
-                             _p(s0), _p(x0), duration, n, None if npush is None else npush.ctypes.data_as(_ip), None if tab is None else C.cast(tab, _pp), mp, None,
-                             _p(x), _p(u), status.ctypes.data_as(_ip), steps.ctypes.data_as(_ip), rej.ctypes.data_as(_ip), _p(last))
-        return x, u, status, steps, rej, last
+        return E.rollout(self.lib, self.h, case, st, s0, x0, duration, n, plant=settings_struct(pl), actuator=None if ac is None else actuator_struct(ac, enabled),
+                         contact=None if ct is None else contact_struct(ct), pushes=pushes)
 
 
 @pytest.fixture(scope="module")
@@ -358,7 +335,7 @@ def test_reverse_order_emulation_is_bit_identical(emu, emu_reverse, model, oracl
 
 
 def test_the_workspaces_fit_the_lds(emu):
-    plain, ground = emu.lib.ace_ws_bytes(0), emu.lib.ace_ws_bytes(1)
+    plain, ground = emu.lib.emu_ws_bytes(0, 1, 0, 1, 0), emu.lib.emu_ws_bytes(0, 1, 1, 1, 0)
     print(f"rollout workspace under the actuator model: {plain} bytes, on the ground {ground} bytes")
     assert plain <= 65536 and ground <= 65536 and ground > plain
 

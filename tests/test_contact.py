@@ -12,6 +12,7 @@ import pytest
 import contact_ref as CR
 import plant_ref as PL
 import push_ref as P
+import rollout_emu as E
 import rollout_ref as R
 from test_plant import ACC_TOL, FD_TOL, Emu as PlantEmu, build_emu as build_plant_emu, plant_case, settings_struct
 from test_rollout import rel, start_states, state_input
@@ -109,28 +110,18 @@ def test_defaults_and_null_arguments():
 
 # ---------------------------------------------------------------------------------------------- host build of the kernel source
 def build_emu(path, *defines):
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Werror", "-fPIC", "-shared",
-                           *defines, "-I", CSRC, os.path.join(ROOT, "tests", "contact", "contact_emu.cpp"), "-o", str(path)])
-    lib = C.CDLL(str(path))
-    lib.cte_create.restype = C.c_void_p
-    lib.cte_create.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.cte_destroy.argtypes = [C.c_void_p]
+    lib = E.build(path, os.path.join("contact", "contact_emu.cpp"), "-ffp-contract=off", *defines)
     lib.cte_eval.argtypes = [C.c_void_p, _cs, _cg, _dp, _dp, _dp]
     lib.cte_accel.argtypes = [C.c_void_p, _cs, _cg, _dp, _dp, _dp, _dp, C.c_int, _pp, _dp]
-    lib.cte_rollout.argtypes = [C.c_void_p, _pl, _cs, _cg, C.POINTER(_abi.RolloutSettings), C.c_int, _dp, C.c_double, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
-                                _dp, _dp, C.c_double, C.c_int, _ip, _pp, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]
     return lib
 
 
 class Emu:
     def __init__(self, lib, model):
-        err = C.create_string_buffer(256)
-        h = lib.cte_create(C.byref(model.desc), err, 256)
-        assert h, err.value
-        self.lib, self.h = lib, C.c_void_p(h)
+        self.lib, self.h = lib, E.create(lib, model)
 
     def close(self):
-        self.lib.cte_destroy(self.h)
+        self.lib.emu_destroy(self.h)
 
     def eval(self, ct, x, ground=None):
         """(force [8][3], penetration [8]); ground: (height, mu) of the instance's table entry."""
@@ -148,21 +139,8 @@ class Emu:
         return vd
 
     def rollout(self, pl, ct, st, case, s0, x0, duration, n, pushes=None, ground=None):
-        B = len(s0)
-        rep = lambda a: None if a is None else np.ascontiguousarray(np.repeat(a[None], B, axis=0))   # noqa: E731
-        xt, ut, dts, K, uff = rep(case["xt"]), rep(case["ut"]), rep(case["dts"]), rep(case["K"]), rep(case["uff"])
-        s = _abi.RolloutSettings(**st)
-        ps = settings_struct(pl)
-        cs = None if ct is None else contact_struct(ct)
-        x, u = np.zeros((B, n, NX)), np.zeros((B, n, NU))
-        status, steps, rej = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        s0, x0 = np.ascontiguousarray(s0, dtype=float), np.ascontiguousarray(x0, dtype=float)
-        npush, tab, mp = (None, None, 0) if pushes is None else solver.HipSqpSolver.pack_pushes(pushes)
-        self.lib.cte_rollout(self.h, C.byref(ps), None if cs is None else C.byref(cs), ground_array(ground), C.byref(s), len(case["ut"]), _p(dts), case["dt"], _p(xt),
-                             _p(ut), _p(K), _p(uff), 0, len(case["K"]), B, _p(s0), _p(x0), duration, n, None if npush is None else npush.ctypes.data_as(_ip),
-                             None if tab is None else C.cast(tab, _pp), mp, None, _p(x), _p(u), status.ctypes.data_as(_ip), steps.ctypes.data_as(_ip),
-                             rej.ctypes.data_as(_ip))
-        return x, u, status, steps, rej
+        return E.rollout(self.lib, self.h, case, st, s0, x0, duration, n, plant=settings_struct(pl), contact=None if ct is None else contact_struct(ct),
+                         ground=ground_array(ground), pushes=pushes)[:5]
 
 
 @pytest.fixture(scope="module")
@@ -392,8 +370,7 @@ def test_reverse_order_emulation_is_bit_identical(emu, emu_reverse, model, cases
 
 
 def test_the_workspace_fits_the_lds(emu):
-    emu.lib.cte_ws_bytes.restype = emu.lib.cte_ws_bytes_plain.restype = C.c_int
-    n, n0 = emu.lib.cte_ws_bytes(), emu.lib.cte_ws_bytes_plain()
+    n, n0 = emu.lib.emu_ws_bytes(0, 1, 1, 0, 0), emu.lib.emu_ws_bytes(0, 1, 0, 0, 0)
     print("sizeof(RolloutWS<PlantContactStage>) =", n, " sizeof(RolloutWS<PlantStage>) =", n0)
     assert n0 == 33200                      # the plant without a ground keeps its workspace
     assert n0 < n <= n0 + 2048              # the contact set is well under 2 KB on top of it

@@ -12,8 +12,9 @@ import contact_ref as CR
 import inertia_ref as IR
 import plant_ref as PL
 import push_ref as P
+import rollout_emu as E
 import rollout_ref as R
-from test_contact import contact_struct, grounded
+from test_contact import contact_struct, grounded, zero_wrench_case
 from test_plant import ACC_TOL, FD_TOL, Emu as PlantEmu, build_emu as build_plant_emu, plant_case, settings_struct, states
 from test_rollout import rel, start_states
 from wb_humanoid_mpc_amd import _abi, solver
@@ -105,17 +106,9 @@ def test_defaults_and_null_handles():
 
 # ---------------------------------------------------------------------------------------------- host build of the kernel source
 def build_emu(path, *defines):
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Werror", "-fPIC", "-shared",
-                           *defines, "-I", CSRC, os.path.join(ROOT, "tests", "inertia", "inertia_emu.cpp"), "-o", str(path)])
-    lib = C.CDLL(str(path))
-    lib.ine_create.restype = C.c_void_p
-    lib.ine_create.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.ine_destroy.argtypes = [C.c_void_p]
+    lib = E.build(path, os.path.join("inertia", "inertia_emu.cpp"), "-ffp-contract=off", *defines)
     lib.ine_eval.argtypes = [C.c_void_p, _ii, _dp, _dp, _dp, _dp]
     lib.ine_accel.argtypes = [C.c_void_p, _ii, _cs, _dp, _dp, _dp, _dp, C.c_int, _pp, _dp]
-    lib.ine_rollout.argtypes = [C.c_void_p, _pl, _ii, C.POINTER(_abi.RolloutSettings), C.c_int, _dp, C.c_double, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
-                                _dp, _dp, C.c_double, C.c_int, _ip, _pp, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]
-    lib.ine_ws_bytes.argtypes = [C.c_int]
     return lib
 
 
@@ -123,13 +116,10 @@ class Emu:
     """variation: (mass_scale [24], payloads) of one instance, or None: no table."""
 
     def __init__(self, lib, model):
-        err = C.create_string_buffer(256)
-        h = lib.ine_create(C.byref(model.desc), err, 256)
-        assert h, err.value
-        self.lib, self.h = lib, C.c_void_p(h)
+        self.lib, self.h = lib, E.create(lib, model)
 
     def close(self):
-        self.lib.ine_destroy(self.h)
+        self.lib.emu_destroy(self.h)
 
     def dynamics(self, variation, x):
         M, nle, mass = np.zeros((NV, NV)), np.zeros(NV), np.zeros(1)
@@ -145,20 +135,8 @@ class Emu:
         return vd
 
     def rollout(self, pl, variations, st, case, s0, x0, duration, n, pushes=None):
-        B = len(s0)
-        rep = lambda a: None if a is None else np.ascontiguousarray(np.repeat(a[None], B, axis=0))   # noqa: E731
-        xt, ut, dts, K, uff = rep(case["xt"]), rep(case["ut"]), rep(case["dts"]), rep(case["K"]), rep(case["uff"])
-        s = _abi.RolloutSettings(**st)
-        ps = settings_struct(pl)
-        x, u = np.zeros((B, n, NX)), np.zeros((B, n, NU))
-        status, steps, rej = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        s0, x0 = np.ascontiguousarray(s0, dtype=float), np.ascontiguousarray(x0, dtype=float)
-        npush, tab, mp = (None, None, 0) if pushes is None else solver.HipSqpSolver.pack_pushes(pushes)
-        self.lib.ine_rollout(self.h, C.byref(ps), None if variations is None else table_of(variations), C.byref(s), len(case["ut"]), _p(dts), case["dt"], _p(xt),
-                             _p(ut), _p(K), _p(uff), 0, len(case["K"]), B, _p(s0), _p(x0), duration, n, None if npush is None else npush.ctypes.data_as(_ip),
-                             None if tab is None else C.cast(tab, _pp), mp, None, _p(x), _p(u), status.ctypes.data_as(_ip), steps.ctypes.data_as(_ip),
-                             rej.ctypes.data_as(_ip))
-        return x, u, status, steps, rej
+        return E.rollout(self.lib, self.h, case, st, s0, x0, duration, n, plant=settings_struct(pl), inertia=None if variations is None else table_of(variations),
+                         pushes=pushes)[:5]
 
 
 @pytest.fixture(scope="module")
@@ -350,9 +328,43 @@ def test_reverse_order_emulation_is_bit_identical(emu, emu_reverse, model, varie
             assert np.array_equal(va, vb), integrator
 
 
+# ---------------------------------------------------------------------------------------------- every instantiation of the torque plant
+def test_every_torque_configuration_with_inert_parts_is_the_plant_bit_for_bit(emu, model, oracle):
+    """The eight configurations of the torque plant (ground x actuator x inertia table) through the one emulated entry, every part that is on inert: a
+    neutral table, the ground 10 m below the feet under a policy without contact wrenches, the actuator at its defaults with a continuous command.  Each
+    runs its own instantiation (the library's rule picks it) and gives the bits of the plain torque plant."""
+    lib = solver.load_library()
+    rng = np.random.default_rng(73)
+    B, N, n = 2, 4, 2
+    full = zero_wrench_case(model, "uniform", rng)
+    case = dict(full, ut=full["ut"][:N], xt=full["xt"][:N + 1], K=full["K"][:N + 1], uff=full["uff"][:N + 1])
+    x0, s0 = start_states(model, False, rng, B), np.array([0.0, 0.003])
+    pl = settings_struct(PL.plant(**GAINS))
+    far = contact_struct(CR.contact(model, ground_height=min(grounded(oracle, model, x, above=-10.0) for x in x0)))
+    act = _abi.ActuatorSettings()
+    lib.hsqp_actuator_defaults(C.byref(act))
+    act.command_period = 0.0
+    neutral = (_abi.InertiaInstance * B)()
+    for e in neutral:
+        lib.hsqp_inertia_defaults(C.byref(e))
+    sizes = set()
+    for controller in (R.FEEDFORWARD, R.FEEDBACK):
+        st = R.settings(R.RK4, controller, initial_step=0.004)
+        run = lambda g, a, v: E.rollout(emu.lib, emu.h, case, st, s0, x0, 1.0 / 64.0, n, plant=pl, contact=far if g else None,   # noqa: E731
+                                        actuator=act if a else None, inertia=neutral if v else None)
+        want = run(0, 0, 0)
+        assert (want[2] == R.OK).all() and (want[3] == 4).all()
+        for g, a, v in [(g, a, v) for v in (0, 1) for a in (0, 1) for g in (0, 1)][1:]:
+            got = run(g, a, v)
+            sizes.add(emu.lib.emu_ws_bytes(0, 1, g, a, v))
+            for name, x, y in zip(("x", "u", "status", "steps"), got, want):
+                assert x.tobytes() == y.tobytes(), (controller, g, a, v, name)
+    assert len(sizes) == 7          # seven workspaces of their own beside the plain plant's: no two configurations ran the same instantiation
+
+
 # ---------------------------------------------------------------------------------------------- 9: LDS
 def test_every_workspace_fits_the_lds(emu):
-    sizes = [emu.lib.ine_ws_bytes(k) for k in range(5)]
+    sizes = [emu.lib.emu_ws_bytes(0, 1, k & 1, k >> 1, 1) for k in range(4)] + [emu.lib.ine_eval_ws_bytes()]
     print("rollout workspaces on the varied plant (plain, ground, actuator, both) and hsqp_inertia_eval's:", sizes)
     assert all(0 < s <= 65536 for s in sizes), sizes
     assert sizes[0] < sizes[1] < sizes[3] and sizes[0] < sizes[2] < sizes[3]

@@ -10,6 +10,7 @@ import pytest
 
 import plant_ref as PL
 import push_ref as P
+import rollout_emu as E
 import rollout_ref as R
 from test_rollout import make_case, rel, start_states, state_input
 from wb_humanoid_mpc_amd import _abi, solver
@@ -85,29 +86,19 @@ def test_defaults_and_null_arguments():
 
 # ---------------------------------------------------------------------------------------------- host build of the kernel source
 def build_emu(path, *defines):
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Werror", "-fPIC", "-shared",
-                           *defines, "-I", CSRC, os.path.join(ROOT, "tests", "plant", "plant_emu.cpp"), "-o", str(path)])
-    lib = C.CDLL(str(path))
-    lib.ple_create.restype = C.c_void_p
-    lib.ple_create.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.ple_destroy.argtypes = [C.c_void_p]
+    lib = E.build(path, os.path.join("plant", "plant_emu.cpp"), "-ffp-contract=off", *defines)
     lib.ple_accel.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int, _pp, _dp]
     lib.ple_tau.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.ple_eval.argtypes = [C.c_void_p, _pl, C.c_int, C.c_int, _dp, C.c_double, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, C.c_int, _pp, _dp]
-    lib.ple_rollout.argtypes = [C.c_void_p, _pl, C.POINTER(_abi.RolloutSettings), C.c_int, _dp, C.c_double, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
-                                _dp, _dp, C.c_double, C.c_int, _ip, _pp, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]
     return lib
 
 
 class Emu:
     def __init__(self, lib, model):
-        err = C.create_string_buffer(256)
-        h = lib.ple_create(C.byref(model.desc), err, 256)
-        assert h, err.value
-        self.lib, self.h = lib, C.c_void_p(h)
+        self.lib, self.h = lib, E.create(lib, model)
 
     def close(self):
-        self.lib.ple_destroy(self.h)
+        self.lib.emu_destroy(self.h)
 
     def accel(self, x, W, tau, armature, pushes=()):
         _, tab, _ = solver.HipSqpSolver.pack_pushes([list(pushes)])
@@ -130,19 +121,7 @@ class Emu:
         return k
 
     def rollout(self, pl, st, case, s0, x0, duration, n, pushes=None):
-        B = len(s0)
-        rep = lambda a: None if a is None else np.ascontiguousarray(np.repeat(a[None], B, axis=0))   # noqa: E731
-        xt, ut, dts, K, uff = rep(case["xt"]), rep(case["ut"]), rep(case["dts"]), rep(case["K"]), rep(case["uff"])
-        s = _abi.RolloutSettings(**st)
-        ps = settings_struct(pl)
-        x, u = np.zeros((B, n, NX)), np.zeros((B, n, NU))
-        status, steps, rej = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        s0, x0 = np.ascontiguousarray(s0, dtype=float), np.ascontiguousarray(x0, dtype=float)
-        npush, tab, mp = (None, None, 0) if pushes is None else solver.HipSqpSolver.pack_pushes(pushes)
-        self.lib.ple_rollout(self.h, C.byref(ps), C.byref(s), len(case["ut"]), _p(dts), case["dt"], _p(xt), _p(ut), _p(K), _p(uff), 0, len(case["K"]), B, _p(s0), _p(x0),
-                             duration, n, None if npush is None else npush.ctypes.data_as(_ip), None if tab is None else C.cast(tab, _pp), mp, None, _p(x), _p(u),
-                             status.ctypes.data_as(_ip), steps.ctypes.data_as(_ip), rej.ctypes.data_as(_ip))
-        return x, u, status, steps, rej
+        return E.rollout(self.lib, self.h, case, st, s0, x0, duration, n, plant=settings_struct(pl), pushes=pushes)[:5]
 
 
 @pytest.fixture(scope="module")

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import push_ref as P
+import rollout_emu as E
 import rollout_ref as R
 from test_rollout import make_case, near_threshold, rel, start_states, state_input
 from wb_humanoid_mpc_amd import _abi, solver
@@ -65,30 +66,18 @@ def test_pack_pushes_takes_dicts_and_tuples():
 
 # ---------------------------------------------------------------------------------------------- host build of the kernel source
 def build_emu(path, *defines):
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-Werror", "-fPIC", "-shared",
-                           *defines, "-I", CSRC, os.path.join(ROOT, "tests", "push", "push_emu.cpp"), "-o", str(path)])
-    lib = C.CDLL(str(path))
-    lib.pe_create.restype = C.c_void_p
-    lib.pe_create.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.pe_destroy.argtypes = [C.c_void_p]
-    lib.pe_rollout.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), C.c_int, _dp, C.c_double, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
-                               _dp, _dp, C.c_double, C.c_int, _ip, _pp, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]
+    lib = E.build(path, os.path.join("push", "push_emu.cpp"), "-ffp-contract=off", *defines)
     lib.pe_flow.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _pp, _dp]
     return lib
 
 
 class Emu:
     def __init__(self, lib, model, cmodel):
-        self.lib, self.h = lib, {}
-        for name, m in (("wb", model), ("centroidal", cmodel)):
-            err = C.create_string_buffer(256)
-            h = lib.pe_create(C.byref(m.desc), err, 256)
-            assert h, err.value
-            self.h[name] = C.c_void_p(h)
+        self.lib, self.h = lib, {"wb": E.create(lib, model), "centroidal": E.create(lib, cmodel)}
 
     def close(self):
         for h in self.h.values():
-            self.lib.pe_destroy(h)
+            self.lib.emu_destroy(h)
 
     def flow(self, name, x, u, pushes):
         xp = np.zeros(NX)
@@ -100,23 +89,7 @@ class Emu:
 
     def rollout(self, name, st, case, s0, x0, duration, n, pushes=None, stamp0=None):
         """The host build over a batch: (x [B][n][58], u [B][n][35], status, steps, rejected).  pushes: a list per instance, or None: no table."""
-        B = len(s0)
-        ut = np.ascontiguousarray(np.repeat(case["ut"][None], B, axis=0))
-        dts = None if case["dts"] is None else np.ascontiguousarray(np.repeat(case["dts"][None], B, axis=0))
-        K = uff = None
-        if st["controller"] == R.FEEDBACK:
-            K = np.ascontiguousarray(np.repeat(case["K"][None], B, axis=0))
-            uff = np.ascontiguousarray(np.repeat(case["uff"][None], B, axis=0))
-        s = _abi.RolloutSettings(**st)
-        x, u = np.zeros((B, n, NX)), np.zeros((B, n, NU))
-        status, steps, rej = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        s0, x0 = np.ascontiguousarray(s0, dtype=float), np.ascontiguousarray(x0, dtype=float)
-        npush, tab, mp = (None, None, 0) if pushes is None else solver.HipSqpSolver.pack_pushes(pushes)
-        st0 = None if stamp0 is None else np.ascontiguousarray(stamp0, dtype=float)
-        self.lib.pe_rollout(self.h[name], C.byref(s), len(case["ut"]), _p(dts), case["dt"], _p(ut), _p(K), _p(uff), 0, len(case["K"]), int(case["cent"]), B,
-                            _p(s0), _p(x0), duration, n, None if npush is None else npush.ctypes.data_as(_ip), None if tab is None else C.cast(tab, _pp), mp,
-                            _p(st0), _p(x), _p(u), status.ctypes.data_as(_ip), steps.ctypes.data_as(_ip), rej.ctypes.data_as(_ip))
-        return x, u, status, steps, rej
+        return E.rollout(self.lib, self.h[name], case, st, s0, x0, duration, n, pushes=pushes, stamp0=stamp0)[:5]
 
 
 def _p(a):

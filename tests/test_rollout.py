@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import rollout_emu as E
 import rollout_ref as R
 from conftest import random_state_input
 from test_oracle_centroidal import cent_state_input
@@ -64,30 +65,17 @@ def test_binding_raises_no_device_without_a_gpu(model):
 # ---------------------------------------------------------------------------------------------- host build of the kernel source
 @pytest.fixture(scope="module")
 def remu(tmp_path_factory):
-    lib_path = tmp_path_factory.mktemp("ro") / "librollout_emu.so"
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-Wall", "-Wno-unknown-pragmas", "-Werror", "-fPIC", "-shared", "-I", CSRC,
-                           os.path.join(ROOT, "tests", "rollout", "rollout_emu.cpp"), "-o", str(lib_path)])
-    lib = C.CDLL(str(lib_path))
-    lib.ro_create.restype = C.c_void_p
-    lib.ro_create.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.ro_destroy.argtypes = [C.c_void_p]
-    lib.ro_rollout.argtypes = [C.c_void_p, C.POINTER(_abi.RolloutSettings), C.c_int, _dp, C.c_double, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
-                               _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _ip]
+    lib = E.build(tmp_path_factory.mktemp("ro") / "librollout_emu.so", os.path.join("rollout", "rollout_emu.cpp"))
     lib.ro_flow.argtypes = [C.c_void_p, _dp, _dp, _dp]
     return lib
 
 
 @pytest.fixture(scope="module")
 def handles(remu, model, cmodel):
-    out = {}
-    for name, m in (("wb", model), ("centroidal", cmodel)):
-        err = C.create_string_buffer(256)
-        h = remu.ro_create(C.byref(m.desc), err, 256)
-        assert h, err.value
-        out[name] = C.c_void_p(h)
+    out = {"wb": E.create(remu, model), "centroidal": E.create(remu, cmodel)}
     yield out
     for h in out.values():
-        remu.ro_destroy(h)
+        remu.emu_destroy(h)
 
 
 def _p(a):
@@ -96,20 +84,7 @@ def _p(a):
 
 def emu_rollout(remu, h, st, case, s0, x0, duration, n):
     """The host build over a batch: (x [B][n][58], u [B][n][35], status, steps, rejected)."""
-    B = len(s0)
-    ut = np.ascontiguousarray(np.repeat(case["ut"][None], B, axis=0))
-    dts = None if case["dts"] is None else np.ascontiguousarray(np.repeat(case["dts"][None], B, axis=0))
-    K = uff = None
-    if st["controller"] == R.FEEDBACK:
-        K = np.ascontiguousarray(np.repeat(case["K"][None], B, axis=0))
-        uff = np.ascontiguousarray(np.repeat(case["uff"][None], B, axis=0))
-    s = _abi.RolloutSettings(**st)
-    x, u = np.zeros((B, n, NX)), np.zeros((B, n, NU))
-    status, steps, rej = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
-    s0, x0 = np.ascontiguousarray(s0, dtype=float), np.ascontiguousarray(x0, dtype=float)
-    remu.ro_rollout(h, C.byref(s), len(case["ut"]), _p(dts), case["dt"], _p(ut), _p(K), _p(uff), 0, len(case["K"]), int(case["cent"]), B, _p(s0), _p(x0),
-                    duration, n, _p(x), _p(u), status.ctypes.data_as(_ip), steps.ctypes.data_as(_ip), rej.ctypes.data_as(_ip))
-    return x, u, status, steps, rej
+    return E.rollout(remu, h, case, st, s0, x0, duration, n)[:5]
 
 
 GRIDS = {"uniform": None, "events": [0.01, 0.01, 0.0, 0.01, 0.0, 0.0, 0.01, 0.01, 0.01]}

@@ -20,6 +20,10 @@ struct ActuatorParams {
   double period, vs;      // command_period, friction_velocity
   double* last;           // [B][3][NJ] the record of hsqp_actuator_last: tau_cmd | tau_act | tau_pas of every instance
 };
+// (host) the public setting as ActuatorParams::table reads it: t [3 NJ]
+inline void actuator_pack_table(const hsqp_actuator_settings& s, double* t) {
+  for (int j = 0; j < NJ; ++j) { t[j] = s.effort_limit[j]; t[NJ + j] = s.damping[j]; t[2 * NJ + j] = s.friction[j]; }
+}
 
 // ONE instance's setting and the joint command in force
 struct ActuatorWS {

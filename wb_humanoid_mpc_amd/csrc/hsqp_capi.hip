@@ -985,14 +985,13 @@ __global__ __launch_bounds__(RO_WIN_THREADS) void k_rollout_window(const double*
   }
 }
 
-struct RolloutArgs {
-  const double* ut; const double* dts; int N; double dt;   // resident inputs and grid (dts null: uniform)
-  const double* K; const double* uff; int first, count;     // gain window [B][count] (feedback controller)
-  hsqp_rollout_settings st;
-  const double* s0; const double* x0; double duration; int n;
-  double* x; double* u; int32_t* status; int32_t* steps; int32_t* rejected;
-  PushTable push;                                           // the resident push table (include/hsqp_push.h; n null: none)
-};
+// What either kernel does for its instance is rollout_entry (hsqp_rollout.h), which the host emulation runs.  The kernels spell the same statements out instead of
+// calling it: through one more inlined call the compiler schedules the plant kernels differently (same registers, LDS and scratch, other SGPR spills) and the
+// loop on the torque plant with every option measured 2.7 .. 3.1 % slower than with these bodies (profiles/rollout_entry_ab.txt).  Keep the two in step.
+// k_rollout: the flow maps.  k_rollout_plant: the torque plant (include/hsqp_plant.h), one instantiation per set of its options — the ground (cp), the actuator
+// model (ap), the inertial variation (ip): a block is read only by the instantiations whose SW carries its part.  An option is a parameter of the instantiation
+// because as a run-time branch the contact alone costs the rollout without a ground 3.6 % (measured); whether the command is held (ap.period > 0)
+// is a run-time, workgroup-uniform branch.  rollout_impl picks SW through rollout_dispatch.
 template <class SW>
 __global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restrict__ dm, RolloutArgs a) {
   RolloutWS<SW>& w = *reinterpret_cast<RolloutWS<SW>*>(hsqp_smem);
@@ -1003,15 +1002,6 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restri
                    a.x ? a.x + (size_t)b * a.n * NX : nullptr, a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr,
                    a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
-static_assert(sizeof(RolloutWS<StageWST<false>>) <= 65536 && sizeof(RolloutWS<CentWST<false>>) <= 65536, "the rollout runs without a dynamic-LDS attribute");
-// the rollout on the torque plant (include/hsqp_plant.h, csrc/hsqp_plant.h): the instantiation of its own that a handle with HSQP_PLANT_TORQUE set launches
-// instead of k_rollout<StageWST<false>>, which does not contain it
-// SW = PlantStage: the plant as it is without a ground (cp is not read); SW = PlantContactStage: on the resident ground of include/hsqp_contact.h.
-// Contact is a parameter of the instantiation: as a run-time branch it costs the rollout without a ground 3.6 % (measured)
-// SW = PlantActStage / PlantContactActStage: either of them under the actuator model of include/hsqp_actuator.h (ap is read by these two only), again a
-// parameter of the instantiation; whether the command is held (ap.period > 0) is a run-time, workgroup-uniform branch inside them
-// SW = PlantVaried<...> of any of the four: on the per-instance inertial variations of include/hsqp_inertia.h (ip is read by these four only), once more a
-// parameter of the instantiation: the handle launches them only while a table is set
 template <class SW>
 __global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp, ContactParams cp, ActuatorParams ap,
                                                               InertiaParams ip) {
@@ -1027,11 +1017,6 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __
   rollout_instance(ctx, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
                    a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr, a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
-static_assert(sizeof(RolloutWS<PlantStage>) <= 65536, "the rollout on the torque plant runs without a dynamic-LDS attribute");
-static_assert(sizeof(RolloutWS<PlantContactStage>) <= 65536, "the rollout on the torque plant over the ground runs without a dynamic-LDS attribute");
-static_assert(sizeof(RolloutWS<PlantActStage>) <= 65536 && sizeof(RolloutWS<PlantContactActStage>) <= 65536, "... and under the actuator model");
-static_assert(sizeof(RolloutWS<PlantVaried<PlantStage>>) <= 65536 && sizeof(RolloutWS<PlantVaried<PlantContactStage>>) <= 65536 &&
-              sizeof(RolloutWS<PlantVaried<PlantActStage>>) <= 65536 && sizeof(RolloutWS<PlantVaried<PlantContactActStage>>) <= 65536, "... and on a varied plant");
 // hsqp_inertia_eval (include/hsqp_inertia.h): one workgroup per instance — the plant's mass matrix, bias forces and total mass at a given state: stage
 // topology, one stage_eval<false>, the instance's variation, the assembly of the plant's bordered system
 __global__ __launch_bounds__(RO_THREADS) void k_inertia_eval(const DevModel* __restrict__ dm, InertiaParams ip, const double* __restrict__ x, double* __restrict__ M,
@@ -1364,9 +1349,7 @@ struct ContactStage { double* x; double* force; double* pen; size_t bytes; };
 static ContactStage contact_stage_layout(Carve c, size_t B, bool want_force, bool want_pen) {
   return {c.take<double>(B * NX), c.take<double>(B * CT_PTS * 3, want_force), c.take<double>(B * CT_PTS, want_pen), c.bytes()};
 }
-// d_plant, and the host array uploaded to it: kp | kd | armature, [NJ] each, which PlantParams::gains reads as one array (own packing, not Carve::take)
-struct PlantGains { double* kp; double* kd; double* armature; };
-static PlantGains plant_gains(double* g) { return {g, g + NJ, g + 2 * NJ}; }
+// d_plant: kp | kd | armature, [NJ] each, which PlantParams::gains reads as one array (own packing, not Carve::take: plant_pack_gains, hsqp_plant.h)
 // d_loop_log, hsqp_loop_run's host logs: x_log [n][B][58] | u_log [n][B][35], the cycles' rows as one array each (own packing, not Carve::take); a null block: the sizing pass
 struct LoopLog { double* x; double* u; size_t bytes; };
 static LoopLog loop_log_layout(double* block, size_t n, size_t B, bool want_x, bool want_u) {
@@ -2478,38 +2461,27 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     pt = PushTable{pb.n, pb.p, h->push_max, h->stamps_resident ? (const double*)h->d_stamps[h->stamps_cur] : nullptr, N + 1};
   }
   const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, sg.status, d_steps, d_rej, pt};
+  const RolloutVariant v(cent, torque, h->contact.enabled, h->actuator.enabled, h->inertia_B);
   ContactParams cp{nullptr, 0.0, 0.0, 0.0};
-  if (torque && h->contact.enabled) {
+  if (v.ground) {
     const int rc = contact_params(h, cp);
     if (rc != HSQP_OK) return rc;
   }
-  const PlantParams pp{torque ? plant_gains(h->d_plant).kp : nullptr, h->plant.lookahead, (const double*)h->d_xnew};
+  const PlantParams pp{torque ? (const double*)h->d_plant.p : nullptr, h->plant.lookahead, (const double*)h->d_xnew};
   ActuatorParams ap{nullptr, 0.0, 0.0, nullptr};
-  if (torque && h->actuator.enabled) {   // (hsqp_actuator_set made d_actuator)
+  if (v.actuated) {   // (hsqp_actuator_set made d_actuator)
     const ActuatorBuf ab = actuator_layout(Carve{h->d_actuator.p}, (size_t)h->st.max_batch);
     ap = ActuatorParams{ab.table, h->actuator.command_period, h->actuator.friction_velocity, ab.last};
     h->actuator_last_B = 0;              // (a failure below leaves no record)
   }
-  // (hsqp_inertia_set_instances* made d_inertia; the table acts on the torque plant only)
-  const InertiaParams ip{torque && h->inertia_B ? inertia_layout(Carve{h->d_inertia.p}, (size_t)h->st.max_batch).table : nullptr};
-  if (ip.table && ap.table && cp.ground)
-    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantContactActStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantContactActStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (ip.table && ap.table)
-    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantActStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantActStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (ip.table && cp.ground)
-    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantContactStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantContactStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (ip.table)
-    HSQP_LAUNCH(k_rollout_plant<PlantVaried<PlantStage>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantVaried<PlantStage>>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (ap.table && cp.ground)
-    HSQP_LAUNCH(k_rollout_plant<PlantContactActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactActStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (ap.table)
-    HSQP_LAUNCH(k_rollout_plant<PlantActStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantActStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (torque && cp.ground)
-    HSQP_LAUNCH(k_rollout_plant<PlantContactStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantContactStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (torque)
-    HSQP_LAUNCH(k_rollout_plant<PlantStage>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<PlantStage>), h->stream, h->d_dm, a, pp, cp, ap, ip);
-  else if (cent) HSQP_LAUNCH(k_rollout<CentWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<CentWST<false>>), h->stream, h->d_dm, a);
-  else HSQP_LAUNCH(k_rollout<StageWST<false>>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<StageWST<false>>), h->stream, h->d_dm, a);
+  // (hsqp_inertia_set_instances* made d_inertia)
+  const InertiaParams ip{v.varied ? inertia_layout(Carve{h->d_inertia.p}, (size_t)h->st.max_batch).table : nullptr};
+  rollout_dispatch(v, [&](auto stage) {
+    using SW = typename decltype(stage)::type;
+    static_assert(sizeof(RolloutWS<SW>) <= 65536, "the rollout runs without a dynamic-LDS attribute");
+    if constexpr (RolloutOnPlant<SW>::value) HSQP_LAUNCH(k_rollout_plant<SW>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<SW>), h->stream, h->d_dm, a, pp, cp, ap, ip);
+    else HSQP_LAUNCH(k_rollout<SW>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<SW>), h->stream, h->d_dm, a);
+  });
   step(hipGetLastError(), "k_rollout");
   std::vector<int32_t> hs(B);
   step(hipMemcpyAsync(hs.data(), sg.status, B * 4, hipMemcpyDeviceToHost, h->stream), "download status");
@@ -2624,8 +2596,7 @@ int hsqp_plant_set(hsqp_handle* h, const hsqp_plant_settings* s) {
     if (!ok(s->kp[j]) || !ok(s->kd[j]) || !ok(s->armature[j])) return bad(("joint " + std::to_string(j) + ": negative or non-finite kp, kd or armature").c_str());
   HCHECK(hipSetDevice(h->device));
   double g[3 * NJ];
-  const PlantGains hg = plant_gains(g);
-  for (int j = 0; j < NJ; ++j) { hg.kp[j] = s->kp[j]; hg.kd[j] = s->kd[j]; hg.armature[j] = s->armature[j]; }
+  plant_pack_gains(*s, g);
   DEV_ENSURE(h->d_plant, sizeof(g), "plant gains");
   HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the gains that are replaced)
   HCHECK(hipMemcpy(h->d_plant.p, g, sizeof(g), hipMemcpyHostToDevice));
@@ -2670,7 +2641,7 @@ int hsqp_actuator_set(hsqp_handle* h, const hsqp_actuator_settings* s) {
   HCHECK(hipSetDevice(h->device));
   const size_t mb = (size_t)h->st.max_batch;
   double t[3 * NJ];
-  for (int j = 0; j < NJ; ++j) { t[j] = s->effort_limit[j]; t[NJ + j] = s->damping[j]; t[2 * NJ + j] = s->friction[j]; }
+  actuator_pack_table(*s, t);
   DEV_ENSURE(h->d_actuator, actuator_layout(Carve{}, mb).bytes, "actuator table and record");
   HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the table that is replaced)
   HCHECK(hipMemcpy(actuator_layout(Carve{h->d_actuator.p}, mb).table, t, sizeof(t), hipMemcpyHostToDevice));
@@ -2724,7 +2695,8 @@ static int contact_params(hsqp_handle* h, ContactParams& cp) {
   if (!h->contact_current) {
     HCHECK(hipSetDevice(h->device));
     DEV_ENSURE(h->d_contact, contact_layout(Carve{}, mb).bytes, "contact ground");
-    const std::vector<hsqp_contact_ground> fill(mb - (size_t)h->contact_B, hsqp_contact_ground{h->contact.ground_height, h->contact.mu});
+    std::vector<hsqp_contact_ground> fill(mb - (size_t)h->contact_B);   // (the table's own entries are resident already)
+    contact_fill_ground(h->contact, nullptr, 0, fill.size(), fill.data());
     HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the entries that are replaced)
     if (!fill.empty())
       HCHECK(hipMemcpy(contact_layout(Carve{h->d_contact.p}, mb).ground + h->contact_B, fill.data(), fill.size() * sizeof(hsqp_contact_ground), hipMemcpyHostToDevice));

@@ -22,6 +22,10 @@ struct ContactParams {
   const hsqp_contact_ground* ground;   // [max_batch] the ground of every instance: the table's entry, or the setting's values
   double k, c, vs;                     // stiffness, damping, slip velocity
 };
+// (host) n entries as ContactParams::ground reads them: the per-instance table's first (n_table of them; table null: none), behind them the setting's values
+inline void contact_fill_ground(const hsqp_contact_settings& s, const hsqp_contact_ground* table, size_t n_table, size_t n, hsqp_contact_ground* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = table && i < n_table ? table[i] : hsqp_contact_ground{s.ground_height, s.mu};
+}
 
 // ONE instance's ground and the points of one flow evaluation
 struct ContactSet {

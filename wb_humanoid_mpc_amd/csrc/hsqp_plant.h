@@ -37,6 +37,10 @@ struct PlantParams {
   double lookahead;
   const double* xt;       // [B][N + 1][NX] nominal states of the resident policy (the state hsqp_evaluate_policy interpolates)
 };
+// (host) the public setting as PlantParams::gains reads it: g [3 NJ]
+inline void plant_pack_gains(const hsqp_plant_settings& s, double* g) {
+  for (int j = 0; j < NJ; ++j) { g[j] = s.kp[j]; g[NJ + j] = s.kd[j]; g[2 * NJ + j] = s.armature[j]; }
+}
 
 struct PlantWS {
   const double* xt;                 // nominal states of THIS instance

@@ -13,20 +13,17 @@
 //                ones behind the flow evaluation of the rollout (no other user of stage_eval<false> / cent_lane_flow sees them), their edges
 //                are break points beside the grid's events, and a segment's activity is fixed at its start.  An instance without pushes
 //                never enters that code.
-//   plant:       with the torque plant set (include/hsqp_plant.h, hsqp_plant.h) a second instantiation of the kernel — workspace
-//                RolloutWS<PlantStage> — replaces the flow evaluation by the compliant plant: full forward dynamics under the joint PD law,
-//                the pushes acting through the whole tree.  The instantiations above do not contain it.
-//   contact:     on that plant only, the ground of include/hsqp_contact.h (hsqp_contact.h): penalty forces at the eight sole corners in place of the
-//                policy's contact wrenches, inside every flow evaluation: a third instantiation, workspace RolloutWS<PlantContactStage>.  The
-//                plant without a ground keeps its own, which does not contain any of it.
-//   actuator:    on that plant only, the actuator model of include/hsqp_actuator.h (hsqp_actuator.h): the joint command sampled at ticks and held, effort
-//                limits and passive joint torques.  Two more instantiations (RolloutWS<PlantActStage>, RolloutWS<PlantContactActStage>): in them
-//                rollout_instance drives the ticks — break points beside the events and the push edges — and writes the record of the last torques.
-//                No other instantiation contains any of it.
-//   inertia:     on that plant only, the per-instance link scales and payloads of include/hsqp_inertia.h (hsqp_inertia.h): four more instantiations,
-//                RolloutWS<PlantVaried<...>> of the four plant workspaces, in which inertia_apply follows the stage_eval<false> at the plant's own
-//                state in every flow evaluation; the policy and tau_ff stay on the nominal model.  No other instantiation contains any of it.
-// The same source builds for the host with a one-lane context (tests/rollout/rollout_emu.cpp, tests/push/push_emu.cpp).
+//   plant:       with the torque plant set (include/hsqp_plant.h, hsqp_plant.h) the compliant plant replaces the flow evaluation: full forward dynamics
+//                under the joint PD law, the pushes acting through the whole tree.  Its options — the ground of include/hsqp_contact.h (penalty forces
+//                at the eight sole corners in place of the policy's contact wrenches), the actuator model of include/hsqp_actuator.h (the joint command
+//                sampled at ticks and held, effort limits, passive joint torques: rollout_instance drives the ticks and writes the record of the
+//                last torques) and the per-instance link scales and payloads of include/hsqp_inertia.h (inertia_apply behind the stage_eval<false>
+//                at the plant's own state; the policy and tau_ff stay on the nominal model) — are parameters of the instantiation, not run-time
+//                branches: an option that is off is not in the code that runs.
+// ONE entry and ONE rule hold the instantiations together:
+//   rollout_entry     what one workgroup does for one instance of a call: the entry of the host emulation (tests/rollout/rollout_emu.h, one-lane
+//                     context).  k_rollout / k_rollout_plant (hsqp_capi.hip) spell the same statements out: called through it they measured slower
+//   rollout_dispatch  (host) the stage workspace a configuration gets: the one list of the ten types
 #pragma once
 #include "hsqp_policy.h"
 #include "hsqp_cent_lq.h"
@@ -509,6 +506,61 @@ HSQP_HD void rollout_instance(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>&
     *status = stat;
     if (steps) *steps = nacc;
     if (rejected) *rejected = nrej;
+  }
+}
+
+// The arguments of one rollout call over the batch, as the kernels take them
+struct RolloutArgs {
+  const double* ut; const double* dts; int N; double dt;   // resident inputs and grid (dts null: uniform)
+  const double* K; const double* uff; int first, count;     // gain window [B][count] (feedback controller)
+  hsqp_rollout_settings st;
+  const double* s0; const double* x0; double duration; int n;
+  double* x; double* u; int32_t* status; int32_t* steps; int32_t* rejected;
+  PushTable push;                                           // the resident push table (include/hsqp_push.h; n null: none)
+};
+
+// whether the stage workspace is one of the torque plant's (ws.pl) and not a flow map's
+template <class SW> struct RolloutOnPlant { static constexpr bool value = true; };
+template <> struct RolloutOnPlant<StageWST<false>> { static constexpr bool value = false; };
+template <> struct RolloutOnPlant<CentWST<false>> { static constexpr bool value = false; };
+
+// Instance b of the call: its policy, the parts of the plant's setting that SW carries (a flow workspace: none, pp .. ip are not read), the integration
+template <class SW>
+HSQP_HD void rollout_entry(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutArgs& a, const PlantParams& pp, const ContactParams& cp,
+                           const ActuatorParams& ap, const InertiaParams& ip, int b) {
+  const RolloutPolicy p{a.ut + (size_t)b * a.N * NU, a.dts ? a.dts + (size_t)b * a.N : nullptr, a.N, a.dt, a.K ? a.K + (size_t)b * a.count * NU * NX : nullptr,
+                        a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count,
+                        !RolloutOnPlant<SW>::value && dm.formulation == HSQP_FORM_CENTROIDAL ? 1 : 0};
+  if constexpr (RolloutOnPlant<SW>::value) plant_load(ctx, pp, b, a.N, w.sw.pl);
+  if constexpr (PlantGrounded<SW>::value) contact_load(ctx, cp, b, w.sw.ct);
+  if constexpr (RolloutActuated<SW>::value) actuator_load(ctx, ap, b, w.sw.act);
+  if constexpr (PlantIsVaried<SW>::value) inertia_load(ctx, ip, b, w.sw.iw);
+  rollout_instance(ctx, dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
+                   a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr, a.rejected ? a.rejected + b : nullptr, a.push, b);
+}
+
+// ---- host side: which instantiation a configuration gets.  The options count on the torque plant only: the ground and the actuator model while
+// their setting is enabled, the variation while a table is resident.
+struct RolloutVariant {
+  bool cent, torque, ground, actuated, varied;
+  RolloutVariant(bool centroidal, bool torque_plant, bool contact_enabled, bool actuator_enabled, bool inertia_table)
+      : cent(centroidal), torque(torque_plant), ground(torque_plant && contact_enabled), actuated(torque_plant && actuator_enabled),
+        varied(torque_plant && inertia_table) {}
+};
+template <class SW> struct RolloutStageType { using type = SW; };
+// f(RolloutStageType<SW>{}) for the stage workspace SW of the configuration.  The ten instantiations are listed here and nowhere else.
+template <class F>
+auto rollout_dispatch(const RolloutVariant& v, F&& f) {
+  if (!v.torque) return v.cent ? f(RolloutStageType<CentWST<false>>{}) : f(RolloutStageType<StageWST<false>>{});
+  switch ((v.varied ? 4 : 0) | (v.actuated ? 2 : 0) | (v.ground ? 1 : 0)) {
+    case 0: return f(RolloutStageType<PlantStage>{});
+    case 1: return f(RolloutStageType<PlantContactStage>{});
+    case 2: return f(RolloutStageType<PlantActStage>{});
+    case 3: return f(RolloutStageType<PlantContactActStage>{});
+    case 4: return f(RolloutStageType<PlantVaried<PlantStage>>{});
+    case 5: return f(RolloutStageType<PlantVaried<PlantContactStage>>{});
+    case 6: return f(RolloutStageType<PlantVaried<PlantActStage>>{});
+    default: return f(RolloutStageType<PlantVaried<PlantContactActStage>>{});
   }
 }
 
