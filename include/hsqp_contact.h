@@ -15,7 +15,8 @@
  *             base and the foot.
  *   policy    with contact on, the prescribed term sum_feet J^T W of step 4 is DROPPED on the plant: the ground reaction is the model's, not
  *             the MPC's plan.  The feed-forward effort tau_ff of step 2 is still formed from (x_p, u_p) with the policy's wrenches, unchanged.
- * The ground is a horizontal plane.  All of it is plain double arithmetic.
+ * The ground is a horizontal plane (hsqp_terrain.h puts a per-instance height map under it: the height and the normal then come from the map under
+ * each point, everything else of this header holds).  All of it is plain double arithmetic.
  *
  * ASSUMPTIONS (stated here the way hsqp_rollout.h states those of its integrators):
  *   C1. This is a penalty model, NOT the soft-constraint contact solver of the MuJoCo front end of the reference, which cannot be restated

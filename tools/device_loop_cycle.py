@@ -12,6 +12,7 @@ iteration and the rollout, and its rollout keeps no step counters).
                                       [--contact] [--stiffness 5e4] [--damping 10] [--mu MODEL] [--slip-velocity 0.01]
                                       [--actuator] [--command-period 0.002] [--effort-limits FILE] [--joint-damping 0] [--joint-friction 0]
                                       [--inertia] [--mass-spread 0.15] [--payload KG]
+                                      [--terrain ramp|ledge|rubble] [--terrain-seed 2026]
                                       [--observe] [--obs-noise 0.005] [--obs-bias 0.02] [--sensor-delay 1] [--compute-delay 1] [--obs-seed 2026]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
                                       [--plant torque [--contact ...] [--actuator ...] [--inertia ...]]
@@ -38,6 +39,12 @@ run with |tau_cmd| above the limit at any joint (hsqp_actuator_last; instances w
 rotational inertia scaled by 1 + spread (2 b / (B - 1) - 1), spread = --mass-spread (0: no scaling), and with --payload KG carries a point mass of
 KG kilograms at the origin of the torso link.  The MPC keeps the nominal model: this is the model mismatch.  The timing mode and the --push sweep
 both honour it; either prints, per instance, the plant's total mass (plant_dynamics) and whether the instance finished the run.
+--terrain: uneven ground under the torque plant (include/hsqp_terrain.h; requires --plant torque --contact): sixteen height maps of growing difficulty,
+built here, instance b on map b mod 16 — ramp: a slope of 0 .. 7.5 degrees (0.5 degree steps) that begins 0.3 m ahead of the start; ledge: a step up of
+0 .. 6 cm (4 mm steps) over one 1 cm cell, 0.3 m ahead; rubble: a 64 x 64 grid of 4 cm cells around the start with heights drawn from --terrain-seed,
+amplitude 0 .. 3 cm (2 mm steps), the cells under the soles at the start levelled.  The MPC plans on flat ground: this is the mismatch.  Isolation is on (park; box: base
+height above 0.45 m, tilt below 0.7 rad, as in --push) unless --isolate says otherwise, and the run prints, per instance, the cycles it survived and its
+final base position; the line carries the count of survivors per map.  It reports; it asserts nothing.
 --observe: the observation model of the loop (include/hsqp_observe.h): the MPC measures the plant with white noise of standard deviation --obs-noise
 on every state entry (rad, m, rad/s, m/s), a bias of --obs-bias metres on the base height, --sensor-delay periods it does not know about and
 --compute-delay periods it does.  The timed run has the model on; the same run is then repeated with the model off, and the line carries, side by
@@ -168,6 +175,41 @@ def inertia_args(args, B):
     return scale, payloads
 
 
+TERRAIN_MAPS = 16
+
+
+def terrain_args(args, x_init):
+    """(maps, placements, labels) of --terrain: sixteen maps of growing difficulty (label: what grows), instance b on map b mod 16, placed relative to its start."""
+    rng = np.random.default_rng(args.terrain_seed)
+    maps, labels = [], []
+    for k in range(TERRAIN_MAPS):
+        if args.terrain == "ramp":
+            deg = 0.5 * k
+            rise = np.tan(np.radians(deg)) * 8.0
+            maps.append((np.array([[0.0, rise], [0.0, rise]]), 8.0))
+            labels.append(f"{deg:.1f} deg")
+        elif args.terrain == "ledge":
+            h = 0.004 * k
+            maps.append((np.array([[0.0, 0.0, 0.0, h, h]] * 4), 0.01))
+            labels.append(f"{100 * h:.1f} cm")
+        else:
+            amp = 0.002 * k
+            H = amp * rng.uniform(-1.0, 1.0, (64, 64))
+            H[27:37, 28:36] = 0.0                          # (level under the start, +-0.14 m ahead and +-0.18 m aside: the feet begin on the plane)
+            maps.append((H, 0.04))
+            labels.append(f"{100 * amp:.1f} cm")
+    place = []
+    for b, x in enumerate(x_init):
+        k = b % TERRAIN_MAPS
+        c, sn = np.cos(x[3]), np.sin(x[3])
+        if args.terrain == "rubble":
+            off = (-31.5 * 0.04, -31.5 * 0.04)             # the map's centre under the base
+        else:
+            off = (0.3 - (0.02 if args.terrain == "ledge" else 0.0), -0.015 if args.terrain == "ledge" else -4.0)
+        place.append(dict(map=k, origin=(x[0] + c * off[0] - sn * off[1], x[1] + sn * off[0] + c * off[1]), yaw=float(x[3])))
+    return maps, place, labels
+
+
 def saturated_share(s, m, args):
     """The share of the instances whose last record has |tau_cmd| above the limit at any joint."""
     limits = actuator_args(args, m)["effort_limit"]
@@ -228,6 +270,8 @@ def main():
     ap.add_argument("--inertia", action="store_true")
     ap.add_argument("--mass-spread", type=float, default=0.15)
     ap.add_argument("--payload", type=float, default=None, metavar="KG")
+    ap.add_argument("--terrain", default=None, choices=("ramp", "ledge", "rubble"))
+    ap.add_argument("--terrain-seed", type=int, default=2026)
     ap.add_argument("--observe", action="store_true")
     ap.add_argument("--obs-noise", type=float, default=5e-3)
     ap.add_argument("--obs-bias", type=float, default=0.02)
@@ -247,6 +291,8 @@ def main():
         ap.error("--mass-spread and --payload belong to --inertia (without it nothing is varied)")
     if args.inertia and args.plant != "torque":
         ap.error("--inertia requires --plant torque (the inertial variations act on the torque plant only)")
+    if args.terrain and not (args.plant == "torque" and args.contact):
+        ap.error("--terrain requires --plant torque --contact (the terrain lies under the ground of the torque plant)")
     if not args.observe and given & {"--obs-noise", "--obs-bias", "--sensor-delay", "--compute-delay", "--obs-seed"}:
         ap.error("--obs-noise, --obs-bias, --sensor-delay, --compute-delay and --obs-seed belong to --observe (without it the MPC measures the plant exactly)")
     if args.push:
@@ -309,6 +355,8 @@ def timed_run(args, observe):
             s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
         if args.isolate:
             s.loop_isolate(s.episode_settings(args.isolate))
+        elif args.terrain:
+            s.loop_isolate(s.episode_settings("park", min_base_height=0.45, max_tilt=0.7))
         if args.with_push is not None:
             s.set_pushes([[dict(body=0, t_start=0.0, duration=1e6, point=(0.0, 0.0, 0.0), force=(0.0, args.with_push, 0.0))]] * B)
         if args.plant:
@@ -317,6 +365,12 @@ def timed_run(args, observe):
             s.set_contact(**contact_args(args))
         if args.actuator:
             s.set_actuator(**actuator_args(args, m))
+        labels = None
+        if args.terrain:
+            maps, place, labels = terrain_args(args, x_init)
+            s.set_terrain_maps(maps)
+            s.set_terrain_instances(place)
+        last_pos = x_init[:, :3].copy()
         masses = None
         if args.inertia:
             s.set_inertia_instances(*inertia_args(args, B))
@@ -329,6 +383,8 @@ def timed_run(args, observe):
             r = s.loop_run(1)
             t_b = time.perf_counter()
             heights.append(r["x"][0, :, 2].copy())
+            live = np.isfinite(r["x"][0]).all(axis=1)
+            last_pos[live] = r["x"][0][live, :3]
             if c >= args.warmup:
                 cycle_ms.append(1e3 * (t_b - t_a))
                 track.append(np.nanmean(tracking_error(m, r["x"][0], cmd)))
@@ -337,13 +393,26 @@ def timed_run(args, observe):
         run_ms = 1e3 * (time.perf_counter() - t_a) / args.cycles
         t_end, x_end, v_filt = s.loop_state()
         rungs = np.bincount(s.gait_state()["rung"], minlength=7).tolist() if args.gait else None
-        ep = s.loop_episodes() if args.isolate else None
+        ep = s.loop_episodes() if args.isolate or args.terrain else None
         heights.append(x_end[:, 2].copy())
         saturated = saturated_share(s, m, args) if args.actuator else None
         probe = rollout_probe(s, args, x_end) if args.plant else None
     finally:
         s.close()
     heights = np.concatenate(heights)
+    terrain = None
+    if args.terrain:
+        total = args.warmup + 2 * args.cycles
+        live = np.isfinite(x_end).all(axis=1)
+        last_pos[live] = x_end[live, :3]
+        survived = np.where(ep["n_failures"] > 0, ep["fail_cycle"], total).astype(int)
+        print(f"terrain {args.terrain}: {B} instances, {total} cycles of {args.period:.4f} s; final base position: the last one logged (the second half of the run keeps no log)")
+        print(f"{'instance':>8} {'map':>4} {'difficulty':>10} {'survived':>9} {'base x':>9} {'base y':>9} {'base z':>9}")
+        for b in range(B):
+            print(f"{b:8d} {b % TERRAIN_MAPS:4d} {labels[b % TERRAIN_MAPS]:>10} {survived[b]:9d} {last_pos[b, 0]:9.4f} {last_pos[b, 1]:9.4f} {last_pos[b, 2]:9.4f}")
+        per_map = [[int((survived[k::TERRAIN_MAPS] == total).sum()), int(len(survived[k::TERRAIN_MAPS]))] for k in range(min(TERRAIN_MAPS, B))]
+        terrain = dict(kind=args.terrain, seed=args.terrain_seed, difficulty=labels[:len(per_map)], survivors_per_map=per_map, survivors=int((survived == total).sum()),
+                       cycles_survived_mean=round(float(survived.mean()), 2))
     q = np.percentile(cycle_ms, [25, 75])
     finished = np.isfinite(x_end).all(axis=1) & ((ep["state"] == 0) if ep else True)
     if args.inertia:
@@ -355,7 +424,7 @@ def timed_run(args, observe):
                       "contact": contact_args(args) if args.contact else None,
                       "actuator": dict(actuator_args(args, m), effort_limits=args.effort_limits, saturated_share=saturated) if args.actuator else None,
                       "inertia": dict(mass_spread=args.mass_spread, payload=args.payload, total_mass_range=[round(float(masses.min()), 3), round(float(masses.max()), 3)],
-                                      finished=int(finished.sum())) if args.inertia else None, "rollout_probe": probe,
+                                      finished=int(finished.sum())) if args.inertia else None, "terrain": terrain, "rollout_probe": probe,
                       "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
                       "cycle_ms_median": round(float(np.median(cycle_ms)), 3), "cycle_ms_mean": round(float(np.mean(cycle_ms)), 3),
                       "cycle_ms_quartiles": [round(float(q[0]), 3), round(float(q[1]), 3)], "cycle_ms_min": round(float(np.min(cycle_ms)), 3),

@@ -229,6 +229,19 @@ INERTIA_ENTRY_POINTS = ("hsqp_inertia_defaults", "hsqp_inertia_set_instances", "
                         "hsqp_inertia_get_instances", "hsqp_inertia_eval", "hsqp_inertia_eval_device")
 
 
+# include/hsqp_terrain.h
+TERRAIN_MAX_MAPS, TERRAIN_MAX_DIM = 16, 256
+
+
+class TerrainPlacement(C.Structure):   # hsqp_terrain_placement
+    _fields_ = [("map", C.c_int32), ("reserved", C.c_int32), ("origin_x", C.c_double), ("origin_y", C.c_double), ("yaw", C.c_double)]
+
+
+# entry points of include/hsqp_terrain.h (tests/test_terrain.py checks that the library exports each of them and the binding declares it)
+TERRAIN_ENTRY_POINTS = ("hsqp_terrain_set_maps", "hsqp_terrain_set_instances", "hsqp_terrain_set_instances_device", "hsqp_terrain_clear",
+                        "hsqp_terrain_get_maps", "hsqp_terrain_get_instances", "hsqp_terrain_eval", "hsqp_terrain_eval_device")
+
+
 # include/hsqp_observe.h
 OBS_MAX_DELAY = 8
 

@@ -989,7 +989,7 @@ __global__ __launch_bounds__(RO_WIN_THREADS) void k_rollout_window(const double*
 // calling it: through one more inlined call the compiler schedules the plant kernels differently (same registers, LDS and scratch, other SGPR spills) and the
 // loop on the torque plant with every option measured 2.7 .. 3.1 % slower than with these bodies (profiles/rollout_entry_ab.txt).  Keep the two in step.
 // k_rollout: the flow maps.  k_rollout_plant: the torque plant (include/hsqp_plant.h), one instantiation per set of its options — the ground (cp), the actuator
-// model (ap), the inertial variation (ip): a block is read only by the instantiations whose SW carries its part.  An option is a parameter of the instantiation
+// model (ap), the inertial variation (ip), the height-map terrain under the ground (tp): a block is read only by the instantiations whose SW carries its part.  An option is a parameter of the instantiation
 // because as a run-time branch the contact alone costs the rollout without a ground 3.6 % (measured); whether the command is held (ap.period > 0)
 // is a run-time, workgroup-uniform branch.  rollout_impl picks SW through rollout_dispatch.
 template <class SW>
@@ -1004,7 +1004,7 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout(const DevModel* __restri
 }
 template <class SW>
 __global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __restrict__ dm, RolloutArgs a, PlantParams pp, ContactParams cp, ActuatorParams ap,
-                                                              InertiaParams ip) {
+                                                              InertiaParams ip, TerrainParams tp) {
   RolloutWS<SW>& w = *reinterpret_cast<RolloutWS<SW>*>(hsqp_smem);
   const int b = blockIdx.x;
   const Ctx ctx{(int)threadIdx.x, RO_THREADS, nullptr};
@@ -1012,6 +1012,7 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout_plant(const DevModel* __
                         a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count, 0};
   plant_load(ctx, pp, b, a.N, w.sw.pl);
   if constexpr (PlantGrounded<SW>::value) contact_load(ctx, cp, b, w.sw.ct);
+  if constexpr (PlantOnTerrain<SW>::value) terrain_load(ctx, tp, b, w.sw.ct.ter);
   if constexpr (RolloutActuated<SW>::value) actuator_load(ctx, ap, b, w.sw.act);
   if constexpr (PlantIsVaried<SW>::value) inertia_load(ctx, ip, b, w.sw.iw);
   rollout_instance(ctx, *dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
@@ -1028,15 +1029,24 @@ __global__ __launch_bounds__(RO_THREADS) void k_inertia_eval(const DevModel* __r
 }
 static_assert(sizeof(InertiaEvalWS) <= 65536, "hsqp_inertia_eval runs without a dynamic-LDS attribute");
 // hsqp_contact_eval (include/hsqp_contact.h): one workgroup per instance — the contact model at a given state: stage topology, one stage_eval<false>
-// for the placements and the link velocities, the eight points
-__global__ __launch_bounds__(RO_THREADS) void k_contact_eval(const DevModel* __restrict__ dm, ContactParams cp, const double* __restrict__ x, double* __restrict__ force,
-                                                             double* __restrict__ pen) {
-  ContactEvalWS& w = *reinterpret_cast<ContactEvalWS*>(hsqp_smem);
+// for the placements and the link velocities, the eight points.  CT: ContactSet, or ContactTerrainSet while a terrain is resident (tp is read by that one only)
+template <class CT>
+__global__ __launch_bounds__(RO_THREADS) void k_contact_eval(const DevModel* __restrict__ dm, ContactParams cp, TerrainParams tp, const double* __restrict__ x,
+                                                             double* __restrict__ force, double* __restrict__ pen) {
+  ContactEvalWST<CT>& w = *reinterpret_cast<ContactEvalWST<CT>*>(hsqp_smem);
   const int b = blockIdx.x;
-  contact_eval_instance(Ctx{(int)threadIdx.x, RO_THREADS, nullptr}, *dm, w, cp, b, x + (size_t)b * NX, force ? force + (size_t)b * CT_PTS * 3 : nullptr,
+  contact_eval_instance(Ctx{(int)threadIdx.x, RO_THREADS, nullptr}, *dm, w, cp, &tp, b, x + (size_t)b * NX, force ? force + (size_t)b * CT_PTS * 3 : nullptr,
                         pen ? pen + (size_t)b * CT_PTS : nullptr);
 }
-static_assert(sizeof(ContactEvalWS) <= 65536, "hsqp_contact_eval runs without a dynamic-LDS attribute");
+static_assert(sizeof(ContactEvalWST<ContactTerrainSet>) <= 65536, "hsqp_contact_eval runs without a dynamic-LDS attribute");
+// hsqp_terrain_eval (include/hsqp_terrain.h): one workgroup per instance — the ground's height and normal under n_pts world points
+__global__ __launch_bounds__(RO_THREADS) void k_terrain_eval(ContactParams cp, TerrainParams tp, int n_pts, const double* __restrict__ xy, double* __restrict__ height,
+                                                             double* __restrict__ normal) {
+  __shared__ TerrainSet ts;
+  const size_t b = blockIdx.x, n = (size_t)n_pts;
+  terrain_eval_instance(Ctx{(int)threadIdx.x, RO_THREADS, nullptr}, cp, tp, ts, (int)b, n_pts, xy + b * n * 2, height ? height + b * n : nullptr,
+                        normal ? normal + b * n * 3 : nullptr);
+}
 
 // ---- per-instance performance index from per-node {ne, dt*cost, dt*eq^2, dt*dyn^2} + terminal cost
 __device__ inline void perf_reduce_instance(int b, const DevModel* __restrict__ dm, const double* __restrict__ misc, int misc_stride, const double* __restrict__ x,
@@ -1185,6 +1195,14 @@ struct hsqp_handle {
   // first inertia_B the table's, the rest neutral; inertia_B = 0: no table.  d_inertia_stage: staging of hsqp_inertia_eval's host arrays (inertia_stage_layout)
   DevBuf<char> d_inertia, d_inertia_stage;
   int inertia_B = 0;
+  // the resident terrain under that ground (include/hsqp_terrain.h).  terrain_maps: the descriptors of the resident maps (empty: none), which d_terrain_maps
+  // (terrain_maps_layout) holds with the heights.  d_terrain_place (terrain_place_layout): the placement of every instance [max_batch] — the first terrain_B the
+  // table's, the rest map = -1; terrain_B = 0: no table; terrain_place_current: it holds that; terrain_top: the largest map index of a table that came as a host
+  // array (-1: none, or a device array).  d_terrain_stage: staging of hsqp_terrain_eval's host arrays (terrain_stage_layout)
+  std::vector<TerrainMap> terrain_maps;
+  DevBuf<char> d_terrain_maps, d_terrain_place, d_terrain_stage;
+  int terrain_B = 0, terrain_top = -1;
+  bool terrain_place_current = false;
   // the resident observation model of the loop (include/hsqp_observe.h).  observe_set: hsqp_observe_set made settings; d_observe_table (observe_table_layout):
   // the entry of every instance [max_batch] — the first observe_B the table's, the rest neutral; observe_B = 0: no table.  d_observe (observe_layout): the
   // loop's ring and its two observation rows; d_observe_stage: staging of hsqp_observe_eval's host arrays (observe_stage_layout)
@@ -1339,6 +1357,17 @@ static ActuatorBuf actuator_layout(Carve c, size_t max_batch) { return {c.take<d
 // d_inertia: the inertial variation of every instance [max_batch]
 struct InertiaBuf { hsqp_inertia_instance* table; size_t bytes; };
 static InertiaBuf inertia_layout(Carve c, size_t max_batch) { return {c.take<hsqp_inertia_instance>(max_batch), c.bytes()}; }
+// d_terrain_maps: the descriptors [HSQP_TERRAIN_MAX_MAPS] | the heights of all maps, concatenated
+struct TerrainMapsBuf { TerrainMap* maps; double* pool; size_t bytes; };
+static TerrainMapsBuf terrain_maps_layout(Carve c, size_t heights) { return {c.take<TerrainMap>(HSQP_TERRAIN_MAX_MAPS), c.take<double>(heights), c.bytes()}; }
+// d_terrain_place: the placement of every instance [max_batch]
+struct TerrainPlaceBuf { hsqp_terrain_placement* place; size_t bytes; };
+static TerrainPlaceBuf terrain_place_layout(Carve c, size_t max_batch) { return {c.take<hsqp_terrain_placement>(max_batch), c.bytes()}; }
+// d_terrain_stage, hsqp_terrain_eval (host arrays): xy [B][n][2] | height [B][n] | normal [B][n][3]
+struct TerrainStage { double* xy; double* height; double* normal; size_t bytes; };
+static TerrainStage terrain_stage_layout(Carve c, size_t pts, bool want_height, bool want_normal) {
+  return {c.take<double>(pts * 2), c.take<double>(pts, want_height), c.take<double>(pts * 3, want_normal), c.bytes()};
+}
 // d_inertia_stage, hsqp_inertia_eval (host arrays): x [B][58] | M [B][29][29] | nle [B][29] | mass [B]
 struct InertiaStage { double* x; double* M; double* nle; double* mass; size_t bytes; };
 static InertiaStage inertia_stage_layout(Carve c, size_t B, bool want_M, bool want_nle, bool want_mass) {
@@ -2399,6 +2428,7 @@ static const char* rollout_settings_error(const hsqp_rollout_settings& st) {
 }
 
 static int contact_params(hsqp_handle* h, ContactParams& cp);   // (below, with the entry points of include/hsqp_contact.h)
+static int terrain_params(hsqp_handle* h, TerrainParams& tp);   // (below, with the entry points of include/hsqp_terrain.h)
 
 // dev: every array argument is device memory of the handle's GPU
 // per_instance (the isolated loop, include/hsqp_episode.h): an instance's status word — of the iteration, of the integration — is the instance's
@@ -2461,10 +2491,15 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
     pt = PushTable{pb.n, pb.p, h->push_max, h->stamps_resident ? (const double*)h->d_stamps[h->stamps_cur] : nullptr, N + 1};
   }
   const RolloutArgs a{h->d_unew, dts, N, h->dt, dK, duff, first, count, *st, d_s0, d_x0, duration, n, d_x, d_u, sg.status, d_steps, d_rej, pt};
-  const RolloutVariant v(cent, torque, h->contact.enabled, h->actuator.enabled, h->inertia_B);
+  const RolloutVariant v(cent, torque, h->contact.enabled, h->actuator.enabled, h->inertia_B, !h->terrain_maps.empty(), h->terrain_B);
   ContactParams cp{nullptr, 0.0, 0.0, 0.0};
   if (v.ground) {
     const int rc = contact_params(h, cp);
+    if (rc != HSQP_OK) return rc;
+  }
+  TerrainParams tp{nullptr, nullptr, nullptr, 0};
+  if (v.terrain) {
+    const int rc = terrain_params(h, tp);
     if (rc != HSQP_OK) return rc;
   }
   const PlantParams pp{torque ? (const double*)h->d_plant.p : nullptr, h->plant.lookahead, (const double*)h->d_xnew};
@@ -2479,7 +2514,7 @@ static int rollout_impl(hsqp_handle* h, const hsqp_rollout_settings* st, const d
   rollout_dispatch(v, [&](auto stage) {
     using SW = typename decltype(stage)::type;
     static_assert(sizeof(RolloutWS<SW>) <= 65536, "the rollout runs without a dynamic-LDS attribute");
-    if constexpr (RolloutOnPlant<SW>::value) HSQP_LAUNCH(k_rollout_plant<SW>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<SW>), h->stream, h->d_dm, a, pp, cp, ap, ip);
+    if constexpr (RolloutOnPlant<SW>::value) HSQP_LAUNCH(k_rollout_plant<SW>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<SW>), h->stream, h->d_dm, a, pp, cp, ap, ip, tp);
     else HSQP_LAUNCH(k_rollout<SW>, dim3(B), dim3(RO_THREADS), sizeof(RolloutWS<SW>), h->stream, h->d_dm, a);
   });
   step(hipGetLastError(), "k_rollout");
@@ -2789,7 +2824,13 @@ static int contact_eval_impl(hsqp_handle* h, int batch, const double* x, double*
     d_x = sg.x; d_f = sg.force; d_p = sg.pen;
     step(hipMemcpyAsync(sg.x, x, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
   }
-  HSQP_LAUNCH(k_contact_eval, dim3(batch), dim3(RO_THREADS), sizeof(ContactEvalWS), h->stream, h->d_dm, cp, d_x, d_f, d_p);
+  TerrainParams tp{nullptr, nullptr, nullptr, 0};
+  if (!h->terrain_maps.empty() && h->terrain_B) {   // (a terrain is resident: the model of include/hsqp_terrain.h)
+    if (const int rc = terrain_params(h, tp)) return rc;
+    HSQP_LAUNCH(k_contact_eval<ContactTerrainSet>, dim3(batch), dim3(RO_THREADS), sizeof(ContactEvalWST<ContactTerrainSet>), h->stream, h->d_dm, cp, tp, d_x, d_f, d_p);
+  } else {
+    HSQP_LAUNCH(k_contact_eval<ContactSet>, dim3(batch), dim3(RO_THREADS), sizeof(ContactEvalWS), h->stream, h->d_dm, cp, tp, d_x, d_f, d_p);
+  }
   step(hipGetLastError(), "k_contact_eval");
   if (!dev) {
     if (force) step(hipMemcpyAsync(force, d_f, B * CT_PTS * 3 * 8, hipMemcpyDeviceToHost, h->stream), "download force");
@@ -2801,6 +2842,190 @@ static int contact_eval_impl(hsqp_handle* h, int batch, const double* x, double*
 int hsqp_contact_eval(hsqp_handle* h, int batch, const double* x, double* force, double* penetration) { return contact_eval_impl(h, batch, x, force, penetration, false); }
 int hsqp_contact_eval_device(hsqp_handle* h, int batch, const double* d_x, double* d_force, double* d_penetration) {
   return contact_eval_impl(h, batch, d_x, d_force, d_penetration, true);
+}
+
+// ---- height-map terrain under the ground of the torque plant (include/hsqp_terrain.h, csrc/hsqp_terrain.h): the resident maps, the placements, the evaluation
+static int terrain_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) { h->err = std::string(who) + ": whole-body handles only (the terrain lies under the torque plant of the whole-body tree)"; return HSQP_ERR_BAD_ARG; }
+  return HSQP_OK;
+}
+// makes d_terrain_place hold the placement of every instance (entries from terrain_B on: map = -1) and gives the kernels' view of the terrain (no maps:
+// n_maps = 0, every instance on the plane)
+static int terrain_params(hsqp_handle* h, TerrainParams& tp) {
+  const size_t mb = (size_t)h->st.max_batch;
+  if (!h->terrain_place_current || !h->d_terrain_place.p) {
+    HCHECK(hipSetDevice(h->device));
+    DEV_ENSURE(h->d_terrain_place, terrain_place_layout(Carve{}, mb).bytes, "terrain placements");
+    std::vector<hsqp_terrain_placement> fill(mb - (size_t)h->terrain_B);   // (the table's own entries are resident already)
+    terrain_fill_place(nullptr, 0, fill.size(), fill.data());
+    HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the entries that are replaced)
+    if (!fill.empty())
+      HCHECK(hipMemcpy(terrain_place_layout(Carve{h->d_terrain_place.p}, mb).place + h->terrain_B, fill.data(), fill.size() * sizeof(hsqp_terrain_placement), hipMemcpyHostToDevice));
+    h->terrain_place_current = true;
+  }
+  size_t heights = 0;
+  for (const TerrainMap& m : h->terrain_maps) heights += (size_t)m.nx * m.ny;
+  const TerrainMapsBuf mbuf = terrain_maps_layout(Carve{h->d_terrain_maps.p}, heights);
+  const bool have = !h->terrain_maps.empty();
+  tp = TerrainParams{have ? mbuf.maps : nullptr, have ? mbuf.pool : nullptr, terrain_place_layout(Carve{h->d_terrain_place.p}, mb).place, (int)h->terrain_maps.size()};
+  return HSQP_OK;
+}
+int hsqp_terrain_set_maps(hsqp_handle* h, int n_maps, const int32_t* nx, const int32_t* ny, const double* cell, const double* heights) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_terrain_set_maps";
+  const auto bad = [&](const std::string& what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = terrain_handle_ok(h, who)) return rc;
+  if (n_maps < 0 || n_maps > HSQP_TERRAIN_MAX_MAPS) return bad("n_maps outside [0, " + std::to_string(HSQP_TERRAIN_MAX_MAPS) + "]");
+  if (n_maps && (!nx || !ny || !cell || !heights)) return bad("null nx, ny, cell or heights");
+  if (h->terrain_B && n_maps <= h->terrain_top)
+    return bad("the resident placement table refers to map " + std::to_string(h->terrain_top) + ", " + std::to_string(n_maps) + " maps given (hsqp_terrain_set_instances / hsqp_terrain_clear)");
+  std::vector<TerrainMap> maps;
+  size_t total = 0;
+  for (int m = 0; m < n_maps; ++m) {
+    const std::string at = "map " + std::to_string(m) + ": ";
+    if (nx[m] < 2 || nx[m] > HSQP_TERRAIN_MAX_DIM || ny[m] < 2 || ny[m] > HSQP_TERRAIN_MAX_DIM) return bad(at + "nx or ny outside [2, " + std::to_string(HSQP_TERRAIN_MAX_DIM) + "]");
+    if (!std::isfinite(cell[m]) || !(cell[m] > 0.0)) return bad(at + "cell not finite or <= 0");
+    maps.push_back(TerrainMap{nx[m], ny[m], cell[m], total});
+    const size_t cnt = (size_t)nx[m] * ny[m];
+    for (size_t i = 0; i < cnt; ++i)
+      if (!std::isfinite(heights[total + i])) return bad(at + "non-finite height");
+    total += cnt;
+  }
+  HCHECK(hipSetDevice(h->device));
+  HCHECK(hipStreamSynchronize(h->stream));   // (no rollout in flight reads the maps that are replaced)
+  h->terrain_maps.clear();                   // (a failure below leaves no maps)
+  if (!n_maps) {
+    if (h->d_terrain_maps.p) { (void)hipFree(h->d_terrain_maps.p); h->d_terrain_maps.p = nullptr; h->d_terrain_maps.bytes = 0; }
+    return HSQP_OK;
+  }
+  DEV_ENSURE(h->d_terrain_maps, terrain_maps_layout(Carve{}, total).bytes, "terrain maps");
+  const TerrainMapsBuf mbuf = terrain_maps_layout(Carve{h->d_terrain_maps.p}, total);
+  HCHECK(hipMemcpy(mbuf.maps, maps.data(), maps.size() * sizeof(TerrainMap), hipMemcpyHostToDevice));
+  HCHECK(hipMemcpy(mbuf.pool, heights, total * sizeof(double), hipMemcpyHostToDevice));
+  h->terrain_maps = std::move(maps);
+  return HSQP_OK;
+}
+static int terrain_set_instances_impl(hsqp_handle* h, int batch, const hsqp_terrain_placement* pl, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_terrain_set_instances_device" : "hsqp_terrain_set_instances";
+  const auto bad = [&](const std::string& what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = terrain_handle_ok(h, who)) return rc;
+  int top = -1;
+  if (pl) {
+    if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+    if (!dev)
+      for (int b = 0; b < batch; ++b) {
+        const std::string at = "instance " + std::to_string(b) + ": ";
+        if (pl[b].reserved != 0) return bad(at + "reserved must be 0");
+        if (pl[b].map < -1 || pl[b].map >= (int)h->terrain_maps.size()) return bad(at + "map outside [-1, n_maps) (" + std::to_string(h->terrain_maps.size()) + " maps resident)");
+        if (!std::isfinite(pl[b].origin_x) || !std::isfinite(pl[b].origin_y) || !std::isfinite(pl[b].yaw)) return bad(at + "non-finite origin or yaw");
+        top = pl[b].map > top ? pl[b].map : top;
+      }
+  } else if (batch < 0 || batch > h->st.max_batch) {
+    return bad("batch outside [0, max_batch]");
+  }
+  HCHECK(hipSetDevice(h->device));
+  if (pl) {
+    const size_t mb = (size_t)h->st.max_batch;
+    DEV_ENSURE(h->d_terrain_place, terrain_place_layout(Carve{}, mb).bytes, "terrain placements");
+    HCHECK(hipStreamSynchronize(h->stream));
+  }
+  h->terrain_B = 0;   // (a failure below leaves no table)
+  h->terrain_top = -1;
+  h->terrain_place_current = false;
+  if (pl) {
+    HCHECK(hipMemcpy(terrain_place_layout(Carve{h->d_terrain_place.p}, (size_t)h->st.max_batch).place, pl, (size_t)batch * sizeof(hsqp_terrain_placement),
+                     dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    h->terrain_B = batch;
+    h->terrain_top = top;
+  }
+  TerrainParams tp;
+  return terrain_params(h, tp);
+}
+int hsqp_terrain_set_instances(hsqp_handle* h, int batch, const hsqp_terrain_placement* place) { return terrain_set_instances_impl(h, batch, place, false); }
+int hsqp_terrain_set_instances_device(hsqp_handle* h, int batch, const hsqp_terrain_placement* d_place) { return terrain_set_instances_impl(h, batch, d_place, true); }
+int hsqp_terrain_clear(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  if (const int rc = terrain_handle_ok(h, "hsqp_terrain_clear")) return rc;
+  h->terrain_B = 0;
+  h->terrain_top = -1;
+  h->terrain_place_current = false;
+  return hsqp_terrain_set_maps(h, 0, nullptr, nullptr, nullptr, nullptr);
+}
+int hsqp_terrain_get_maps(hsqp_handle* h, int32_t* n_maps, int32_t* nx, int32_t* ny, double* cell, double* heights, size_t max_heights) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_terrain_get_maps";
+  const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = terrain_handle_ok(h, who)) return rc;
+  if (!n_maps) return bad("null n_maps");
+  size_t total = 0;
+  for (const TerrainMap& m : h->terrain_maps) total += (size_t)m.nx * m.ny;
+  if (heights && max_heights < total) return bad("max_heights is less than the resident maps hold");
+  *n_maps = (int32_t)h->terrain_maps.size();
+  for (size_t m = 0; m < h->terrain_maps.size(); ++m) {
+    if (nx) nx[m] = h->terrain_maps[m].nx;
+    if (ny) ny[m] = h->terrain_maps[m].ny;
+    if (cell) cell[m] = h->terrain_maps[m].cell;
+  }
+  if (heights && total) {
+    HCHECK(hipSetDevice(h->device));
+    HCHECK(hipStreamSynchronize(h->stream));
+    HCHECK(hipMemcpy(heights, terrain_maps_layout(Carve{h->d_terrain_maps.p}, total).pool, total * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return HSQP_OK;
+}
+int hsqp_terrain_get_instances(hsqp_handle* h, int batch, hsqp_terrain_placement* place) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_terrain_get_instances";
+  const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = terrain_handle_ok(h, who)) return rc;
+  if (!place) return bad("null table");
+  if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+  const int have = batch < h->terrain_B ? batch : h->terrain_B;
+  if (have) {
+    HCHECK(hipSetDevice(h->device));
+    HCHECK(hipStreamSynchronize(h->stream));
+    HCHECK(hipMemcpy(place, terrain_place_layout(Carve{h->d_terrain_place.p}, (size_t)h->st.max_batch).place, (size_t)have * sizeof(hsqp_terrain_placement), hipMemcpyDeviceToHost));
+  }
+  terrain_fill_place(nullptr, 0, (size_t)(batch - have), place + have);
+  return HSQP_OK;
+}
+static int terrain_eval_impl(hsqp_handle* h, int batch, int n_pts, const double* xy, double* height, double* normal, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_terrain_eval_device" : "hsqp_terrain_eval";
+  const auto bad = [&](const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; };
+  if (const int rc = terrain_handle_ok(h, who)) return rc;
+  if (!xy) return bad("null points");
+  if (batch < 1 || batch > h->st.max_batch) return bad("batch outside [1, max_batch]");
+  if (n_pts < 1 || n_pts > HSQP_TERRAIN_MAX_POINTS) return bad("n_pts outside [1, HSQP_TERRAIN_MAX_POINTS]");
+  ContactParams cp;
+  if (const int rc = contact_params(h, cp)) return rc;
+  TerrainParams tp;
+  if (const int rc = terrain_params(h, tp)) return rc;
+  HCHECK(hipSetDevice(h->device));
+  const size_t pts = (size_t)batch * (size_t)n_pts;
+  const double* d_xy = xy;
+  double* d_h = height;
+  double* d_n = normal;
+  StickyError step{h};
+  if (!dev) {
+    DEV_ENSURE(h->d_terrain_stage, terrain_stage_layout(Carve{}, pts, height, normal).bytes, "terrain staging");
+    const TerrainStage sg = terrain_stage_layout(Carve{h->d_terrain_stage.p}, pts, height, normal);
+    d_xy = sg.xy; d_h = sg.height; d_n = sg.normal;
+    step(hipMemcpyAsync(sg.xy, xy, pts * 2 * 8, hipMemcpyHostToDevice, h->stream), "upload points");
+  }
+  HSQP_LAUNCH(k_terrain_eval, dim3(batch), dim3(RO_THREADS), 0, h->stream, cp, tp, n_pts, d_xy, d_h, d_n);
+  step(hipGetLastError(), "k_terrain_eval");
+  if (!dev) {
+    if (height) step(hipMemcpyAsync(height, d_h, pts * 8, hipMemcpyDeviceToHost, h->stream), "download height");
+    if (normal) step(hipMemcpyAsync(normal, d_n, pts * 3 * 8, hipMemcpyDeviceToHost, h->stream), "download normal");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+int hsqp_terrain_eval(hsqp_handle* h, int batch, int n_pts, const double* xy, double* height, double* normal) { return terrain_eval_impl(h, batch, n_pts, xy, height, normal, false); }
+int hsqp_terrain_eval_device(hsqp_handle* h, int batch, int n_pts, const double* d_xy, double* d_height, double* d_normal) {
+  return terrain_eval_impl(h, batch, n_pts, d_xy, d_height, d_normal, true);
 }
 
 // ---- per-instance inertial variations of the torque plant (include/hsqp_inertia.h, csrc/hsqp_inertia.h): the resident table and the evaluation

@@ -8,9 +8,13 @@
 //                    point adds the base position q[2].  The eight points are eight work items; each leaves P, d, the force and its wrench
 //                    {P x f, f} about O, which plant_forward_dynamics picks up per coordinate by the subtree test of the pushes.
 // A point without normal force stores +0 in every entry of force and wrench: subtracting it changes no bit of the right-hand side.
+// On a height map (include/hsqp_terrain.h) the set carries the instance's map too and a second contact_point reads height and normal under each point.
 // Everything is uniform across the workgroup; the same source builds for the host with a one-lane context (tests/contact/contact_emu.cpp).
 #pragma once
+#include <type_traits>
+
 #include "hsqp_model.h"
+#include "hsqp_terrain.h"
 #include "../../include/hsqp_contact.h"
 
 namespace hsqp {
@@ -75,20 +79,57 @@ HSQP_HD void contact_point(const DevModel& dm, const StageWST<false>& ws, Contac
   for (int k = 0; k < 3; ++k) { ct.P[i][k] = P[k]; ct.f[i][k] = F[k]; ct.wr[i][k] = mom[k]; ct.wr[i][3 + k] = F[k]; }
 }
 
-HSQP_HD void contact_forces(const Ctx& ctx, const DevModel& dm, const StageWST<false>& ws, ContactSet& ct) {
+// ... and ONE instance's ground on a height map (include/hsqp_terrain.h): the set above — its height is the offset under the map — and the instance's map.
+// A type of its own: the plane's set, its contact_point and every instantiation built on them stay what they were.
+struct ContactTerrainSet : ContactSet {
+  TerrainSet ter;
+};
+// point i on the terrain: the height and the normal n of the map under the point's own (X, Y); d is the distance to the local tangent plane, the normal
+// force acts along n, friction against the tangential velocity.  A NaN height (a non-finite X or Y) stays in fn: the instance ends non-finite.
+HSQP_HD void contact_point(const DevModel& dm, const StageWST<false>& ws, ContactTerrainSet& ct, int i) {
+  const int f = i / HSQP_CONTACT_CORNERS, b = dm.contact_body[f];
+  double p[3], P[3], wxP[3], n[3], hm;
+  contact_corner(dm, f, i % HSQP_CONTACT_CORNERS, p);
+  m3_mulv(ws.R[b], p, P);
+  for (int k = 0; k < 3; ++k) P[k] += ws.r[b][k];
+  const double* vl = ws.vl[b + 2];
+  v3_cross(vl, P, wxP);
+  const double V[3] = {vl[3] + wxP[0], vl[4] + wxP[1], vl[5] + wxP[2]};
+  terrain_height(ct.ter, ws.q[0] + P[0], ws.q[1] + P[1], &hm, n);
+  const double d = ((ct.height + hm) - (ws.q[2] + P[2])) * n[2];
+  const double vn = (V[0] * n[0] + V[1] * n[1]) + V[2] * n[2], ddot = -vn;
+  double fn = d > 0.0 ? ct.k * d * (1.0 + ct.c * ddot) : (d == d ? 0.0 : d);
+  if (!(fn > 0.0) && fn == fn) fn = 0.0;   // (a NaN stays: the instance ends non-finite)
+  double F[3] = {0.0, 0.0, 0.0}, mom[3] = {0.0, 0.0, 0.0};
+  if (fn != 0.0) {
+    const double vt[3] = {V[0] - vn * n[0], V[1] - vn * n[1], V[2] - vn * n[2]};
+    const double s = -ct.mu * fn / sqrt(((vt[0] * vt[0] + vt[1] * vt[1]) + vt[2] * vt[2]) + ct.vs * ct.vs);
+    for (int k = 0; k < 3; ++k) F[k] = fn * n[k] + s * vt[k];
+    v3_cross(P, F, mom);
+  }
+  ct.d[i] = d;
+  for (int k = 0; k < 3; ++k) { ct.P[i][k] = P[k]; ct.f[i][k] = F[k]; ct.wr[i][k] = mom[k]; ct.wr[i][3 + k] = F[k]; }
+}
+
+template <class CT>
+HSQP_HD void contact_forces(const Ctx& ctx, const DevModel& dm, const StageWST<false>& ws, CT& ct) {
   WG_FOR(ctx, i, CT_PTS) contact_point(dm, ws, ct, i);
   WG_SYNC(ctx);
 }
 
-// The workspace of hsqp_contact_eval: the stage's, and the set
-struct ContactEvalWS {
+// The workspace of hsqp_contact_eval: the stage's, and the set (CT: ContactSet, or ContactTerrainSet while a terrain is resident)
+template <class CT>
+struct ContactEvalWST {
   StageWST<false> st;
-  ContactSet ct;
+  CT ct;
 };
+using ContactEvalWS = ContactEvalWST<ContactSet>;
 
-// hsqp_contact_eval for one instance: the model at state x [58] with instance b of the setting; force [8][3], pen [8] (either may be null)
-HSQP_HD void contact_eval_instance(const Ctx& ctx, const DevModel& dm, ContactEvalWS& w, const ContactParams& cp, int b, const double* x, double* force,
-                                   double* pen) {
+// hsqp_contact_eval for one instance: the model at state x [58] with instance b of the setting (tp: the resident terrain, read on a ContactTerrainSet
+// only); force [8][3], pen [8] (either may be null)
+template <class CT>
+HSQP_HD void contact_eval_instance(const Ctx& ctx, const DevModel& dm, ContactEvalWST<CT>& w, const ContactParams& cp, const TerrainParams* tp, int b, const double* x,
+                                   double* force, double* pen) {
   stage_topology(ctx, dm, w.st, false);
   WG_FOR(ctx, i, NV + NV + NJ + 12) {
     if (i < NV) w.st.q[i] = x[i];
@@ -96,6 +137,7 @@ HSQP_HD void contact_eval_instance(const Ctx& ctx, const DevModel& dm, ContactEv
     else if (i < 2 * NV + NJ) w.st.qddj[i - 2 * NV] = 0.0;
     else w.st.W[i - 2 * NV - NJ] = 0.0;
   }
+  if constexpr (!std::is_same<CT, ContactSet>::value) terrain_load(ctx, *tp, b, w.ct.ter);
   contact_load(ctx, cp, b, w.ct);   // (its barrier closes the topology and the inputs)
   stage_eval<false>(ctx, dm, w.st);
   contact_forces(ctx, dm, w.st, w.ct);
@@ -103,6 +145,23 @@ HSQP_HD void contact_eval_instance(const Ctx& ctx, const DevModel& dm, ContactEv
     const int pt = i / 4, k = i % 4;
     if (k < 3) { if (force) force[pt * 3 + k] = w.ct.f[pt][k]; }
     else if (pen) pen[pt] = w.ct.d[pt];
+  }
+}
+HSQP_HD void contact_eval_instance(const Ctx& ctx, const DevModel& dm, ContactEvalWS& w, const ContactParams& cp, int b, const double* x, double* force,
+                                   double* pen) {
+  contact_eval_instance(ctx, dm, w, cp, nullptr, b, x, force, pen);
+}
+
+// hsqp_terrain_eval for one instance: the ground g [n_pts] = the instance's height + the map's, and the normal [n_pts][3], at the points xy [n_pts][2]
+// (either output may be null).  ts: the instance's map in the workgroup's memory.
+HSQP_HD void terrain_eval_instance(const Ctx& ctx, const ContactParams& cp, const TerrainParams& tp, TerrainSet& ts, int b, int n_pts, const double* xy,
+                                   double* height, double* normal) {
+  terrain_load(ctx, tp, b, ts);
+  WG_FOR(ctx, i, n_pts) {
+    double hm, n[3];
+    terrain_height(ts, xy[2 * i], xy[2 * i + 1], &hm, n);
+    if (height) height[i] = cp.ground[b].height + hm;
+    if (normal) for (int k = 0; k < 3; ++k) normal[3 * i + k] = n[k];
   }
 }
 

@@ -83,17 +83,39 @@ struct PlantContactActStage {
   ActuatorWS act;
 };
 
-// ... and any of the four under the per-instance inertial variations of include/hsqp_inertia.h: once more a parameter of the instantiation — the four
+// ... and either grounded one on the height-map terrain of include/hsqp_terrain.h: the set carries the instance's map, the second contact_point of
+// hsqp_contact.h reads it — again a parameter of the instantiation: the four above are the code and the workspace they were before there was a terrain
+struct PlantTerrainStage {
+  StageWST<false> st;
+  PlantWS pl;
+  ContactTerrainSet ct;
+};
+struct PlantTerrainActStage {
+  StageWST<false> st;
+  PlantWS pl;
+  ContactTerrainSet ct;
+  ActuatorWS act;
+};
+
+// ... and any of the six under the per-instance inertial variations of include/hsqp_inertia.h: once more a parameter of the instantiation — the four
 // above are the code and the workspace they were before there was a table
 template <class Base>
 struct PlantVaried : Base {
   InertiaWS iw;                     // the instance's link scales and payloads
 };
-// whether the stage workspace carries the ground (ws.ct), the inertial variation (ws.iw)
+// whether the stage workspace carries the ground (ws.ct), the terrain (ws.ct.ter), the inertial variation (ws.iw)
 template <class SW> struct PlantGrounded { static constexpr bool value = false; };
 template <> struct PlantGrounded<PlantContactStage> { static constexpr bool value = true; };
 template <> struct PlantGrounded<PlantContactActStage> { static constexpr bool value = true; };
+template <> struct PlantGrounded<PlantTerrainStage> { static constexpr bool value = true; };
+template <> struct PlantGrounded<PlantTerrainActStage> { static constexpr bool value = true; };
 template <class Base> struct PlantGrounded<PlantVaried<Base>> : PlantGrounded<Base> {};
+template <class SW> struct PlantOnTerrain { static constexpr bool value = false; };
+template <> struct PlantOnTerrain<PlantTerrainStage> { static constexpr bool value = true; };
+template <> struct PlantOnTerrain<PlantTerrainActStage> { static constexpr bool value = true; };
+template <class Base> struct PlantOnTerrain<PlantVaried<Base>> : PlantOnTerrain<Base> {};
+// the type of the ground's set in the stage workspace (of a workspace without a ground: the null pointer's)
+template <class SW> struct PlantGroundSet { using type = typename std::conditional<PlantOnTerrain<SW>::value, ContactTerrainSet, ContactSet>::type; };
 template <class SW> struct PlantIsVaried { static constexpr bool value = false; };
 template <class Base> struct PlantIsVaried<PlantVaried<Base>> { static constexpr bool value = true; };
 
@@ -128,11 +150,11 @@ HSQP_HD int plant_end(const StageWST<false>& ws, int c) { return c < 6 ? NB : (c
 
 // vd [NV] (into pl.vd) of the plant at the state and the contact wrenches stage_eval<false> has just been run on (qdd_j = 0), under the joint
 // torques pl.tau and the pushes `mask` of ps (0: none).  ct (null: none; a constant of the caller's instantiation, folded when this is inlined) —
-// the ground of the instance: its contact forces replace the contact wrenches.  Ends with a barrier.
+// the ground of the instance (CT: ContactSet, or ContactTerrainSet on a height map): its contact forces replace the contact wrenches.  Ends with a barrier.
 // SOLVE = false: the assembly only — the bordered system pl.A is left as it is filled: rows 0 .. NV - 1 the mass matrix with the armature pl.arm, both
 // triangles; row NV the right-hand side; pl.Ic[0][0] the total mass.
-template <bool SOLVE = true>
-HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, PlantWS& pl, PushSet& ps, unsigned mask, ContactSet* ct = nullptr) {
+template <bool SOLVE = true, class CT = ContactSet>
+HSQP_HD void plant_forward_dynamics(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, PlantWS& pl, PushSet& ps, unsigned mask, CT* ct = nullptr) {
   // ---- composites over the subtrees; the wrench {P x f, f} about O of every active push and of every contact point
   WG_FOR(ctx, it, NB * 16 + HSQP_PUSH_MAX + (ct ? CT_PTS : 0)) {
     if (it >= NB * 16 + HSQP_PUSH_MAX) { contact_point(dm, ws, *ct, it - NB * 16 - HSQP_PUSH_MAX); continue; }

@@ -18,12 +18,13 @@
 //                at the eight sole corners in place of the policy's contact wrenches), the actuator model of include/hsqp_actuator.h (the joint command
 //                sampled at ticks and held, effort limits, passive joint torques: rollout_instance drives the ticks and writes the record of the
 //                last torques) and the per-instance link scales and payloads of include/hsqp_inertia.h (inertia_apply behind the stage_eval<false>
-//                at the plant's own state; the policy and tau_ff stay on the nominal model) — are parameters of the instantiation, not run-time
+//                at the plant's own state; the policy and tau_ff stay on the nominal model) and the height-map terrain of include/hsqp_terrain.h under
+//                that ground (each sole corner on the map's height and normal under it) — are parameters of the instantiation, not run-time
 //                branches: an option that is off is not in the code that runs.
 // ONE entry and ONE rule hold the instantiations together:
 //   rollout_entry     what one workgroup does for one instance of a call: the entry of the host emulation (tests/rollout/rollout_emu.h, one-lane
 //                     context).  k_rollout / k_rollout_plant (hsqp_capi.hip) spell the same statements out: called through it they measured slower
-//   rollout_dispatch  (host) the stage workspace a configuration gets: the one list of the ten types
+//   rollout_dispatch  (host) the stage workspace a configuration gets: the one list of the fourteen types
 #pragma once
 #include "hsqp_policy.h"
 #include "hsqp_cent_lq.h"
@@ -70,11 +71,14 @@ HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantStage& ws
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantContactStage& ws) { stage_topology(ctx, dm, ws.st); }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantActStage& ws) { stage_topology(ctx, dm, ws.st); }
 HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantContactActStage& ws) { stage_topology(ctx, dm, ws.st); }
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantTerrainStage& ws) { stage_topology(ctx, dm, ws.st); }
+HSQP_HD void rollout_topology(const Ctx& ctx, const DevModel& dm, PlantTerrainActStage& ws) { stage_topology(ctx, dm, ws.st); }
 
 // whether the stage workspace carries the actuator model (ws.act)
 template <class SW> struct RolloutActuated { static constexpr bool value = false; };
 template <> struct RolloutActuated<PlantActStage> { static constexpr bool value = true; };
 template <> struct RolloutActuated<PlantContactActStage> { static constexpr bool value = true; };
+template <> struct RolloutActuated<PlantTerrainActStage> { static constexpr bool value = true; };
 template <class Base> struct RolloutActuated<PlantVaried<Base>> : RolloutActuated<Base> {};
 
 HSQP_HD void rollout_flow(const Ctx& ctx, const DevModel& dm, StageWST<false>& ws, const double* x, const double* u, double* xdot) {
@@ -209,8 +213,8 @@ HSQP_HD void rollout_plant_command(const Ctx& ctx, const DevModel& dm, RolloutWS
   stage_eval<false>(ctx, dm, w.sw.st);
   joint_torques(ctx, dm, w.sw.st, pl.tau);
 }
-template <class SW>
-HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, ContactSet* ct, const RolloutPolicy& p, int controller, double s,
+template <class SW, class CT>
+HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, CT* ct, const RolloutPolicy& p, int controller, double s,
                                 const double* x, double* k, unsigned mask) {
   PlantWS& pl = w.sw.pl;
   rollout_plant_command(ctx, dm, w, p, controller, s, x);
@@ -224,7 +228,7 @@ HSQP_HD void rollout_eval_plant(const Ctx& ctx, const DevModel& dm, RolloutWS<SW
 }
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantStage>& w, const RolloutPolicy& p, int controller, double s, const double* x,
                           double* k, unsigned mask) {
-  rollout_eval_plant(ctx, dm, w, nullptr, p, controller, s, x, k, mask);
+  rollout_eval_plant(ctx, dm, w, (ContactSet*)nullptr, p, controller, s, x, k, mask);
 }
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantContactStage>& w, const RolloutPolicy& p, int controller, double s,
                           const double* x, double* k, unsigned mask) {
@@ -244,8 +248,8 @@ HSQP_HD void rollout_actuator_sample(const Ctx& ctx, const DevModel& dm, Rollout
   WG_SYNC(ctx);
 }
 // one evaluation: the command in force (a continuous one is formed here), the joint law at the plant's own state, forward dynamics
-template <class SW>
-HSQP_HD void rollout_eval_actuated(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, ContactSet* ct, const RolloutPolicy& p, int controller, double s,
+template <class SW, class CT>
+HSQP_HD void rollout_eval_actuated(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, CT* ct, const RolloutPolicy& p, int controller, double s,
                                    const double* x, double* k, unsigned mask) {
   PlantWS& pl = w.sw.pl;
   ActuatorWS& ac = w.sw.act;
@@ -260,17 +264,26 @@ HSQP_HD void rollout_eval_actuated(const Ctx& ctx, const DevModel& dm, RolloutWS
 }
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantActStage>& w, const RolloutPolicy& p, int controller, double s, const double* x,
                           double* k, unsigned mask) {
-  rollout_eval_actuated(ctx, dm, w, nullptr, p, controller, s, x, k, mask);
+  rollout_eval_actuated(ctx, dm, w, (ContactSet*)nullptr, p, controller, s, x, k, mask);
 }
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantContactActStage>& w, const RolloutPolicy& p, int controller, double s,
                           const double* x, double* k, unsigned mask) {
   rollout_eval_actuated(ctx, dm, w, &w.sw.ct, p, controller, s, x, k, mask);
 }
-// ... and any of the four on a varied plant (include/hsqp_inertia.h; the workspace's entry was loaded by inertia_load)
+// ... and either grounded one on the height-map terrain (include/hsqp_terrain.h; the workspace's map was loaded by terrain_load)
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantTerrainStage>& w, const RolloutPolicy& p, int controller, double s,
+                          const double* x, double* k, unsigned mask) {
+  rollout_eval_plant(ctx, dm, w, &w.sw.ct, p, controller, s, x, k, mask);
+}
+HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantTerrainActStage>& w, const RolloutPolicy& p, int controller, double s,
+                          const double* x, double* k, unsigned mask) {
+  rollout_eval_actuated(ctx, dm, w, &w.sw.ct, p, controller, s, x, k, mask);
+}
+// ... and any of the six on a varied plant (include/hsqp_inertia.h; the workspace's entry was loaded by inertia_load)
 template <class Base>
 HSQP_HD void rollout_eval(const Ctx& ctx, const DevModel& dm, RolloutWS<PlantVaried<Base>>& w, const RolloutPolicy& p, int controller, double s, const double* x,
                           double* k, unsigned mask) {
-  ContactSet* ct = nullptr;
+  typename PlantGroundSet<Base>::type* ct = nullptr;
   if constexpr (PlantGrounded<Base>::value) ct = &w.sw.ct;
   if constexpr (RolloutActuated<Base>::value) rollout_eval_actuated(ctx, dm, w, ct, p, controller, s, x, k, mask);
   else rollout_eval_plant(ctx, dm, w, ct, p, controller, s, x, k, mask);
@@ -527,31 +540,48 @@ template <> struct RolloutOnPlant<CentWST<false>> { static constexpr bool value 
 // Instance b of the call: its policy, the parts of the plant's setting that SW carries (a flow workspace: none, pp .. ip are not read), the integration
 template <class SW>
 HSQP_HD void rollout_entry(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutArgs& a, const PlantParams& pp, const ContactParams& cp,
-                           const ActuatorParams& ap, const InertiaParams& ip, int b) {
+                           const ActuatorParams& ap, const InertiaParams& ip, const TerrainParams& tp, int b) {
   const RolloutPolicy p{a.ut + (size_t)b * a.N * NU, a.dts ? a.dts + (size_t)b * a.N : nullptr, a.N, a.dt, a.K ? a.K + (size_t)b * a.count * NU * NX : nullptr,
                         a.uff ? a.uff + (size_t)b * a.count * NU : nullptr, a.first, a.count,
                         !RolloutOnPlant<SW>::value && dm.formulation == HSQP_FORM_CENTROIDAL ? 1 : 0};
   if constexpr (RolloutOnPlant<SW>::value) plant_load(ctx, pp, b, a.N, w.sw.pl);
   if constexpr (PlantGrounded<SW>::value) contact_load(ctx, cp, b, w.sw.ct);
+  if constexpr (PlantOnTerrain<SW>::value) terrain_load(ctx, tp, b, w.sw.ct.ter);
   if constexpr (RolloutActuated<SW>::value) actuator_load(ctx, ap, b, w.sw.act);
   if constexpr (PlantIsVaried<SW>::value) inertia_load(ctx, ip, b, w.sw.iw);
   rollout_instance(ctx, dm, w, p, a.st, a.s0[b], a.x0 + (size_t)b * NX, a.duration, a.n, a.x ? a.x + (size_t)b * a.n * NX : nullptr,
                    a.u ? a.u + (size_t)b * a.n * NU : nullptr, a.status + b, a.steps ? a.steps + b : nullptr, a.rejected ? a.rejected + b : nullptr, a.push, b);
 }
 
+// ... of a configuration without a terrain (SW carries none: tp is not read).  A caller that goes through rollout_dispatch instantiates this for the
+// terrain's workspaces too; the rule gives those only to a variant with maps and a table, which this caller's variant never has: not reached, nothing to do
+template <class SW>
+HSQP_HD void rollout_entry(const Ctx& ctx, const DevModel& dm, RolloutWS<SW>& w, const RolloutArgs& a, const PlantParams& pp, const ContactParams& cp,
+                           const ActuatorParams& ap, const InertiaParams& ip, int b) {
+  if constexpr (!PlantOnTerrain<SW>::value) rollout_entry(ctx, dm, w, a, pp, cp, ap, ip, TerrainParams{nullptr, nullptr, nullptr, 0}, b);
+}
+
 // ---- host side: which instantiation a configuration gets.  The options count on the torque plant only: the ground and the actuator model while
-// their setting is enabled, the variation while a table is resident.
+// their setting is enabled, the variation while a table is resident, the terrain (include/hsqp_terrain.h) on the ground while both a map and a placement
+// table are resident.
 struct RolloutVariant {
-  bool cent, torque, ground, actuated, varied;
-  RolloutVariant(bool centroidal, bool torque_plant, bool contact_enabled, bool actuator_enabled, bool inertia_table)
+  bool cent, torque, ground, actuated, varied, terrain;
+  RolloutVariant(bool centroidal, bool torque_plant, bool contact_enabled, bool actuator_enabled, bool inertia_table, bool terrain_maps = false,
+                 bool terrain_table = false)
       : cent(centroidal), torque(torque_plant), ground(torque_plant && contact_enabled), actuated(torque_plant && actuator_enabled),
-        varied(torque_plant && inertia_table) {}
+        varied(torque_plant && inertia_table), terrain(torque_plant && contact_enabled && terrain_maps && terrain_table) {}
 };
 template <class SW> struct RolloutStageType { using type = SW; };
-// f(RolloutStageType<SW>{}) for the stage workspace SW of the configuration.  The ten instantiations are listed here and nowhere else.
+// f(RolloutStageType<SW>{}) for the stage workspace SW of the configuration.  The fourteen instantiations are listed here and nowhere else.
 template <class F>
 auto rollout_dispatch(const RolloutVariant& v, F&& f) {
   if (!v.torque) return v.cent ? f(RolloutStageType<CentWST<false>>{}) : f(RolloutStageType<StageWST<false>>{});
+  if (v.terrain) switch ((v.varied ? 2 : 0) | (v.actuated ? 1 : 0)) {
+    case 0: return f(RolloutStageType<PlantTerrainStage>{});
+    case 1: return f(RolloutStageType<PlantTerrainActStage>{});
+    case 2: return f(RolloutStageType<PlantVaried<PlantTerrainStage>>{});
+    default: return f(RolloutStageType<PlantVaried<PlantTerrainActStage>>{});
+  }
   switch ((v.varied ? 4 : 0) | (v.actuated ? 2 : 0) | (v.ground ? 1 : 0)) {
     case 0: return f(RolloutStageType<PlantStage>{});
     case 1: return f(RolloutStageType<PlantContactStage>{});

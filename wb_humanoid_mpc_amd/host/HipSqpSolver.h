@@ -24,6 +24,7 @@
 #include "../../include/hsqp_contact.h"
 #include "../../include/hsqp_actuator.h"
 #include "../../include/hsqp_inertia.h"
+#include "../../include/hsqp_terrain.h"
 #include "../../include/hsqp_observe.h"
 
 namespace hsqp_host {
@@ -248,6 +249,44 @@ class HipSqpSolver {
     force.assign(B * pts * 3, 0.0); penetration.assign(B * pts, 0.0);
     const int rc = hsqp_contact_eval(h_, (int)B, x.data(), force.data(), penetration.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_contact_eval failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** ---- height-map terrain under that ground (include/hsqp_terrain.h): up to HSQP_TERRAIN_MAX_MAPS maps shared by all instances, and a placement (map,
+   *  origin, yaw; map = -1: the plane) per instance.  It acts on the torque plant with contact on while maps and a placement table are resident; the
+   *  instance's contact ground height is an offset under its map.  setTerrainMaps: map m is heights[m] = nx[m] * ny[m] doubles, row-major H[iy][ix]; no
+   *  maps: frees them.  setTerrainInstances: an empty vector: no table.  terrainHeight: the ground of each instance at world points xy [B][n][2] —
+   *  height [B][n], normal [B][n][3].  The MPC never sees it. */
+  void setTerrainMaps(const std::vector<int32_t>& nx, const std::vector<int32_t>& ny, const std::vector<double>& cell, const std::vector<std::vector<double>>& heights) {
+    if (ny.size() != nx.size() || cell.size() != nx.size() || heights.size() != nx.size()) throw std::runtime_error("[HipSqpSolver] setTerrainMaps: one nx, ny, cell and height array per map expected");
+    std::vector<double> pool;
+    for (size_t m = 0; m < nx.size(); ++m) {
+      if (nx[m] < 0 || ny[m] < 0 || heights[m].size() != (size_t)nx[m] * (size_t)ny[m]) throw std::runtime_error("[HipSqpSolver] setTerrainMaps: map " + std::to_string(m) + " needs nx * ny heights");
+      pool.insert(pool.end(), heights[m].begin(), heights[m].end());
+    }
+    const int rc = hsqp_terrain_set_maps(h_, (int)nx.size(), nx.data(), ny.data(), cell.data(), pool.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_terrain_set_maps failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void setTerrainInstances(const std::vector<hsqp_terrain_placement>& place) {
+    const int rc = hsqp_terrain_set_instances(h_, (int)place.size(), place.empty() ? nullptr : place.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_terrain_set_instances failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  void clearTerrain() {
+    const int rc = hsqp_terrain_clear(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_terrain_clear failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  std::vector<hsqp_terrain_placement> terrainInstances(int batch) {
+    if (batch < 1) throw std::runtime_error("[HipSqpSolver] terrainInstances: batch < 1");
+    std::vector<hsqp_terrain_placement> place((size_t)batch);
+    const int rc = hsqp_terrain_get_instances(h_, batch, place.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_terrain_get_instances failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return place;
+  }
+  void terrainHeight(int batch, const std::vector<double>& xy, std::vector<double>& height, std::vector<double>& normal) {
+    if (batch < 1 || xy.empty() || xy.size() % (2 * (size_t)batch) != 0) throw std::runtime_error("[HipSqpSolver] terrainHeight: the same number of (x, y) points per instance expected");
+    const size_t pts = xy.size() / 2;
+    height.assign(pts, 0.0); normal.assign(pts * 3, 0.0);
+    const int rc = hsqp_terrain_eval(h_, batch, (int)(pts / (size_t)batch), xy.data(), height.data(), normal.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_terrain_eval failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
   /** ---- the actuator model on the torque plant (include/hsqp_actuator.h): the joint command sampled at a control rate and held, effort limits,

@@ -20,6 +20,7 @@ from . import _abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HSQP_LIB") or os.path.join(_HERE, "libhsqp_hip.so")   # HSQP_LIB: debug builds only
 _dp = C.POINTER(C.c_double)
+_ip = C.POINTER(C.c_int32)
 _lib = None
 
 
@@ -139,6 +140,16 @@ def load_library():
     lib.hsqp_inertia_get_instances.argtypes = [C.c_void_p, C.c_int, _ii]
     lib.hsqp_inertia_eval.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     lib.hsqp_inertia_eval_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+    # include/hsqp_terrain.h
+    _tp = C.POINTER(_abi.TerrainPlacement)
+    lib.hsqp_terrain_set_maps.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, _dp]
+    lib.hsqp_terrain_set_instances.argtypes = [C.c_void_p, C.c_int, _tp]
+    lib.hsqp_terrain_set_instances_device.argtypes = [C.c_void_p, C.c_int, _tp]
+    lib.hsqp_terrain_clear.argtypes = [C.c_void_p]
+    lib.hsqp_terrain_get_maps.argtypes = [C.c_void_p, _ip, _ip, _ip, _dp, _dp, C.c_size_t]
+    lib.hsqp_terrain_get_instances.argtypes = [C.c_void_p, C.c_int, _tp]
+    lib.hsqp_terrain_eval.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]
+    lib.hsqp_terrain_eval_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]
     # include/hsqp_observe.h
     _os, _oi = C.POINTER(_abi.ObserveSettings), C.POINTER(_abi.ObserveInstance)
     lib.hsqp_observe_defaults.argtypes = [_os]
@@ -674,6 +685,81 @@ class HipSqpSolver:
         f, d = np.zeros((B, _abi.CONTACT_FEET, _abi.CONTACT_CORNERS, 3)), np.zeros((B, _abi.CONTACT_FEET, _abi.CONTACT_CORNERS))
         self._check(self.lib.hsqp_contact_eval(self.h, B, x.ctypes.data_as(_dp), f.ctypes.data_as(_dp), d.ctypes.data_as(_dp)))
         return f, d
+
+    # ---- include/hsqp_terrain.h: per-instance height-map terrain under that ground
+    @staticmethod
+    def pack_terrain_maps(maps):
+        """The arrays of hsqp_terrain_set_maps: maps = a list of (heights [ny, nx], cell) -> (nx, ny int32 [n], cell [n], heights concatenated)."""
+        hs = [np.ascontiguousarray(h, dtype=np.float64) for h, _ in maps]
+        if any(h.ndim != 2 for h in hs):
+            raise ValueError("a map is heights [ny, nx] (row-major: H[iy][ix])")
+        nx, ny = np.array([h.shape[1] for h in hs], np.int32), np.array([h.shape[0] for h in hs], np.int32)
+        cell = np.array([float(c) for _, c in maps], np.float64)
+        return nx, ny, cell, (np.concatenate([h.ravel() for h in hs]) if hs else np.zeros(0))
+
+    @staticmethod
+    def pack_terrain_instances(place):
+        """The table of hsqp_terrain_set_instances as a ctypes array: per instance dict(map, origin (x, y), yaw) — map -1 (or None for the entry): the plane."""
+        tab = (_abi.TerrainPlacement * len(place))()
+        for t, p in zip(tab, place):
+            p = p or dict(map=-1)
+            ox, oy = p.get("origin", (0.0, 0.0))
+            t.map, t.reserved, t.origin_x, t.origin_y, t.yaw = int(p["map"]), int(p.get("reserved", 0)), float(ox), float(oy), float(p.get("yaw", 0.0))
+        return tab
+
+    def set_terrain_maps(self, maps):
+        """hsqp_terrain_set_maps: the height maps all instances share — a list of (heights [ny, nx], cell), at most 16, 2 .. 256 nodes per axis; an empty
+        list frees them.  A map acts under the instances set_terrain_instances places on it, on the torque plant with contact on; the MPC never sees it."""
+        nx, ny, cell, heights = self.pack_terrain_maps(maps)
+        self._check(self.lib.hsqp_terrain_set_maps(self.h, len(nx), nx.ctypes.data_as(_ip), ny.ctypes.data_as(_ip), cell.ctypes.data_as(_dp), heights.ctypes.data_as(_dp)))
+
+    def set_terrain_instances(self, place):
+        """hsqp_terrain_set_instances: per instance dict(map, origin (x, y) — the world position of grid node (0, 0) —, yaw), map -1: the plane; None: no
+        table.  The instance's contact ground height (set_contact / set_contact_instances) is an offset under its map."""
+        if place is None:
+            self._check(self.lib.hsqp_terrain_set_instances(self.h, 0, None))
+            return
+        tab = self.pack_terrain_instances(place)
+        self._check(self.lib.hsqp_terrain_set_instances(self.h, len(tab), tab))
+
+    def set_terrain_instances_device(self, batch, place_ptr):
+        """hsqp_terrain_set_instances_device: the table in device memory (address); its values are not checked (the kernels clamp the map index)."""
+        self._check(self.lib.hsqp_terrain_set_instances_device(self.h, int(batch), C.cast(C.c_void_p(int(place_ptr)), C.POINTER(_abi.TerrainPlacement))))
+
+    def clear_terrain(self):
+        self._check(self.lib.hsqp_terrain_clear(self.h))
+
+    def get_terrain_maps(self):
+        """hsqp_terrain_get_maps: a list of (heights [ny, nx], cell)."""
+        n = np.zeros(1, np.int32)
+        nx, ny, cell = np.zeros(_abi.TERRAIN_MAX_MAPS, np.int32), np.zeros(_abi.TERRAIN_MAX_MAPS, np.int32), np.zeros(_abi.TERRAIN_MAX_MAPS)
+        self._check(self.lib.hsqp_terrain_get_maps(self.h, n.ctypes.data_as(_ip), nx.ctypes.data_as(_ip), ny.ctypes.data_as(_ip), cell.ctypes.data_as(_dp), None, 0))
+        total = int((nx[:n[0]].astype(np.int64) * ny[:n[0]]).sum())
+        heights = np.zeros(max(total, 1))
+        self._check(self.lib.hsqp_terrain_get_maps(self.h, n.ctypes.data_as(_ip), None, None, None, heights.ctypes.data_as(_dp), total))
+        out, at = [], 0
+        for m in range(int(n[0])):
+            cnt = int(nx[m]) * int(ny[m])
+            out.append((heights[at:at + cnt].reshape(int(ny[m]), int(nx[m])).copy(), float(cell[m])))
+            at += cnt
+        return out
+
+    def get_terrain_instances(self, batch):
+        """hsqp_terrain_get_instances: per instance dict(map, origin, yaw); instances past the table have map -1."""
+        tab = (_abi.TerrainPlacement * int(batch))()
+        self._check(self.lib.hsqp_terrain_get_instances(self.h, int(batch), tab))
+        return [dict(map=int(t.map), origin=(t.origin_x, t.origin_y), yaw=t.yaw) for t in tab]
+
+    def terrain_height(self, xy):
+        """hsqp_terrain_eval at the world points xy [B, n, 2]: (height [B, n] — the instance's ground height plus its map's —, normal [B, n, 3]).  Works
+        with any plant kind and needs no resident solution."""
+        xy = _c(xy)
+        if xy.ndim != 3 or xy.shape[2] != 2:
+            raise ValueError("xy: [B, n, 2]")
+        B, n = xy.shape[:2]
+        hgt, nrm = np.zeros((B, n)), np.zeros((B, n, 3))
+        self._check(self.lib.hsqp_terrain_eval(self.h, B, n, xy.ctypes.data_as(_dp), hgt.ctypes.data_as(_dp), nrm.ctypes.data_as(_dp)))
+        return hgt, nrm
 
     # ---- include/hsqp_actuator.h: the actuator model on the torque plant
     def actuator_settings(self, enabled=True, command_period=None, effort_limit=None, damping=None, friction=None, friction_velocity=None, reserved=0):
