@@ -14,6 +14,7 @@ iteration and the rollout, and its rollout keeps no step counters).
                                       [--inertia] [--mass-spread 0.15] [--payload KG]
                                       [--terrain ramp|ledge|rubble] [--terrain-seed 2026]
                                       [--observe] [--obs-noise 0.005] [--obs-bias 0.02] [--sensor-delay 1] [--compute-delay 1] [--obs-seed 2026]
+                                      [--metrics]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
                                       [--plant torque [--contact ...] [--actuator ...] [--inertia ...]]
 --with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
@@ -52,6 +53,12 @@ side, the tracking of the commanded planar velocity (`tracking_on`, `tracking_of
 and the timed cycles, and over the instances at the end) and the cycle times of both runs.
 It reports; it asserts nothing (profiles/observe_loop_ab.txt: with the feed-forward controller one period of compute delay is enough to lose the walk
 on the flow plant, with --controller feedback the defaults walk).
+--metrics: the episode metrics of include/hsqp_metrics.h are on for the whole run (warm-up, the single cycles and the one long call): one record per
+instance accumulated on the device and read back once, at the end.  The run prints a table of the open record of every instance (and, where an episode was
+closed, of the last closed one) and the line carries `metrics`: the summary over the batch (survivors, RMS tracking error, distance, cost of transport) and
+the share of torque samples in saturation.  With --terrain the final base position, and with --actuator `saturated_share` (then: the share of the
+instances with a saturated sample anywhere in their records), come from the records instead of from logs and the last actuator record.  Opt-in: without
+the flag the tool's output is what it was.
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -278,6 +285,7 @@ def main():
     ap.add_argument("--sensor-delay", type=int, default=1)
     ap.add_argument("--compute-delay", type=int, default=1)
     ap.add_argument("--obs-seed", type=int, default=2026)
+    ap.add_argument("--metrics", action="store_true")
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -312,6 +320,33 @@ def tracking_error(m, x, cmd):
     c, sn = np.cos(x[:, 3]), np.sin(x[:, 3])
     want = np.column_stack([c * cmd[:, 0] - sn * cmd[:, 1], sn * cmd[:, 0] + c * cmd[:, 1]])
     return np.linalg.norm(x[:, 6 + m.nj:8 + m.nj] - want, axis=1)
+
+
+def metrics_report(s, args, ep):
+    """The records at the end of the run: the per-instance table on stdout, the summary for the JSON line, (current, previous)."""
+    cur, prev = s.loop_metrics("current"), s.loop_metrics("previous")
+    causes = {-1: "open", 0: "host", 1: "numeric", 2: "rollout", 3: "bounds"}
+    print(f"episode metrics: {len(cur['cycles'])} instances, period {args.period:.4f} s (the open record; 'closed': the last closed one)")
+    print(f"{'instance':>8} {'record':>7} {'cycles':>6} {'first':>6} {'end':>8} {'track rms':>10} {'track max':>10} {'dist [m]':>9} {'path [m]':>9} {'z min':>7} {'z max':>7} "
+          f"{'tilt max':>8} {'sat share':>9} {'tau ratio':>9} {'work+ [J]':>10} {'flight':>6} {'touchdowns':>10} {'load max':>9} {'pen max':>8} {'cost mean':>11} {'steps':>6} {'rej':>5}")
+    for b in range(len(cur["cycles"])):
+        for label, r in (("open", cur), ("closed", prev)):
+            n = int(r["cycles"][b])
+            if not n:
+                continue
+            dist = float(np.linalg.norm(r["end_xy"][b] - r["start_xy"][b]))
+            sat = r["saturated_samples"][b] / r["torque_samples"][b] if r["torque_samples"][b] else 0.0
+            print(f"{b:8d} {label:>7} {n:6d} {int(r['first_cycle'][b]):6d} {causes.get(int(r['end_cause'][b]), '?'):>8} {np.sqrt(r['vel_err_sq'][b] / n):10.5f} "
+                  f"{r['vel_err_max'][b]:10.5f} {dist:9.4f} {r['path_length'][b]:9.4f} {r['height_min'][b]:7.4f} {r['height_max'][b]:7.4f} {r['tilt_max'][b]:8.4f} "
+                  f"{sat:9.4f} {r['tau_ratio_max'][b]:9.4f} {r['work_pos'][b]:10.3f} {int(r['flight_samples'][b]):6d} "
+                  f"{'%d/%d' % tuple(int(v) for v in r['touchdowns'][b]):>10} {r['load_max'][b]:9.1f} {r['penetration_max'][b]:8.5f} {r['cost_sum'][b] / n:11.4e} "
+                  f"{int(r['rollout_steps'][b]):6d} {int(r['rollout_rejected'][b]):5d}")
+    sm = s.metrics_summary(cur)
+    torque = int(cur["torque_samples"].sum() + prev["torque_samples"].sum())
+    sm = {k: (round(v, 6) if isinstance(v, float) else v) for k, v in sm.items()}
+    sm["saturated_sample_share"] = round(float((cur["saturated_samples"].sum() + prev["saturated_samples"].sum()) / torque), 4) if torque else None
+    sm["closed_records"] = int((prev["cycles"] > 0).sum())
+    return sm, cur, prev
 
 
 def timed_run(args, observe):
@@ -370,6 +405,8 @@ def timed_run(args, observe):
             maps, place, labels = terrain_args(args, x_init)
             s.set_terrain_maps(maps)
             s.set_terrain_instances(place)
+        if args.metrics:
+            s.loop_metrics_enable()
         last_pos = x_init[:, :3].copy()
         masses = None
         if args.inertia:
@@ -396,6 +433,15 @@ def timed_run(args, observe):
         ep = s.loop_episodes() if args.isolate or args.terrain else None
         heights.append(x_end[:, 2].copy())
         saturated = saturated_share(s, m, args) if args.actuator else None
+        metrics = None
+        if args.metrics:                                          # the records instead of logs and of the last actuator record
+            metrics, rec, rec_prev = metrics_report(s, args, ep)
+            seen = (rec["torque_samples"] + rec_prev["torque_samples"]) > 0
+            if args.actuator:
+                saturated = round(float(((rec["saturated_samples"] + rec_prev["saturated_samples"])[seen] > 0).mean()), 4) if seen.any() else 0.0
+            for r in (rec_prev, rec):                             # where an instance ended: its open record's last sample, else its last closed record's
+                have = r["cycles"] > 0
+                last_pos[have, :2] = r["end_xy"][have]
         probe = rollout_probe(s, args, x_end) if args.plant else None
     finally:
         s.close()
@@ -404,9 +450,11 @@ def timed_run(args, observe):
     if args.terrain:
         total = args.warmup + 2 * args.cycles
         live = np.isfinite(x_end).all(axis=1)
-        last_pos[live] = x_end[live, :3]
+        if not args.metrics:
+            last_pos[live] = x_end[live, :3]
         survived = np.where(ep["n_failures"] > 0, ep["fail_cycle"], total).astype(int)
-        print(f"terrain {args.terrain}: {B} instances, {total} cycles of {args.period:.4f} s; final base position: the last one logged (the second half of the run keeps no log)")
+        where = "x, y from the episode metrics' records" if args.metrics else "the last one logged (the second half of the run keeps no log)"
+        print(f"terrain {args.terrain}: {B} instances, {total} cycles of {args.period:.4f} s; final base position: {where}")
         print(f"{'instance':>8} {'map':>4} {'difficulty':>10} {'survived':>9} {'base x':>9} {'base y':>9} {'base z':>9}")
         for b in range(B):
             print(f"{b:8d} {b % TERRAIN_MAPS:4d} {labels[b % TERRAIN_MAPS]:>10} {survived[b]:9d} {last_pos[b, 0]:9.4f} {last_pos[b, 1]:9.4f} {last_pos[b, 2]:9.4f}")
@@ -418,6 +466,7 @@ def timed_run(args, observe):
     if args.inertia:
         for b in range(B):
             print(f"instance {b}: total mass {masses[b]:.3f} kg, finished {'yes' if finished[b] else 'no'}")
+    extra = {"metrics": metrics} if args.metrics else {}
     return dict({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
                       "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
                       "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None,
@@ -434,7 +483,7 @@ def timed_run(args, observe):
                       "base_height_range": [round(float(heights.min()), 5), round(float(heights.max()), 5)],
                       "observe": dict(noise=args.obs_noise, height_bias=args.obs_bias, sensor_delay=args.sensor_delay, compute_delay=args.compute_delay,
                                       seed=args.obs_seed) if observe else None,
-                      "tracking": dict(mean=round(float(np.mean(track)), 5), end=round(float(np.nanmean(tracking_error(m, x_end, cmd))), 5))})
+                      "tracking": dict(mean=round(float(np.mean(track)), 5), end=round(float(np.nanmean(tracking_error(m, x_end, cmd))), 5))}, **extra)
 
 
 if __name__ == "__main__":

@@ -159,6 +159,23 @@ class EpisodeSettings(C.Structure):   # hsqp_episode_settings
 # entry points of include/hsqp_episode.h (tests/test_episode.py checks that the library exports each of them and the binding declares it)
 EPISODE_ENTRY_POINTS = ("hsqp_episode_defaults", "hsqp_loop_isolate", "hsqp_loop_reset_instances", "hsqp_loop_episodes", "hsqp_loop_episodes_device")
 
+# include/hsqp_metrics.h
+METRICS_CURRENT, METRICS_PREVIOUS = 0, 1
+METRICS_END_OPEN, METRICS_END_HOST = -1, 0
+
+
+class Metrics(C.Structure):   # hsqp_metrics: 8-byte fields only
+    _fields_ = [(k, C.c_int64) for k in ("cycles", "first_cycle", "end_cause", "torque_samples", "ground_samples", "flight_samples")] + \
+               [("touchdowns", C.c_int64 * 2)] + [(k, C.c_int64) for k in ("saturated_samples", "saturated_joint_samples", "rollout_steps", "rollout_rejected")] + \
+               [("duration", C.c_double), ("start_xy", C.c_double * 2), ("end_xy", C.c_double * 2)] + \
+               [(k, C.c_double) for k in ("path_length", "vel_err_sq", "vel_err_max", "yaw_rate_err_sq", "height_err_sq", "height_min", "height_max", "tilt_max",
+                                          "tau_sq", "tau_ratio_max", "work_pos", "work_abs", "load_sum", "load_max", "penetration_max", "cost_sum",
+                                          "dynamics_sse_max", "equality_sse_max")]
+
+
+# entry points of include/hsqp_metrics.h (tests/test_metrics.py checks that the library exports each of them and the binding declares it)
+METRICS_ENTRY_POINTS = ("hsqp_loop_metrics_enable", "hsqp_loop_metrics_disable", "hsqp_loop_metrics_restart", "hsqp_loop_metrics", "hsqp_loop_metrics_device")
+
 # include/hsqp_push.h
 PUSH_MAX = 8
 

@@ -25,6 +25,7 @@
 #include "../../include/hsqp_loop.h"
 #include "hsqp_gait.h"
 #include "hsqp_episode.h"
+#include "hsqp_metrics.h"
 #include "hsqp_observe.h"
 #include "hsqp_warm.h"
 #include "hsqp_cent.h"
@@ -1039,6 +1040,18 @@ __global__ __launch_bounds__(RO_THREADS) void k_contact_eval(const DevModel* __r
                         pen ? pen + (size_t)b * CT_PTS : nullptr);
 }
 static_assert(sizeof(ContactEvalWST<ContactTerrainSet>) <= 65536, "hsqp_contact_eval runs without a dynamic-LDS attribute");
+// the episode metrics of the resident loop (include/hsqp_metrics.h, csrc/hsqp_metrics.h): one workgroup per instance behind the rollout of a cycle.
+// CT: MetricsNoGround (the light path: no stage evaluation), ContactSet, or ContactTerrainSet while a terrain is resident (tp is read by that one only)
+template <class CT>
+__global__ __launch_bounds__(RO_THREADS) void k_loop_metrics(const DevModel* __restrict__ dm, MetricsArgs a, ContactParams cp, TerrainParams tp) {
+  MetricsWST<CT>& w = *reinterpret_cast<MetricsWST<CT>*>(hsqp_smem);
+  metrics_instance<CT>(Ctx{(int)threadIdx.x, RO_THREADS, nullptr}, *dm, w, a, cp, &tp, blockIdx.x);
+}
+static_assert(sizeof(MetricsWST<ContactTerrainSet>) <= 65536, "k_loop_metrics runs without a dynamic-LDS attribute");
+// ... and the host's closing of n records (hsqp_loop_reset_instances, hsqp_loop_metrics_restart): one wave per request entry
+__global__ __launch_bounds__(64) void k_metrics_host_close(const int* __restrict__ ids, hsqp_metrics* rec, int* feet) {
+  metrics_host_close(Ctx{(int)threadIdx.x, 64, nullptr}, ids, rec, feet, blockIdx.x);
+}
 // hsqp_terrain_eval (include/hsqp_terrain.h): one workgroup per instance — the ground's height and normal under n_pts world points
 __global__ __launch_bounds__(RO_THREADS) void k_terrain_eval(ContactParams cp, TerrainParams tp, int n_pts, const double* __restrict__ xy, double* __restrict__ height,
                                                              double* __restrict__ normal) {
@@ -1234,6 +1247,12 @@ struct hsqp_handle {
     EpisodeState ep = {};
     double* x_reset = nullptr; double* v_use = nullptr;
     int* req_ids = nullptr; double* req_x0 = nullptr; double* req_v = nullptr;
+    // episode metrics (include/hsqp_metrics.h): off after every start.  metrics: the kernel runs behind every rollout; metrics_made: the records exist since
+    // the start (readable after a disable).  In d_metrics (metrics_layout): the records [B][2], the rollout's step counts, the feet's flags, a request's ids
+    bool metrics = false, metrics_made = false;
+    hsqp_metrics* met_rec = nullptr;
+    int32_t* met_steps = nullptr; int32_t* met_rejected = nullptr;
+    int* met_feet = nullptr; int* met_ids = nullptr;
     // the observation model (include/hsqp_observe.h): the ring [delay + 1][B][58] (null without a delay) and the observations of the even and the odd
     // cycles [B][58] in d_observe (observe_layout); obs_last: a cycle with the model in force has completed since the start, obs_tp its problem time
     double* obs_ring = nullptr; double* obs_y[2] = {nullptr, nullptr};
@@ -1250,7 +1269,7 @@ struct hsqp_handle {
     int* status = nullptr; int* ne = nullptr; int* seq = nullptr;
     double* ev = nullptr; double* v = nullptr; double* x = nullptr;
   } gait;
-  DevBuf<char> d_gait, d_episode;
+  DevBuf<char> d_gait, d_episode, d_metrics;
   DevBuf<char> d_loop, d_loop_log;   // the loop's resident arrays; staging of hsqp_loop_run's host logs and of hsqp_command_targets' host arrays
   double kernel_ms[5] = {0, 0, 0, 0, 0};
   int last_iterations = 0;
@@ -1332,6 +1351,12 @@ static size_t episode_layout(Carve c, hsqp_handle::Loop& L, size_t B) {
   L.ep = EpisodeState{c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B), c.take<int>(B)};
   L.x_reset = c.take<double>(B * NX); L.v_use = c.take<double>(B * CMD_N);
   L.req_ids = c.take<int>(B); L.req_x0 = c.take<double>(B * NX); L.req_v = c.take<double>(B * CMD_N);
+  return c.bytes();
+}
+// d_metrics: the records [B][2] (CURRENT, PREVIOUS), the step counts of the cycle's rollout, the feet's flags [B][2], the ids of a restart request
+static size_t metrics_layout(Carve c, hsqp_handle::Loop& L, size_t B) {
+  L.met_rec = c.take<hsqp_metrics>(2 * B); L.met_steps = c.take<int32_t>(B); L.met_rejected = c.take<int32_t>(B);
+  L.met_feet = c.take<int>(2 * B); L.met_ids = c.take<int>(B);
   return c.bytes();
 }
 // d_observe: the loop's ring of plant states (absent without a delay) and the observations of the even and the odd cycles
@@ -3287,6 +3312,7 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
   L.cycle = 0;
   L.obs_last = false;
   L.isolate = false;
+  L.metrics = false; L.metrics_made = false;
   L.gait = gait != nullptr;
   L.started = true;
   return HSQP_OK;
@@ -3510,6 +3536,32 @@ static void launch_observe(hsqp_handle* h, const ObserveArgs& a) {
   HSQP_LAUNCH(k_observe, dim3((a.B * OBS_BLOCKS + OBS_THREADS - 1) / OBS_THREADS), dim3(OBS_THREADS), 0, h->stream, a);
 }
 
+// the metrics kernel of the cycle that has just been rolled out: the form follows the rollout's own variant rule (ground, terrain, actuator model)
+static int loop_metrics_cycle(hsqp_handle* h) {
+  hsqp_handle::Loop& L = h->loop;
+  const RolloutVariant v(false, h->plant.kind == HSQP_PLANT_TORQUE, h->contact.enabled, h->actuator.enabled, h->inertia_B, !h->terrain_maps.empty(), h->terrain_B);
+  MetricsArgs a{};
+  a.isolate = L.isolate ? 1 : 0; a.cycle = L.cycle; a.period = L.st.period;
+  if (L.isolate) { a.st = L.ep_st; a.ep_state = L.ep.state; }
+  a.it_status = h->d_status; a.perf = h->d_perf_after; a.ro_status = L.ro_status;
+  a.xs = L.xs; a.x_before = L.x; a.cmd = L.isolate ? L.v_use : L.v_cmd;
+  a.steps = L.met_steps; a.rejected = L.met_rejected;
+  if (v.actuated) {   // (the rollout has just written the record)
+    const ActuatorBuf ab = actuator_layout(Carve{h->d_actuator.p}, (size_t)h->st.max_batch);
+    a.act_last = ab.last; a.act_limit = ab.table;
+  }
+  a.rec = L.met_rec; a.feet = L.met_feet;
+  ContactParams cp{nullptr, 0.0, 0.0, 0.0};
+  TerrainParams tp{nullptr, nullptr, nullptr, 0};
+  if (v.ground) { const int rc = contact_params(h, cp); if (rc != HSQP_OK) return rc; }
+  if (v.terrain) { const int rc = terrain_params(h, tp); if (rc != HSQP_OK) return rc; }
+  if (v.terrain) HSQP_LAUNCH(k_loop_metrics<ContactTerrainSet>, dim3(L.B), dim3(RO_THREADS), sizeof(MetricsWST<ContactTerrainSet>), h->stream, h->d_dm, a, cp, tp);
+  else if (v.ground) HSQP_LAUNCH(k_loop_metrics<ContactSet>, dim3(L.B), dim3(RO_THREADS), sizeof(MetricsWST<ContactSet>), h->stream, h->d_dm, a, cp, tp);
+  else HSQP_LAUNCH(k_loop_metrics<MetricsNoGround>, dim3(L.B), dim3(RO_THREADS), sizeof(MetricsWST<MetricsNoGround>), h->stream, h->d_dm, a, cp, tp);
+  HCHECK(hipGetLastError());
+  return HSQP_OK;
+}
+
 static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   hsqp_handle::Loop& L = h->loop;
   const hsqp_loop_settings& st = L.st;
@@ -3563,7 +3615,10 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   // 3. the iteration
   { const int rc = hsqp_iterate_device(h, st.iterations, st.iterate_flags); if (rc != HSQP_OK) return rc; }
   // 4. the plant under the policy over one period, from its true state (with the model in force at s0 = compute_delay periods in the policy's frame)
-  { const int rc = rollout_impl(h, &st.rollout, L.s0, L.x, st.period, 1, L.xs, L.us, L.ro_status, nullptr, nullptr, true, iso); if (rc != HSQP_OK) return rc; }
+  { const int rc = rollout_impl(h, &st.rollout, L.s0, L.x, st.period, 1, L.xs, L.us, L.ro_status, L.metrics ? L.met_steps : nullptr, L.metrics ? L.met_rejected : nullptr, true, iso);
+    if (rc != HSQP_OK) return rc; }
+  // the episode metrics (include/hsqp_metrics.h): the cycle's sample, while L.x is still the state the rollout started from and the command the one step 1 read
+  if (L.metrics) { const int rc = loop_metrics_cycle(h); if (rc != HSQP_OK) return rc; }
   // 5. the rolled-out state is the next measured state
   HCHECK(hipMemcpyAsync(L.x, L.xs, B * NX * 8, hipMemcpyDeviceToDevice, h->stream));
   HCHECK(hipMemcpyAsync(L.v_filt, vf_next, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -3828,20 +3883,27 @@ static int loop_isolated(hsqp_handle* h, const char* who) {
   return HSQP_OK;
 }
 
+// the ids of a request on the started loop (hsqp_loop_reset_instances, hsqp_loop_metrics_restart): n >= 1 of them, each inside [0, B), none repeated
+static int loop_ids_ok(hsqp_handle* h, const char* who, int n, const int32_t* ids) {
+  const int B = h->loop.B;
+  if (n < 1) return loop_bad(h, who, "n < 1");
+  if (!ids) return loop_bad(h, who, "null ids");
+  if (n > B) return loop_bad(h, who, "more ids than instances (an id is repeated)");
+  std::vector<char> seen(B, 0);
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= B) return loop_bad(h, who, "id outside [0, B)");
+    if (seen[ids[i]]) return loop_bad(h, who, "repeated id");
+    seen[ids[i]] = 1;
+  }
+  return HSQP_OK;
+}
+
 int hsqp_loop_reset_instances(hsqp_handle* h, int n, const int32_t* ids, const double* x0, const double* v_cmd) {
   if (!h) return HSQP_ERR_BAD_ARG;
   const char* who = "hsqp_loop_reset_instances";
   { const int rc = loop_isolated(h, who); if (rc != HSQP_OK) return rc; }
   hsqp_handle::Loop& L = h->loop;
-  if (n < 1) return loop_bad(h, who, "n < 1");
-  if (!ids) return loop_bad(h, who, "null ids");
-  if (n > L.B) return loop_bad(h, who, "more ids than instances (an id is repeated)");
-  std::vector<char> seen(L.B, 0);
-  for (int i = 0; i < n; ++i) {
-    if (ids[i] < 0 || ids[i] >= L.B) return loop_bad(h, who, "id outside [0, B)");
-    if (seen[ids[i]]) return loop_bad(h, who, "repeated id");
-    seen[ids[i]] = 1;
-  }
+  { const int rc = loop_ids_ok(h, who, n, ids); if (rc != HSQP_OK) return rc; }
   if (x0 && !all_finite(x0, (size_t)n * NX)) return loop_bad(h, who, "non-finite x0");
   if (v_cmd && !all_finite(v_cmd, (size_t)n * CMD_N)) return loop_bad(h, who, "non-finite command");
   HCHECK(hipSetDevice(h->device));
@@ -3852,6 +3914,7 @@ int hsqp_loop_reset_instances(hsqp_handle* h, int n, const int32_t* ids, const d
   if (step.rc == HSQP_OK) {
     const HostResetArgs a{L.req_ids, x0 ? L.req_x0 : nullptr, v_cmd ? L.req_v : nullptr, L.x_reset, L.ep, L.x, L.v_cmd, L.v_filt, L.v_use};
     HSQP_LAUNCH(k_episode_host_reset, dim3(n), dim3(64), 0, h->stream, a);
+    if (L.metrics) HSQP_LAUNCH(k_metrics_host_close, dim3(n), dim3(64), 0, h->stream, (const int*)L.req_ids, L.met_rec, L.met_feet);   // the records close with END_HOST
     const bool obs = observe_in_force(h);
     const double lag = obs ? observe_policy_time(h->observe.compute_delay, L.st.period) : 0.0;
     if (L.gait)   // the gait's clock: the problem time of the next cycle (include/hsqp_observe.h)
@@ -3884,6 +3947,73 @@ int hsqp_loop_episodes(hsqp_handle* h, int32_t* state, int32_t* cause, int32_t* 
 int hsqp_loop_episodes_device(hsqp_handle* h, int32_t* d_state, int32_t* d_cause, int32_t* d_fail_cycle, int32_t* d_n_failures, int32_t* d_n_episodes) {
   return loop_episodes_impl(h, d_state, d_cause, d_fail_cycle, d_n_failures, d_n_episodes, true);
 }
+
+// ---- per-instance episode metrics (include/hsqp_metrics.h, csrc/hsqp_metrics.h)
+static int metrics_loop_ok(hsqp_handle* h, const char* who, bool made) {
+  if (h->hdm.formulation != HSQP_FORM_WB) return loop_bad(h, who, "whole-body handles only (the record reads the whole-body state row of the resident loop)");
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  if (made && !h->loop.metrics_made) return loop_bad(h, who, "no metrics since the loop was started (hsqp_loop_metrics_enable; every hsqp_loop_start turns them off)");
+  return HSQP_OK;
+}
+int hsqp_loop_metrics_enable(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_metrics_enable";
+  { const int rc = metrics_loop_ok(h, who, false); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Loop& L = h->loop;
+  const size_t B = L.B;
+  HCHECK(hipSetDevice(h->device));
+  L.metrics = false; L.metrics_made = false;
+  DEV_ENSURE(h->d_metrics, metrics_layout(Carve{}, L, B), "episode metrics");
+  metrics_layout(Carve{h->d_metrics.p}, L, B);
+  std::vector<hsqp_metrics> empty(2 * B);
+  for (hsqp_metrics& r : empty)
+    for (int i = 0; i < MET_WORDS; ++i) metrics_put_empty(&r, i);
+  StickyError step{h};
+  step(hipMemcpyAsync(L.met_rec, empty.data(), 2 * B * sizeof(hsqp_metrics), hipMemcpyHostToDevice, h->stream), "upload empty records");
+  step(hipMemsetAsync(L.met_feet, 0, 2 * B * sizeof(int), h->stream), "memset feet");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  L.metrics = true; L.metrics_made = true;
+  return HSQP_OK;
+}
+int hsqp_loop_metrics_disable(hsqp_handle* h) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  { const int rc = metrics_loop_ok(h, "hsqp_loop_metrics_disable", false); if (rc != HSQP_OK) return rc; }
+  h->loop.metrics = false;
+  return HSQP_OK;
+}
+int hsqp_loop_metrics_restart(hsqp_handle* h, int n, const int32_t* ids) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_metrics_restart";
+  { const int rc = metrics_loop_ok(h, who, true); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Loop& L = h->loop;
+  if (ids) { const int rc = loop_ids_ok(h, who, n, ids); if (rc != HSQP_OK) return rc; }
+  else n = L.B;
+  HCHECK(hipSetDevice(h->device));
+  StickyError step{h};
+  if (ids) step(hipMemcpyAsync(L.met_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream), "upload ids");
+  if (step.rc == HSQP_OK) {
+    HSQP_LAUNCH(k_metrics_host_close, dim3(n), dim3(64), 0, h->stream, ids ? (const int*)L.met_ids : (const int*)nullptr, L.met_rec, L.met_feet);
+    step(hipGetLastError(), "k_metrics_host_close");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+static int loop_metrics_impl(hsqp_handle* h, int which, hsqp_metrics* out, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_loop_metrics_device" : "hsqp_loop_metrics";
+  { const int rc = metrics_loop_ok(h, who, true); if (rc != HSQP_OK) return rc; }
+  if (which != HSQP_METRICS_CURRENT && which != HSQP_METRICS_PREVIOUS) return loop_bad(h, who, "which must be HSQP_METRICS_CURRENT or HSQP_METRICS_PREVIOUS");
+  if (!out) return loop_bad(h, who, "null out");
+  HCHECK(hipSetDevice(h->device));
+  // record `which` of every instance's pair into its own array [B]
+  HCHECK(hipMemcpy2DAsync(out, sizeof(hsqp_metrics), h->loop.met_rec + which, 2 * sizeof(hsqp_metrics), sizeof(hsqp_metrics), (size_t)h->loop.B,
+                          dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_loop_metrics(hsqp_handle* h, int which, hsqp_metrics* out) { return loop_metrics_impl(h, which, out, false); }
+int hsqp_loop_metrics_device(hsqp_handle* h, int which, hsqp_metrics* d_out) { return loop_metrics_impl(h, which, d_out, true); }
 
 int hsqp_last_kernel_ms(hsqp_handle* h, double out_ms[5]) {
   if (!h || !out_ms) return HSQP_ERR_BAD_ARG;

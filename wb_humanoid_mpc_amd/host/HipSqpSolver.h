@@ -19,6 +19,7 @@
 #include "../../include/hsqp_loop.h"
 #include "../../include/hsqp_gait.h"
 #include "../../include/hsqp_episode.h"
+#include "../../include/hsqp_metrics.h"
 #include "../../include/hsqp_push.h"
 #include "../../include/hsqp_plant.h"
 #include "../../include/hsqp_contact.h"
@@ -485,6 +486,30 @@ class HipSqpSolver {
     const int rc = hsqp_loop_episodes(h_, e.state.data(), e.cause.data(), e.failCycle.data(), e.nFailures.data(), e.nEpisodes.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_episodes failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     return e;
+  }
+
+  /** Episode metrics of the started loop (include/hsqp_metrics.h): one record per instance accumulated on the device behind every cycle's rollout,
+   *  cut at episode boundaries.  Off after every start of a loop. */
+  void enableLoopMetrics() {
+    const int rc = hsqp_loop_metrics_enable(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_metrics_enable failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** Accumulation stops; the records stay readable until the next start. */
+  void disableLoopMetrics() {
+    const int rc = hsqp_loop_metrics_disable(h_);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_metrics_disable failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** The records of the instances `ids` (empty: all) are closed with HSQP_METRICS_END_HOST and reopened; their episodes are untouched. */
+  void restartLoopMetrics(const std::vector<int32_t>& ids = {}) {
+    const int rc = hsqp_loop_metrics_restart(h_, (int)ids.size(), ids.empty() ? nullptr : ids.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_metrics_restart failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** The record of every instance: HSQP_METRICS_CURRENT (the open one) or HSQP_METRICS_PREVIOUS (the last closed one; empty: none). */
+  std::vector<hsqp_metrics> loopMetrics(int which = HSQP_METRICS_CURRENT) {
+    std::vector<hsqp_metrics> out(loopBatch_);
+    const int rc = hsqp_loop_metrics(h_, which, out.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_metrics failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return out;
   }
 
   const PrimalSolution& getPrimalSolution() const { return solution_; }

@@ -196,6 +196,12 @@ def load_library():
     lib.hsqp_loop_reset_instances.argtypes = [C.c_void_p, C.c_int, _ip, _dp, _dp]
     lib.hsqp_loop_episodes.argtypes = [C.c_void_p, _ip, _ip, _ip, _ip, _ip]
     lib.hsqp_loop_episodes_device.argtypes = [C.c_void_p, _ip, _ip, _ip, _ip, _ip]
+    _mp = C.POINTER(_abi.Metrics)
+    lib.hsqp_loop_metrics_enable.argtypes = [C.c_void_p]
+    lib.hsqp_loop_metrics_disable.argtypes = [C.c_void_p]
+    lib.hsqp_loop_metrics_restart.argtypes = [C.c_void_p, C.c_int, _ip]
+    lib.hsqp_loop_metrics.argtypes = [C.c_void_p, C.c_int, _mp]
+    lib.hsqp_loop_metrics_device.argtypes = [C.c_void_p, C.c_int, _mp]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -205,6 +211,32 @@ def load_library():
 
 def _c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def metrics_dict(rec):
+    """A ctypes array of hsqp_metrics ([B]) as a dict of numpy arrays, one per field."""
+    raw = np.frombuffer(bytes(rec), dtype=np.uint8).reshape(len(rec), C.sizeof(_abi.Metrics))
+    out = {}
+    for name, _ in _abi.Metrics._fields_:
+        f = getattr(_abi.Metrics, name)   # (the counts come first: every field in front of `duration` is int64)
+        words = np.ascontiguousarray(raw[:, f.offset:f.offset + f.size]).view(np.int64 if f.offset < _abi.Metrics.duration.offset else np.float64)
+        out[name] = words[:, 0].copy() if words.shape[1] == 1 else words.copy()
+    return out
+
+
+def metrics_summary(records, mass, gravity=9.81):
+    """What a batch of records (loop_metrics()) says as a whole: survivors (records still open with samples), RMS velocity tracking error over
+    all samples, mean straight-line distance, and the cost of transport work_pos / (m g |end - start|) over the instances that have torque
+    samples and moved (None: none did)."""
+    cycles = records["cycles"]
+    have = cycles > 0
+    dist = np.linalg.norm(records["end_xy"] - records["start_xy"], axis=1)
+    n = int(cycles.sum())
+    moved = have & (records["torque_samples"] > 0) & (dist > 0.0)
+    return dict(instances=int(cycles.shape[0]), survivors=int((have & (records["end_cause"] == _abi.METRICS_END_OPEN)).sum()), samples=n,
+                rms_tracking=float(np.sqrt(records["vel_err_sq"].sum() / n)) if n else None,
+                distance=float(dist[have].mean()) if have.any() else None,
+                cost_of_transport=float(records["work_pos"][moved].sum() / (mass * abs(gravity) * dist[moved].sum())) if moved.any() else None)
 
 
 class HipSqpSolver:
@@ -1085,6 +1117,43 @@ class HipSqpSolver:
     def loop_episodes_device(self, state_ptr=0, cause_ptr=0, fail_cycle_ptr=0, n_failures_ptr=0, n_episodes_ptr=0):
         icast = lambda a: C.cast(C.c_void_p(int(a)), C.POINTER(C.c_int32)) if a else None  # noqa: E731
         self._check(self.lib.hsqp_loop_episodes_device(self.h, icast(state_ptr), icast(cause_ptr), icast(fail_cycle_ptr), icast(n_failures_ptr), icast(n_episodes_ptr)))
+
+    # ---- include/hsqp_metrics.h: per-instance episode metrics accumulated on the device
+    def loop_metrics_enable(self):
+        """hsqp_loop_metrics_enable on the started loop: every record empty, one sample per instance behind every cycle's rollout from now on."""
+        self._check(self.lib.hsqp_loop_metrics_enable(self.h))
+
+    def loop_metrics_disable(self):
+        """hsqp_loop_metrics_disable: accumulation stops; the records stay readable until the next start."""
+        self._check(self.lib.hsqp_loop_metrics_disable(self.h))
+
+    def loop_metrics_restart(self, ids=None):
+        """hsqp_loop_metrics_restart: the records of the instances `ids` (None: all) are closed (END_HOST) and reopened; their episodes are untouched."""
+        if ids is None:
+            self._check(self.lib.hsqp_loop_metrics_restart(self.h, 0, None))
+            return
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        self._check(self.lib.hsqp_loop_metrics_restart(self.h, ids.shape[0], ids.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    @staticmethod
+    def _metrics_which(which):
+        return {"current": _abi.METRICS_CURRENT, "previous": _abi.METRICS_PREVIOUS}.get(which, which)
+
+    def loop_metrics(self, which="current"):
+        """hsqp_loop_metrics: the records of every instance ("current": the open one, "previous": the last closed one) as a dict of arrays, one
+        per field of hsqp_metrics ([B], touchdowns / start_xy / end_xy [B][2])."""
+        B = max(self._loop_batch, 1)
+        rec = (_abi.Metrics * B)()
+        self._check(self.lib.hsqp_loop_metrics(self.h, int(self._metrics_which(which)), rec))
+        return metrics_dict(rec)
+
+    def loop_metrics_device(self, which, out_ptr):
+        """hsqp_loop_metrics_device: the records [B] into device memory at the address out_ptr (B * sizeof(hsqp_metrics) bytes)."""
+        self._check(self.lib.hsqp_loop_metrics_device(self.h, int(self._metrics_which(which)), C.cast(C.c_void_p(int(out_ptr)), C.POINTER(_abi.Metrics))))
+
+    def metrics_summary(self, records):
+        """metrics_summary(records) with the model's total mass and gravity."""
+        return metrics_summary(records, self.model.total_mass, self.model.desc.gravity)
 
     # ---- include/hsqp_gait.h: per-instance gait schedule and ladder
     def gait_reset(self, settings, batch, t0=0.0):
