@@ -50,7 +50,8 @@
  * settings pointer, an unknown on_failure, NaN bounds, min_base_height > max_base_height, max_tilt < 0, a non-finite x_reset / x0 / v_cmd
  * (host arrays), n < 1, NULL ids, ids outside [0, B) or repeated, hsqp_loop_reset_instances / hsqp_loop_episodes without hsqp_loop_isolate.
  *
- * Out of scope: fall detection beyond the caller's box, per-instance loop time, centroidal handles, event grids, several GPUs.
+ * Out of scope: fall detection beyond the caller's box, per-instance loop time, centroidal handles, several GPUs.  (On the event-node
+ * grid of include/hsqp_grid.h an instance whose schedule overflows the grid stops the cycle for all: it is a fault of the schedule, not of an episode.)
  *
  * ABI: additions only — no public struct and no entry point of the other headers changes, HSQP_ABI_VERSION stays.
  */

@@ -46,7 +46,8 @@
  * the device, reported through the status words).
  *
  * Out of scope: the motion manager's BreakFrequencyAlphaFilter and command scaling, gait commands from a topic
- * (GaitScheduleUpdater::updateModeSequence), centroidal handles, event grids, several GPUs, reading gait.info in C++.
+ * (GaitScheduleUpdater::updateModeSequence), centroidal handles, several GPUs, reading gait.info in C++.  (Event grids: include/hsqp_grid.h
+ * builds the cycle's grid from this schedule on the device.)
  *
  * ABI: additions only — no public struct and no entry point of the other headers changes, HSQP_ABI_VERSION stays.
  */

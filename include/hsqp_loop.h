@@ -54,8 +54,9 @@
  * include/hsqp_gait.h: hsqp_loop_start_gait starts this loop with a per-instance gait schedule and ladder resident on the device.
  * The measured state x of steps 1 and 2 IS the plant's state unless include/hsqp_observe.h says otherwise: a resident observation model (bias,
  * noise, sensor and compute delay) between the plant's state and everything the MPC reads; with none set the cycle is exactly the one above.
- * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, event grids (hsqp_reference::node_times), the
- * centroidal formulation, several GPUs.
+ * The uniform grid of step 2 is the default: include/hsqp_grid.h switches the started loop to ocs2's event-node grid (hsqp_reference::node_times),
+ * built per instance on the device in every cycle.
+ * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, the centroidal formulation, several GPUs.
  *
  * ABI: additions only — no public struct and no entry point of hsqp.h, hsqp_feedback.h or hsqp_rollout.h changes, HSQP_ABI_VERSION stays.
  */

@@ -59,6 +59,10 @@ closed, of the last closed one) and the line carries `metrics`: the summary over
 the share of torque samples in saturation.  With --terrain the final base position, and with --actuator `saturated_share` (then: the share of the
 instances with a saturated sample anywhere in their records), come from the records instead of from logs and the last actuator record.  Opt-in: without
 the flag the tool's output is what it was.
+--event-grid [EVENT_NODES]: hsqp_loop_event_grid (include/hsqp_grid.h) behind the start: every cycle builds the ocs2 event-node grid of every instance on
+the device and solves on nodes + EVENT_NODES intervals (default 32; the handle is created with that many nodes).  The line carries `event_grid`: the
+settings and the range of the instances' own interval counts in the last cycle.  --schedule walk | run: the gait of the uploaded schedules (run has
+twice the events per second).  Opt-in: without the flags the tool's output is what it was.
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -286,6 +290,8 @@ def main():
     ap.add_argument("--compute-delay", type=int, default=1)
     ap.add_argument("--obs-seed", type=int, default=2026)
     ap.add_argument("--metrics", action="store_true")
+    ap.add_argument("--event-grid", type=int, nargs="?", const=32, default=None, metavar="EVENT_NODES")
+    ap.add_argument("--schedule", default="walk", choices=("walk", "run"))
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -354,7 +360,7 @@ def timed_run(args, observe):
     m = load_model()
     B, N, dt = args.batch, args.nodes, m.sqp["dt"]
     t_final = (2 * args.warmup + 2 * args.cycles) * args.period + N * dt + 1.0
-    schedules = [tile_gait(m.gaits["walk"], 0.3 + 0.5 * b / B, t_final) for b in range(B)]
+    schedules = [tile_gait(m.gaits[args.schedule], 0.3 + 0.5 * b / B, t_final) for b in range(B)]
     knots = velocity_command_targets(m, (0.3, 0.0, 0.7925, 0.0), 0.0, m.initial_state, t_final)
     n_events, event_times, mode_sequence = pack_reference(schedules, [knots] * B)[:3]
     rng = np.random.default_rng(20250808)
@@ -364,7 +370,7 @@ def timed_run(args, observe):
     if args.commands == "spread":
         cmd[:, 0] = np.linspace(0.0, 0.6, B)
         cmd[:, 3] = np.linspace(-0.2, 0.2, B)
-    s = HipSqpSolver(m, max_nodes=N, max_batch=B, linesearch=True)
+    s = HipSqpSolver(m, max_nodes=N + (args.event_grid or 0), max_batch=B, linesearch=True)
     s.set_scan_backoff_persistent(True)
     st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True,
                          controller=args.controller)
@@ -407,6 +413,8 @@ def timed_run(args, observe):
             s.set_terrain_instances(place)
         if args.metrics:
             s.loop_metrics_enable()
+        if args.event_grid is not None:
+            s.loop_event_grid(s.grid_settings(event_nodes=args.event_grid))
         last_pos = x_init[:, :3].copy()
         masses = None
         if args.inertia:
@@ -443,6 +451,7 @@ def timed_run(args, observe):
                 have = r["cycles"] > 0
                 last_pos[have, :2] = r["end_xy"][have]
         probe = rollout_probe(s, args, x_end) if args.plant else None
+        counts = s.loop_grid()["n_intervals"] if args.event_grid is not None else None
     finally:
         s.close()
     heights = np.concatenate(heights)
@@ -467,6 +476,8 @@ def timed_run(args, observe):
         for b in range(B):
             print(f"instance {b}: total mass {masses[b]:.3f} kg, finished {'yes' if finished[b] else 'no'}")
     extra = {"metrics": metrics} if args.metrics else {}
+    if args.event_grid is not None:
+        extra["event_grid"] = dict(event_nodes=args.event_grid, schedule=args.schedule, intervals=N + args.event_grid, n_intervals_range=[int(counts.min()), int(counts.max())])
     return dict({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
                       "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "gait": args.gait, "instances_per_rung": rungs, "isolate": args.isolate, "with_push": args.with_push,
                       "plant": dict(kind=args.plant, kp=args.kp, kd=args.kd, armature=args.armature, lookahead=args.lookahead) if args.plant else None,

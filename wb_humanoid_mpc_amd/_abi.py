@@ -276,6 +276,17 @@ OBSERVE_ENTRY_POINTS = ("hsqp_observe_defaults", "hsqp_observe_instance_defaults
                         "hsqp_observe_set_instances_device", "hsqp_observe_clear", "hsqp_observe_get", "hsqp_observe_eval", "hsqp_observe_eval_device",
                         "hsqp_observe_last", "hsqp_observe_last_device")
 
+# include/hsqp_grid.h
+GRID_OK, GRID_OVERFLOW = 0, 1
+
+
+class GridSettings(C.Structure):   # hsqp_grid_settings
+    _fields_ = [("event_nodes", C.c_int32), ("reserved", C.c_int32), ("dt_min", C.c_double)]
+
+
+# entry points of include/hsqp_grid.h (tests/test_grid.py checks that the library exports each of them and the binding declares it)
+GRID_ENTRY_POINTS = ("hsqp_grid_defaults", "hsqp_event_grid", "hsqp_event_grid_device", "hsqp_loop_event_grid", "hsqp_loop_grid", "hsqp_loop_grid_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

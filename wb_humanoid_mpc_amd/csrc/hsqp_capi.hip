@@ -24,6 +24,7 @@
 #include "hsqp_loop.h"
 #include "../../include/hsqp_loop.h"
 #include "hsqp_gait.h"
+#include "hsqp_grid.h"
 #include "hsqp_episode.h"
 #include "hsqp_metrics.h"
 #include "hsqp_observe.h"
@@ -820,6 +821,25 @@ __global__ __launch_bounds__(64) void k_gait_update(const hsqp_gait_settings* __
   if (threadIdx.x == 0) status[b] = st;
 }
 
+// ---- the event-node time grid (hsqp_grid.h): the recurrence is serial and a few flops per node, so one LANE per instance, 64 instances per workgroup.
+// An instance reads its own events and writes its own rows (dt_nodes, node_times, n_intervals, status); `any_bad` (may be null) is set, never cleared,
+// by an instance that fails; dts_keep (may be null): a second copy of the instance's interval lengths (the loop's record of the cycle)
+__global__ __launch_bounds__(64) void k_event_grid(double t0, int n_nodes, double dt, double dt_min, int event_nodes, int B, int max_events,
+                                                   const int* __restrict__ n_events, const double* __restrict__ event_times, int* __restrict__ n_intervals,
+                                                   double* __restrict__ dts, double* __restrict__ nts, int* __restrict__ status, int* any_bad,
+                                                   double* __restrict__ dts_keep) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const size_t N = (size_t)n_nodes + event_nodes;
+  int nb = 0;
+  const int st = grid_build_instance(t0, n_nodes, dt, dt_min, event_nodes, max_events, n_events[b], event_times + (size_t)b * max_events, &nb, dts + (size_t)b * N,
+                                     nts + (size_t)b * (N + 1));
+  n_intervals[b] = nb;
+  if (status) status[b] = st;
+  if (st != HSQP_GRID_OK && any_bad) *any_bad = 1;
+  if (dts_keep) for (size_t k = 0; k < N; ++k) dts_keep[(size_t)b * N + k] = dts[(size_t)b * N + k];
+}
+
 // ---- failure isolation and episode reset of the resident loop (hsqp_episode.h): one wave per instance
 __global__ __launch_bounds__(64) void k_loop_triage(TriageArgs a) { triage_instance(Ctx{(int)threadIdx.x, 64, nullptr}, a, blockIdx.x); }
 // step 0 of a cycle with the observation model in force, and hsqp_observe_eval (include/hsqp_observe.h, csrc/hsqp_observe.h): OBS_THREADS items
@@ -1258,6 +1278,14 @@ struct hsqp_handle {
     double* obs_ring = nullptr; double* obs_y[2] = {nullptr, nullptr};
     bool obs_last = false;
     double obs_tp = 0.0;
+    // the event-node grid (include/hsqp_grid.h): off after every start.  In d_grid (grid_layout): two records of (n_intervals [B], dt_nodes [B][N],
+    // node_times [B][N + 1]) — a cycle builds into grid_rec[grid_cur ^ 1], which becomes grid_rec[grid_cur] when the cycle completes — the status words and
+    // the one word the cycle reads back.  grid_have: grid_rec[grid_cur] is the grid of the last completed cycle
+    bool grid = false, grid_have = false;
+    hsqp_grid_settings grid_st = {};
+    int grid_cur = 0;
+    struct GridRec { int* ni; double* dts; double* nts; } grid_rec[2] = {};
+    int* grid_status = nullptr; int* grid_bad = nullptr;
   } loop;
   // the resident gait state (include/hsqp_gait.h): two copies in d_gait (gait_layout), s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
   struct Gait {
@@ -1269,7 +1297,8 @@ struct hsqp_handle {
     int* status = nullptr; int* ne = nullptr; int* seq = nullptr;
     double* ev = nullptr; double* v = nullptr; double* x = nullptr;
   } gait;
-  DevBuf<char> d_gait, d_episode, d_metrics;
+  DevBuf<char> d_gait, d_episode, d_metrics, d_grid;
+  DevBuf<char> d_grid_stage;      // staging of hsqp_event_grid's host arrays (grid_stage_layout)
   DevBuf<char> d_loop, d_loop_log;   // the loop's resident arrays; staging of hsqp_loop_run's host logs and of hsqp_command_targets' host arrays
   double kernel_ms[5] = {0, 0, 0, 0, 0};
   int last_iterations = 0;
@@ -1358,6 +1387,17 @@ static size_t metrics_layout(Carve c, hsqp_handle::Loop& L, size_t B) {
   L.met_rec = c.take<hsqp_metrics>(2 * B); L.met_steps = c.take<int32_t>(B); L.met_rejected = c.take<int32_t>(B);
   L.met_feet = c.take<int>(2 * B); L.met_ids = c.take<int>(B);
   return c.bytes();
+}
+// d_grid: the loop's two grid records, the status words of a cycle's build, the word the cycle reads back
+static size_t grid_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t N) {
+  for (auto& r : L.grid_rec) r = {c.take<int>(B), c.take<double>(B * N), c.take<double>(B * (N + 1))};
+  L.grid_status = c.take<int>(B); L.grid_bad = c.take<int>(1);
+  return c.bytes();
+}
+// d_grid_stage, hsqp_event_grid (host arrays): n_events [B], event_times [B][E] | n_intervals [B], status [B], dt_nodes [B][N], node_times [B][N + 1]
+struct GridStage { int* ne; int* ni; int* status; double* ev; double* dts; double* nts; size_t bytes; };
+static GridStage grid_stage_layout(Carve c, size_t B, size_t N, size_t E, bool host) {
+  return {c.take<int>(B, host), c.take<int>(B, host), c.take<int>(B), c.take<double>(B * E, host), c.take<double>(B * N, host), c.take<double>(B * (N + 1), host), c.bytes()};
 }
 // d_observe: the loop's ring of plant states (absent without a delay) and the observations of the even and the odd cycles
 static size_t observe_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t slots) {
@@ -1807,6 +1847,7 @@ struct RefDev {
   hsqp_swing_config swing; double terrain_height; int arm_swing, warm, N_prev;
   bool sorted;
   const int* warm_b = nullptr;     // [B] HSQP_WARM_SHIFT / _COLD per instance (the isolated loop; `warm` is then SHIFT), or null: `warm` for all
+  const int* grid_bad = nullptr;   // one int the builder of a device-built grid has set if an instance has none (the loop on the event grid), or null
 };
 
 // The device side of hsqp_upload_reference, behind the copies `step` has queued on the stream (x_init in d_xinit, the grid in d_dt, the CALLER warm start
@@ -1832,10 +1873,12 @@ static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& 
     HSQP_LAUNCH(k_warm_start, dim3((unsigned)((N + 1 + WARM_WAVES - 1) / WARM_WAVES), (unsigned)B), dim3(64 * WARM_WAVES), lds, h->stream, w);
     step(hipGetLastError(), "k_warm_start");
   }
-  int bad = 0;
+  int bad = 0, grid_bad = 0;
   step(hipMemcpyAsync(&bad, r.bad, 4, hipMemcpyDeviceToHost, h->stream), "download status");
+  if (r.grid_bad) step(hipMemcpyAsync(&grid_bad, r.grid_bad, 4, hipMemcpyDeviceToHost, h->stream), "download grid status");
   step(hipStreamSynchronize(h->stream), "sync");
   if (step.rc != HSQP_OK) return step.rc;
+  if (grid_bad) return HSQP_ERR_BAD_ARG;   // (the caller reads the instances' status words and writes the message)
   if (bad) { h->err = "a swing phase has no lift-off / touch-down inside the mode schedule"; return HSQP_ERR_BAD_ARG; }
   h->stamps_cur = 1 - h->stamps_cur;
   commit_problem(h, p, r.sorted);
@@ -3313,6 +3356,7 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
   L.obs_last = false;
   L.isolate = false;
   L.metrics = false; L.metrics_made = false;
+  L.grid = false; L.grid_have = false;
   L.gait = gait != nullptr;
   L.started = true;
   return HSQP_OK;
@@ -3562,6 +3606,26 @@ static int loop_metrics_cycle(hsqp_handle* h) {
   return HSQP_OK;
 }
 
+// the first instance of `batch` status words (device) that has no grid, into h->err; HSQP_OK if every instance has one
+static int grid_status_check(hsqp_handle* h, const char* who, const int* d_status, int batch, int n_nodes, int event_nodes) {
+  std::vector<int> status(batch);
+  HCHECK(hipMemcpy(status.data(), d_status, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  for (int b = 0; b < batch; ++b)
+    if (status[b] != HSQP_GRID_OK)
+      return loop_bad(h, who, ("event grid of instance " + std::to_string(b) + ": it needs more than n_nodes + event_nodes = " + std::to_string(n_nodes) + " + " +
+                               std::to_string(event_nodes) + " intervals (or its event times admit no grid)").c_str());
+  return HSQP_OK;
+}
+// step 2 of a cycle on the event grid has failed with rc: if the builder refused an instance that is the failure (the status words are read only here)
+static int loop_grid_failure(hsqp_handle* h, const char* who, int rc) {
+  const hsqp_handle::Loop& L = h->loop;
+  const std::string err = h->err;
+  const int g = grid_status_check(h, who, L.grid_status, L.B, L.st.n_nodes, L.grid_st.event_nodes);
+  if (g == HSQP_ERR_BAD_ARG) return g;
+  h->err = err;
+  return rc;
+}
+
 static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   hsqp_handle::Loop& L = h->loop;
   const hsqp_loop_settings& st = L.st;
@@ -3573,8 +3637,11 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   const double lag = obs ? observe_policy_time(h->observe.compute_delay, st.period) : 0.0;
   const double tp = obs ? observe_problem_time(L.t, lag) : L.t;
   const double* xm = obs ? L.obs_y[L.cycle & 1] : L.x;
+  // the event-node grid (include/hsqp_grid.h): N = n_nodes + event_nodes intervals, built into the shadow record behind the gait update
+  const bool grid = L.grid;
+  const hsqp_handle::Loop::GridRec* gr = grid ? &L.grid_rec[L.grid_cur ^ 1] : nullptr;
   hsqp_problem p{};
-  p.batch = L.B; p.n_nodes = st.n_nodes; p.dt = st.dt; p.x_init = xm;
+  p.batch = L.B; p.n_nodes = grid ? st.n_nodes + L.grid_st.event_nodes : st.n_nodes; p.dt = st.dt; p.x_init = xm;
   // step 2's checks come first, as in hsqp_upload_reference: a rejected cycle leaves the resident solution as it was
   h->have_policy = false;
   const int N_prev = h->N;
@@ -3606,12 +3673,22 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   }
   // 2. hsqp_upload_reference's work on the resident arrays
   h->have_problem = false; h->have_solution = false; h->have_stamps = false;
-  { const int rc = set_grid(h, &p, false); if (rc != HSQP_OK) return rc; }
+  if (grid) {   // the grid of every instance from this cycle's schedule, into d_dt and the shadow record; set_grid's part is the builder's
+    h->uniform_grid = false; h->grid_resident = false; h->has_events = true;
+    step(hipMemsetAsync(L.grid_bad, 0, 4, h->stream), "memset");
+    HSQP_LAUNCH(k_event_grid, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, tp, st.n_nodes, st.dt, L.grid_st.dt_min, L.grid_st.event_nodes, L.B, L.E, (const int*)L.ne,
+                (const double*)L.ev, gr->ni, (double*)h->d_dt, gr->nts, L.grid_status, L.grid_bad, gr->dts);
+    step(hipGetLastError(), "k_event_grid");
+  } else {
+    const int rc = set_grid(h, &p, false); if (rc != HSQP_OK) return rc;
+  }
   step(hipMemsetAsync(L.bad, 0, 4, h->stream), "memset");
   step(hipMemcpyAsync(h->d_xinit, xm, B * NX * 8, hipMemcpyDeviceToDevice, h->stream), "copy x_init");
-  RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, nullptr, L.bad, tp, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
+  RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, grid ? gr->nts : nullptr, L.bad, tp, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
   if (iso && warm == HSQP_WARM_SHIFT) rd.warm_b = L.ep.mode;
-  { const int rc = reference_build(h, &p, rd, step); if (rc != HSQP_OK) return rc; }
+  if (grid) rd.grid_bad = L.grid_bad;
+  { const int rc = reference_build(h, &p, rd, step);
+    if (rc != HSQP_OK) return grid ? loop_grid_failure(h, "hsqp_loop_run", rc) : rc; }
   // 3. the iteration
   { const int rc = hsqp_iterate_device(h, st.iterations, st.iterate_flags); if (rc != HSQP_OK) return rc; }
   // 4. the plant under the policy over one period, from its true state (with the model in force at s0 = compute_delay periods in the policy's frame)
@@ -3635,6 +3712,8 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
     HCHECK(hipGetLastError());
   }
   if (obs) { L.obs_last = true; L.obs_tp = tp; }
+  if (grid) L.grid_cur ^= 1;   // the shadow record is the completed cycle's
+  L.grid_have = grid;
   ++L.cycle;
   L.have_cycle = true;
   return HSQP_OK;
@@ -3681,6 +3760,10 @@ static int loop_run_impl(hsqp_handle* h, int n_cycles, double* x_log, double* u_
     if (x_log) step(hipMemcpyAsync(x_log, d_xl, done * nx * 8, hipMemcpyDeviceToHost, h->stream), "download x_log");
     if (u_log) step(hipMemcpyAsync(u_log, d_ul, done * nu * 8, hipMemcpyDeviceToHost, h->stream), "download u_log");
   }
+  if (h->loop.grid && !h->uniform_grid) {   // the host copy of the resident problem's device-built grid (debug reads), once per run
+    h->h_dt.resize(B * (size_t)(h->loop.st.n_nodes + h->loop.grid_st.event_nodes));
+    step(hipMemcpyAsync(h->h_dt.data(), h->d_dt, h->h_dt.size() * 8, hipMemcpyDeviceToHost, h->stream), "download dt_nodes");
+  }
   step(hipStreamSynchronize(h->stream), "sync");
   if (rc != HSQP_OK) { h->err = err; return rc; }
   return step.rc;
@@ -3704,6 +3787,120 @@ static int loop_state_impl(hsqp_handle* h, double* t, double* x, double* v_filt,
 }
 int hsqp_loop_state(hsqp_handle* h, double* t, double* x, double* v_filt) { return loop_state_impl(h, t, x, v_filt, false); }
 int hsqp_loop_state_device(hsqp_handle* h, double* t, double* d_x, double* d_v_filt) { return loop_state_impl(h, t, d_x, d_v_filt, true); }
+
+// ---- the event-node time grid (include/hsqp_grid.h, csrc/hsqp_grid.h): the stand-alone builder, the loop's switch, the loop's last grid
+void hsqp_grid_defaults(hsqp_grid_settings* s) {
+  if (!s) return;
+  memset(s, 0, sizeof(*s));
+  s->event_nodes = 32;
+  s->dt_min = 1e-4;   // HipSqpSolverAdaptor's dtMin
+}
+
+// what every grid entry point asks of (settings, n_nodes, dt) on handle h
+static int grid_settings_ok(hsqp_handle* h, const char* who, const hsqp_grid_settings* gs, int n_nodes, double dt) {
+  if (!gs) return loop_bad(h, who, "null settings");
+  if (gs->reserved != 0) return loop_bad(h, who, "hsqp_grid_settings::reserved must be 0");
+  if (gs->event_nodes < 0) return loop_bad(h, who, "hsqp_grid_settings::event_nodes < 0");
+  if (!std::isfinite(gs->dt_min) || gs->dt_min < 0.0) return loop_bad(h, who, "hsqp_grid_settings::dt_min not finite and >= 0");
+  if (!std::isfinite(dt) || !(dt > gs->dt_min)) return loop_bad(h, who, ("dt = " + std::to_string(dt) + " must be finite and > hsqp_grid_settings::dt_min = " + std::to_string(gs->dt_min)).c_str());
+  if (n_nodes < 1) return loop_bad(h, who, "n_nodes < 1");
+  if ((long long)n_nodes + gs->event_nodes > h->st.max_nodes)
+    return loop_bad(h, who, ("n_nodes + hsqp_grid_settings::event_nodes = " + std::to_string(n_nodes) + " + " + std::to_string(gs->event_nodes) + " exceeds max_nodes = " +
+                             std::to_string(h->st.max_nodes)).c_str());
+  return HSQP_OK;
+}
+
+static int event_grid_impl(hsqp_handle* h, const hsqp_grid_settings* gs, int batch, double t0, int n_nodes, double dt, int max_events, const int32_t* ne, const double* ev,
+                           int32_t* ni, double* dts, double* nts, int32_t* status, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_event_grid_device" : "hsqp_event_grid";
+  { const int rc = grid_settings_ok(h, who, gs, n_nodes, dt); if (rc != HSQP_OK) return rc; }
+  if (!ne || !ev || !ni || !dts || !nts) return loop_bad(h, who, "null array");
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (max_events < 1) return loop_bad(h, who, "max_events < 1");
+  if (!std::isfinite(t0)) return loop_bad(h, who, "t0 not finite");
+  const size_t B = batch, E = max_events, N = (size_t)n_nodes + gs->event_nodes;
+  if (!dev)
+    for (size_t b = 0; b < B; ++b) {
+      if (ne[b] < 0 || ne[b] > max_events) return loop_bad(h, who, ("n_events of instance " + std::to_string(b) + " outside [0, max_events]").c_str());
+      for (int i = 0; i < ne[b]; ++i)
+        if (!std::isfinite(ev[b * E + i]) || (i > 0 && ev[b * E + i] < ev[b * E + i - 1]))
+          return loop_bad(h, who, ("event_times of instance " + std::to_string(b) + ": entry " + std::to_string(i) + " is not finite or lies before the entry in front of it").c_str());
+    }
+  HCHECK(hipSetDevice(h->device));
+  DEV_ENSURE(h->d_grid_stage, grid_stage_layout(Carve{}, B, N, E, !dev).bytes, "event grid staging");
+  const GridStage sg = grid_stage_layout(Carve{h->d_grid_stage.p}, B, N, E, !dev);
+  StickyError step{h};
+  if (!dev) {
+    step(hipMemcpyAsync(sg.ne, ne, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
+    step(hipMemcpyAsync(sg.ev, ev, B * E * 8, hipMemcpyHostToDevice, h->stream), "upload event_times");
+  }
+  if (step.rc == HSQP_OK) {
+    HSQP_LAUNCH(k_event_grid, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, t0, n_nodes, dt, gs->dt_min, gs->event_nodes, batch, max_events,
+                dev ? (const int*)ne : (const int*)sg.ne, dev ? ev : (const double*)sg.ev, dev ? (int*)ni : sg.ni, dev ? dts : sg.dts, dev ? nts : sg.nts, sg.status, (int*)nullptr,
+                (double*)nullptr);
+    step(hipGetLastError(), "k_event_grid");
+  }
+  if (!dev) {
+    step(hipMemcpyAsync(ni, sg.ni, B * 4, hipMemcpyDeviceToHost, h->stream), "download n_intervals");
+    step(hipMemcpyAsync(dts, sg.dts, B * N * 8, hipMemcpyDeviceToHost, h->stream), "download dt_nodes");
+    step(hipMemcpyAsync(nts, sg.nts, B * (N + 1) * 8, hipMemcpyDeviceToHost, h->stream), "download node_times");
+  }
+  if (status) step(hipMemcpyAsync(status, sg.status, B * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream), "download status");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  return grid_status_check(h, who, sg.status, batch, n_nodes, gs->event_nodes);
+}
+int hsqp_event_grid(hsqp_handle* h, const hsqp_grid_settings* settings, int batch, double t0, int n_nodes, double dt, int max_events, const int32_t* n_events,
+                    const double* event_times, int32_t* n_intervals, double* dt_nodes, double* node_times, int32_t* status) {
+  return event_grid_impl(h, settings, batch, t0, n_nodes, dt, max_events, n_events, event_times, n_intervals, dt_nodes, node_times, status, false);
+}
+int hsqp_event_grid_device(hsqp_handle* h, const hsqp_grid_settings* settings, int batch, double t0, int n_nodes, double dt, int max_events,
+                           const int32_t* d_n_events, const double* d_event_times, int32_t* d_n_intervals, double* d_dt_nodes, double* d_node_times,
+                           int32_t* d_status) {
+  return event_grid_impl(h, settings, batch, t0, n_nodes, dt, max_events, d_n_events, d_event_times, d_n_intervals, d_dt_nodes, d_node_times, d_status, true);
+}
+
+int hsqp_loop_event_grid(hsqp_handle* h, const hsqp_grid_settings* gs) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_event_grid";
+  { const int rc = loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Loop& L = h->loop;
+  if (!gs) { L.grid = false; return HSQP_OK; }   // (the record of the last completed cycle stays readable until a cycle on the uniform grid completes)
+  { const int rc = grid_settings_ok(h, who, gs, L.st.n_nodes, L.st.dt); if (rc != HSQP_OK) return rc; }
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = L.B, N = (size_t)L.st.n_nodes + gs->event_nodes;
+  const bool same = L.grid_have && L.grid_st.event_nodes == gs->event_nodes;   // the records keep their place: the completed cycle's grid stays
+  DEV_ENSURE(h->d_grid, grid_layout(Carve{}, L, B, N), "loop grid records");
+  grid_layout(Carve{h->d_grid.p}, L, B, N);
+  if (!same) { L.grid_have = false; L.grid_cur = 0; }
+  L.grid_st = *gs;
+  L.grid = true;
+  return HSQP_OK;
+}
+
+static int loop_grid_impl(hsqp_handle* h, int32_t* ni, double* dts, double* nts, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_loop_grid_device" : "hsqp_loop_grid";
+  { const int rc = loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  const hsqp_handle::Loop& L = h->loop;
+  if (!L.grid_have) return loop_bad(h, who, "the last completed cycle did not run on the event grid (hsqp_loop_event_grid, then hsqp_loop_run)");
+  HCHECK(hipSetDevice(h->device));
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t B = L.B, N = (size_t)L.st.n_nodes + L.grid_st.event_nodes;
+  const hsqp_handle::Loop::GridRec& r = L.grid_rec[L.grid_cur];
+  if (ni) HCHECK(hipMemcpyAsync(ni, r.ni, B * 4, kind, h->stream));
+  if (dts) HCHECK(hipMemcpyAsync(dts, r.dts, B * N * 8, kind, h->stream));
+  if (nts) HCHECK(hipMemcpyAsync(nts, r.nts, B * (N + 1) * 8, kind, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_loop_grid(hsqp_handle* h, int32_t* n_intervals, double* dt_nodes, double* node_times) { return loop_grid_impl(h, n_intervals, dt_nodes, node_times, false); }
+int hsqp_loop_grid_device(hsqp_handle* h, int32_t* d_n_intervals, double* d_dt_nodes, double* d_node_times) {
+  return loop_grid_impl(h, d_n_intervals, d_dt_nodes, d_node_times, true);
+}
 
 // ---- the observation model of the loop (include/hsqp_observe.h, csrc/hsqp_observe.h): the resident settings and table, the evaluation, the last observation
 void hsqp_observe_defaults(hsqp_observe_settings* s) { if (s) memset(s, 0, sizeof(*s)); }

@@ -9,6 +9,7 @@
 // ocs2::SolverBase and owns one of these is shown in INTEGRATION.md.  Failures map to std::runtime_error, which is
 // what the reference's MPC thread expects from its solver (WBMpcMrtJointController.cpp:210-213).
 #pragma once
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -20,6 +21,7 @@
 #include "../../include/hsqp_gait.h"
 #include "../../include/hsqp_episode.h"
 #include "../../include/hsqp_metrics.h"
+#include "../../include/hsqp_grid.h"
 #include "../../include/hsqp_push.h"
 #include "../../include/hsqp_plant.h"
 #include "../../include/hsqp_contact.h"
@@ -424,6 +426,7 @@ class HipSqpSolver {
     const int rc = hsqp_loop_start(h_, &st, (int)B, t0, x0.data(), velocityCommands.data(), maxEvents, nEvents.data(), eventTimes.data(), modeSequence.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_start failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     loopBatch_ = B;
+    loopNodes_ = (size_t)st.n_nodes; gridNodes_ = 0;
     shiftable_ = false;   // (the loop owns the resident problem until the next run* call ends it)
   }
   /** startLoop with the per-instance gait schedule and ladder resident on the device (include/hsqp_gait.h) in place of uploaded schedules: every
@@ -436,6 +439,7 @@ class HipSqpSolver {
     const int rc = hsqp_loop_start_gait(h_, &st, &gait, (int)B, t0, x0.data(), velocityCommands.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_start_gait failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     loopBatch_ = B;
+    loopNodes_ = (size_t)st.n_nodes; gridNodes_ = 0;
     shiftable_ = false;
   }
   /** New commands [batch][4]; in effect from the next cycle. */
@@ -512,6 +516,38 @@ class HipSqpSolver {
     return out;
   }
 
+  /** The padded ocs2 event-node grid of a batch (include/hsqp_grid.h), built on the device: interval lengths [batch][N], sampling times [batch][N + 1]
+   *  (what hsqp_problem::dt_nodes and hsqp_reference::node_times take) and the intervals of every instance's own grid, N = nNodes + settings.event_nodes. */
+  struct EventGrid { std::vector<int32_t> nIntervals; std::vector<double> dtNodes, nodeTimes; };
+  hsqp_grid_settings gridDefaults() const { hsqp_grid_settings st; hsqp_grid_defaults(&st); return st; }
+  EventGrid eventGrid(const hsqp_grid_settings& settings, double t0, int nNodes, double dt, int maxEvents, const std::vector<int32_t>& nEvents,
+                      const std::vector<double>& eventTimes) {
+    const size_t B = nEvents.size(), N = (size_t)std::max(nNodes + settings.event_nodes, 0);
+    if (B == 0 || maxEvents < 1 || eventTimes.size() != B * (size_t)maxEvents) throw std::runtime_error("[HipSqpSolver] eventGrid: inconsistent array sizes");
+    EventGrid g;
+    g.nIntervals.assign(B, 0); g.dtNodes.assign(B * N, 0.0); g.nodeTimes.assign(B * (N + 1), 0.0);
+    const int rc = hsqp_event_grid(h_, &settings, (int)B, t0, nNodes, dt, maxEvents, nEvents.data(), eventTimes.data(), g.nIntervals.data(), g.dtNodes.data(),
+                                   g.nodeTimes.data(), nullptr);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_event_grid failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return g;
+  }
+  /** The started loop on the event-node grid from its next cycle on (settings == nullptr: back to the uniform grid).  Off after every start. */
+  void setLoopEventGrid(const hsqp_grid_settings* settings) {
+    const int rc = hsqp_loop_event_grid(h_, settings);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_event_grid failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    if (settings) gridNodes_ = loopNodes_ + (size_t)settings->event_nodes;
+  }
+  /** The grid of the loop's last completed cycle, which ran on the event grid. */
+  EventGrid loopGrid() {
+    const size_t B = loopBatch_, N = gridNodes_;
+    if (B == 0 || N == 0) throw std::runtime_error("[HipSqpSolver] loopGrid: no loop on the event grid (startLoop, setLoopEventGrid)");
+    EventGrid g;
+    g.nIntervals.assign(B, 0); g.dtNodes.assign(B * N, 0.0); g.nodeTimes.assign(B * (N + 1), 0.0);
+    const int rc = hsqp_loop_grid(h_, g.nIntervals.data(), g.dtNodes.data(), g.nodeTimes.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_grid failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return g;
+  }
+
   const PrimalSolution& getPrimalSolution() const { return solution_; }
   const std::vector<hsqp_perf>& getPerformanceIndeces() const { return perf_; }
   const std::vector<hsqp_perf>& getPerformanceIndecesBeforeStep() const { return perfBefore_; }
@@ -581,6 +617,8 @@ class HipSqpSolver {
   int iterations_ = 0;
   bool reportKkt_ = false;
   size_t loopBatch_ = 0;     // instances of the started loop (startLoop)
+  size_t loopNodes_ = 0;     // its n_nodes
+  size_t gridNodes_ = 0;     // n_nodes + event_nodes of its last setLoopEventGrid (0: none since the start)
   bool shiftable_ = false;   // the handle holds the solution of a runWithReference / runRecedingHorizon: the next runRecedingHorizon shifts it
 };
 

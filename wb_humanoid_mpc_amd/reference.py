@@ -336,6 +336,61 @@ def event_grid(t0, tf, dt, event_times):
     return np.diff(times), times + EVENT_EPS * post
 
 
+class GridOverflow(RuntimeError):
+    """padded_event_grid: the ocs2 grid needs more than n_nodes + event_nodes intervals (HSQP_GRID_OVERFLOW), or the events admit no grid."""
+
+
+def padded_event_grid(t0, n_nodes, dt, event_times, event_nodes, dt_min=1e-4):
+    """The Python mirror of csrc/hsqp_grid.h (include/hsqp_grid.h), operation by operation: event_grid(t0, t0 + n_nodes * dt, dt, events) with the
+    builder's bounded loop, padded to N = n_nodes + event_nodes intervals by N - N_b zero-length intervals directly in front of the last interval
+    (the padding nodes duplicate node N_b - 1, its sampling time included).  Returns (dts[N], node_times[N + 1], n_intervals = N_b); raises
+    GridOverflow where the device answers HSQP_GRID_OVERFLOW."""
+    N = int(n_nodes) + int(event_nodes)
+    t0, dt, dt_min = float(t0), float(dt), float(dt_min)
+    ev = [float(e) for e in event_times]
+    tf = t0 + n_nodes * dt
+    dts, nts = [0.0] * N, [0.0] * (N + 1)
+    n, ie, last, prev, last_post = 1, 0, t0, t0, False
+    nts[0] = t0
+    cap, passes = N + len(ev) + 2, 0
+    while last < tf:
+        passes += 1
+        if passes > cap:
+            raise GridOverflow("the grid's loop does not end")
+        while ie < len(ev) and not (t0 < ev[ie] and ev[ie] < tf):
+            ie += 1
+        t_next, is_event = last + dt, False
+        if ie < len(ev) and t_next >= ev[ie]:
+            t_next, is_event = ev[ie], True
+            ie += 1
+        if t_next >= tf:
+            t_next, is_event = tf, False
+        if t_next > last + dt_min or last_post:
+            if n > N:
+                raise GridOverflow("more than %d intervals" % N)
+            nts[n], dts[n - 1] = t_next, t_next - last
+            n, prev, last, last_post = n + 1, last, t_next, False
+        else:
+            nts[n - 1] = t_next
+            if n > 1:
+                dts[n - 2] = t_next - prev
+            last = t_next
+        if is_event:
+            if n > N:
+                raise GridOverflow("more than %d intervals" % N)
+            nts[n], dts[n - 1] = t_next + EVENT_EPS, t_next - last
+            n, prev, last, last_post = n + 1, last, t_next, True
+    nb = n - 1
+    if nb < 1 or not dts[nb - 1] > 0.0 or any(not (dts[k] >= 0.0) or not (dts[k] <= 1e6) for k in range(nb)):
+        raise GridOverflow("the events admit no grid")
+    if nb < N:
+        d_last, t_end, t_dup = dts[nb - 1], nts[nb], nts[nb - 1]
+        for k in range(nb - 1, N - 1):
+            dts[k], nts[k + 1] = 0.0, t_dup
+        dts[N - 1], nts[N] = d_last, t_end
+    return np.array(dts), np.array(nts), nb
+
+
 def raw_stamps(dts, node_times):
     """PrimalSolution time stamps of a grid from its interval lengths and sampling times (event_grid): a post-event node takes the stamp of
     the node before it, so pre- and post-event node share one (what hsqp_upload_reference records, HSQP_BLK_STAMPS)."""

@@ -202,6 +202,15 @@ def load_library():
     lib.hsqp_loop_metrics_restart.argtypes = [C.c_void_p, C.c_int, _ip]
     lib.hsqp_loop_metrics.argtypes = [C.c_void_p, C.c_int, _mp]
     lib.hsqp_loop_metrics_device.argtypes = [C.c_void_p, C.c_int, _mp]
+    # include/hsqp_grid.h
+    _gr = C.POINTER(_abi.GridSettings)
+    lib.hsqp_grid_defaults.argtypes = [_gr]
+    lib.hsqp_grid_defaults.restype = None
+    lib.hsqp_event_grid.argtypes = [C.c_void_p, _gr, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _ip, _dp, _ip, _dp, _dp, _ip]
+    lib.hsqp_event_grid_device.argtypes = [C.c_void_p, _gr, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _ip, _dp, _ip, _dp, _dp, _ip]
+    lib.hsqp_loop_event_grid.argtypes = [C.c_void_p, _gr]
+    lib.hsqp_loop_grid.argtypes = [C.c_void_p, _ip, _dp, _dp]
+    lib.hsqp_loop_grid_device.argtypes = [C.c_void_p, _ip, _dp, _dp]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -258,6 +267,7 @@ class HipSqpSolver:
         self._shape = None
         self._sol = None
         self._loop_batch = 0
+        self._loop_nodes = self._grid_nodes = 0
         if not model.centroidal:   # the velocity-command generator's joint targets (reference.info defaultJointState) are not part of hsqp_model_desc
             self._check(self.lib.hsqp_set_default_joint_state(h, _c(model.default_joint_state).ctypes.data_as(_dp)))
 
@@ -1019,6 +1029,7 @@ class HipSqpSolver:
             self._loop_batch = self._gait_batch = B
             self._gait_events = int(gait.max_events)
             self._shape = (B, int(settings.n_nodes))
+            self._loop_nodes = int(settings.n_nodes)
             return
         n_events = np.ascontiguousarray(n_events, dtype=np.int32)
         mode_sequence = np.ascontiguousarray(mode_sequence, dtype=np.int32)
@@ -1032,6 +1043,7 @@ class HipSqpSolver:
                                              n_events.ctypes.data_as(ip), event_times.ctypes.data_as(_dp), mode_sequence.ctypes.data_as(ip)))
         self._loop_batch = B
         self._shape = (B, int(settings.n_nodes))
+        self._loop_nodes = int(settings.n_nodes)
 
     def loop_command(self, v_cmd):
         """hsqp_loop_command: new commands [B][4], in effect from the next cycle."""
@@ -1154,6 +1166,70 @@ class HipSqpSolver:
     def metrics_summary(self, records):
         """metrics_summary(records) with the model's total mass and gravity."""
         return metrics_summary(records, self.model.total_mass, self.model.desc.gravity)
+
+    # ---- include/hsqp_grid.h: the ocs2 event-node time grid built per instance on the device
+    def grid_settings(self, event_nodes=None, dt_min=None):
+        """hsqp_grid_settings: hsqp_grid_defaults (32 event nodes, dt_min 1e-4) with the given values."""
+        st = _abi.GridSettings()
+        self.lib.hsqp_grid_defaults(C.byref(st))
+        if event_nodes is not None:
+            st.event_nodes = int(event_nodes)
+        if dt_min is not None:
+            st.dt_min = float(dt_min)
+        return st
+
+    def event_grid(self, t0, n_nodes, dt, n_events, event_times, settings=None):
+        """hsqp_event_grid: the padded event-node grid of every instance from its events (n_events [B], event_times [B][E]):
+        dict(n_intervals[B], dt_nodes[B, N], node_times[B, N + 1], status[B]), N = n_nodes + event_nodes — what upload_reference takes as dt and
+        node_times.  An instance without a grid (_abi.GRID_OVERFLOW) raises HsqpError with that dict as its `result` attribute."""
+        settings = self.grid_settings() if settings is None else settings
+        n_events, event_times = np.ascontiguousarray(n_events, dtype=np.int32), _c(event_times)
+        B = n_events.shape[0]
+        if event_times.ndim != 2 or event_times.shape[0] != B:
+            raise ValueError("inconsistent event array shapes")
+        N = max(int(n_nodes) + int(settings.event_nodes), 0)
+        out = dict(n_intervals=np.zeros(B, np.int32), dt_nodes=np.zeros((B, N)), node_times=np.zeros((B, N + 1)), status=np.zeros(B, np.int32))
+        rc = self.lib.hsqp_event_grid(self.h, C.byref(settings), B, C.c_double(t0), int(n_nodes), C.c_double(dt), event_times.shape[1], n_events.ctypes.data_as(_ip),
+                                      event_times.ctypes.data_as(_dp), out["n_intervals"].ctypes.data_as(_ip), out["dt_nodes"].ctypes.data_as(_dp),
+                                      out["node_times"].ctypes.data_as(_dp), out["status"].ctypes.data_as(_ip))
+        if rc != 0:
+            err = HsqpError(rc, self.lib.hsqp_last_error(self.h).decode())
+            err.result = out
+            raise err
+        return out
+
+    def event_grid_device(self, settings, batch, t0, n_nodes, dt, max_events, n_events_ptr, event_times_ptr, n_intervals_ptr, dt_nodes_ptr, node_times_ptr, status_ptr=0):
+        """hsqp_event_grid_device: the same with every array in device memory (addresses); the events are not checked."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        icast = lambda a: C.cast(C.c_void_p(int(a)), _ip) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_event_grid_device(self.h, C.byref(settings), int(batch), C.c_double(t0), int(n_nodes), C.c_double(dt), int(max_events), icast(n_events_ptr),
+                                                    cast(event_times_ptr), icast(n_intervals_ptr), cast(dt_nodes_ptr), cast(node_times_ptr), icast(status_ptr)))
+
+    def loop_event_grid(self, settings=None, on=True):
+        """hsqp_loop_event_grid on the started loop: from the next cycle every problem is posed on the padded event-node grid of its instance
+        (settings: grid_settings()); on=False: back to the uniform grid.  debug_read / device_trajectory / stamps take the new node count from
+        here on, which the device has after the next cycle."""
+        if not on:
+            self._check(self.lib.hsqp_loop_event_grid(self.h, None))
+            if self._shape is not None and getattr(self, "_loop_nodes", 0):
+                self._shape = (self._shape[0], self._loop_nodes)
+            return
+        settings = self.grid_settings() if settings is None else settings
+        self._check(self.lib.hsqp_loop_event_grid(self.h, C.byref(settings)))
+        self._grid_nodes = self._loop_nodes + int(settings.event_nodes)
+        self._shape = (self._loop_batch, self._grid_nodes)
+
+    def loop_grid(self):
+        """hsqp_loop_grid: dict(n_intervals[B], dt_nodes[B, N], node_times[B, N + 1]) of the last completed cycle (which ran on the event grid)."""
+        B, N = max(self._loop_batch, 1), max(getattr(self, "_grid_nodes", 0), 1)
+        out = dict(n_intervals=np.zeros(B, np.int32), dt_nodes=np.zeros((B, N)), node_times=np.zeros((B, N + 1)))
+        self._check(self.lib.hsqp_loop_grid(self.h, out["n_intervals"].ctypes.data_as(_ip), out["dt_nodes"].ctypes.data_as(_dp), out["node_times"].ctypes.data_as(_dp)))
+        return out
+
+    def loop_grid_device(self, n_intervals_ptr=0, dt_nodes_ptr=0, node_times_ptr=0):
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        icast = lambda a: C.cast(C.c_void_p(int(a)), _ip) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_loop_grid_device(self.h, icast(n_intervals_ptr), cast(dt_nodes_ptr), cast(node_times_ptr)))
 
     # ---- include/hsqp_gait.h: per-instance gait schedule and ladder
     def gait_reset(self, settings, batch, t0=0.0):
