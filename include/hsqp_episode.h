@@ -52,6 +52,7 @@
  *
  * Out of scope: fall detection beyond the caller's box, per-instance loop time, centroidal handles, several GPUs.  (On the event-node
  * grid of include/hsqp_grid.h an instance whose schedule overflows the grid stops the cycle for all: it is a fault of the schedule, not of an episode.)
+ * The base-height box is absolute unless include/hsqp_ground.h (box_above_ground) puts it on the height above the estimated ground.
  *
  * ABI: additions only — no public struct and no entry point of the other headers changes, HSQP_ABI_VERSION stays.
  */

@@ -56,6 +56,8 @@
  * noise, sensor and compute delay) between the plant's state and everything the MPC reads; with none set the cycle is exactly the one above.
  * The uniform grid of step 2 is the default: include/hsqp_grid.h switches the started loop to ocs2's event-node grid (hsqp_reference::node_times),
  * built per instance on the device in every cycle.
+ * The command's height entry is a world height and terrain_height one constant unless include/hsqp_ground.h switches the started loop to the
+ * per-instance ground-height estimate from the stance feet.
  * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, the centroidal formulation, several GPUs.
  *
  * ABI: additions only — no public struct and no entry point of hsqp.h, hsqp_feedback.h or hsqp_rollout.h changes, HSQP_ABI_VERSION stays.

@@ -63,6 +63,12 @@ the flag the tool's output is what it was.
 the device and solves on nodes + EVENT_NODES intervals (default 32; the handle is created with that many nodes).  The line carries `event_grid`: the
 settings and the range of the instances' own interval counts in the last cycle.  --schedule walk | run: the gait of the uploaded schedules (run has
 twice the events per second).  Opt-in: without the flags the tool's output is what it was.
+--ground-adapt [on | off]: hsqp_loop_ground (include/hsqp_ground.h) behind the start: every cycle estimates the ground height under every instance from its
+stance feet, the command's height entry means height above it and step 2 takes it as the instance's terrain height; --box-above-ground puts the
+base-height box of the triage on the height above the estimate.  The line carries `ground`: the range of the estimates at the end, the instances alive
+and the base height above the LOCAL ground at the end (the height map under the base with --terrain, the plane at 0 without), mean and range over
+the instances alive.  off: the same report from a loop that does not follow the ground (the partner of an A/B pair).  Opt-in: without the flag the
+tool's output is what it was.
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -292,6 +298,8 @@ def main():
     ap.add_argument("--metrics", action="store_true")
     ap.add_argument("--event-grid", type=int, nargs="?", const=32, default=None, metavar="EVENT_NODES")
     ap.add_argument("--schedule", default="walk", choices=("walk", "run"))
+    ap.add_argument("--ground-adapt", nargs="?", const="on", default=None, choices=("on", "off"))
+    ap.add_argument("--box-above-ground", action="store_true")
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -309,6 +317,8 @@ def main():
         ap.error("--terrain requires --plant torque --contact (the terrain lies under the ground of the torque plant)")
     if not args.observe and given & {"--obs-noise", "--obs-bias", "--sensor-delay", "--compute-delay", "--obs-seed"}:
         ap.error("--obs-noise, --obs-bias, --sensor-delay, --compute-delay and --obs-seed belong to --observe (without it the MPC measures the plant exactly)")
+    if args.box_above_ground and args.ground_adapt != "on":
+        ap.error("--box-above-ground belongs to --ground-adapt (the box stands on the estimated ground)")
     if args.push:
         return push_sweep(args)
     line = timed_run(args, args.observe)
@@ -415,6 +425,8 @@ def timed_run(args, observe):
             s.loop_metrics_enable()
         if args.event_grid is not None:
             s.loop_event_grid(s.grid_settings(event_nodes=args.event_grid))
+        if args.ground_adapt == "on":
+            s.loop_ground(s.ground_settings(box_above_ground=args.box_above_ground))
         last_pos = x_init[:, :3].copy()
         masses = None
         if args.inertia:
@@ -452,6 +464,18 @@ def timed_run(args, observe):
                 last_pos[have, :2] = r["end_xy"][have]
         probe = rollout_probe(s, args, x_end) if args.plant else None
         counts = s.loop_grid()["n_intervals"] if args.event_grid is not None else None
+        ground = None
+        if args.ground_adapt:
+            alive = np.isfinite(x_end).all(axis=1) & ((ep["state"] == 0) if ep else True)
+            local = s.terrain_height(np.where(alive[:, None, None], x_end[:, None, :2], 0.0))[0][:, 0] if args.terrain else np.zeros(B)
+            above = (x_end[:, 2] - local)[alive]
+            est = s.loop_ground_state()[0][alive] if args.ground_adapt == "on" else None
+            ground = dict(adapt=args.ground_adapt, box_above_ground=args.box_above_ground, alive=int(alive.sum()),
+                          local_ground_range=[round(float(local[alive].min()), 4), round(float(local[alive].max()), 4)] if alive.any() else None,
+                          height_above_ground_mean=round(float(above.mean()), 4) if alive.any() else None,
+                          height_above_ground_range=[round(float(above.min()), 4), round(float(above.max()), 4)] if alive.any() else None,
+                          estimate_range=[round(float(est.min()), 4), round(float(est.max()), 4)] if est is not None and alive.any() else None,
+                          estimate_error_max=round(float(np.abs(est - local[alive]).max()), 4) if est is not None and alive.any() else None)
     finally:
         s.close()
     heights = np.concatenate(heights)
@@ -476,6 +500,8 @@ def timed_run(args, observe):
         for b in range(B):
             print(f"instance {b}: total mass {masses[b]:.3f} kg, finished {'yes' if finished[b] else 'no'}")
     extra = {"metrics": metrics} if args.metrics else {}
+    if args.ground_adapt:
+        extra["ground"] = ground
     if args.event_grid is not None:
         extra["event_grid"] = dict(event_nodes=args.event_grid, schedule=args.schedule, intervals=N + args.event_grid, n_intervals_range=[int(counts.min()), int(counts.max())])
     return dict({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,

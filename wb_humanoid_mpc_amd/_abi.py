@@ -287,6 +287,16 @@ class GridSettings(C.Structure):   # hsqp_grid_settings
 # entry points of include/hsqp_grid.h (tests/test_grid.py checks that the library exports each of them and the binding declares it)
 GRID_ENTRY_POINTS = ("hsqp_grid_defaults", "hsqp_event_grid", "hsqp_event_grid_device", "hsqp_loop_event_grid", "hsqp_loop_grid", "hsqp_loop_grid_device")
 
+
+# include/hsqp_ground.h
+class GroundSettings(C.Structure):   # hsqp_ground_settings
+    _fields_ = [("enabled", C.c_int32), ("box_above_ground", C.c_int32), ("filter_alpha", C.c_double), ("initial_height", C.c_double)]
+
+
+# entry points of include/hsqp_ground.h (tests/test_ground.py checks that the library exports each of them and the binding declares it)
+GROUND_ENTRY_POINTS = ("hsqp_ground_defaults", "hsqp_ground_estimate", "hsqp_ground_estimate_device", "hsqp_upload_reference_ground", "hsqp_loop_ground",
+                       "hsqp_loop_ground_state", "hsqp_loop_ground_state_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

@@ -25,6 +25,7 @@
 #include "../../include/hsqp_loop.h"
 #include "hsqp_gait.h"
 #include "hsqp_grid.h"
+#include "hsqp_ground.h"
 #include "hsqp_episode.h"
 #include "hsqp_metrics.h"
 #include "hsqp_observe.h"
@@ -785,11 +786,12 @@ __global__ __launch_bounds__(256, 4) void k_kkt_boundaries(const double* __restr
 __global__ __launch_bounds__(64) void k_params(const DevModel* __restrict__ dm, hsqp_swing_config cfg, double terrain, int arm_swing, int max_events,
                                                const int* __restrict__ n_events, const double* __restrict__ ev, const int* __restrict__ seq, int n_knots,
                                                const double* __restrict__ tt, const double* __restrict__ ts, double t0, double dt, const double* __restrict__ times,
-                                               int N, int B, double* __restrict__ par, int* __restrict__ bad) {
+                                               int N, int B, double* __restrict__ par, int* __restrict__ bad, const double* __restrict__ terrain_b) {
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= B * (N + 1)) return;
   const int b = id / (N + 1), k = id % (N + 1);
-  const bool ok = node_params_eval(cfg, terrain, arm_swing, n_events[b], ev + (size_t)b * max_events, seq + (size_t)b * (max_events + 1), n_knots,
+  // terrain_b (may be null): one terrain height per instance in place of `terrain` (include/hsqp_ground.h)
+  const bool ok = node_params_eval(cfg, terrain_b ? terrain_b[b] : terrain, arm_swing, n_events[b], ev + (size_t)b * max_events, seq + (size_t)b * (max_events + 1), n_knots,
                                    tt + (size_t)b * n_knots, ts + (size_t)b * n_knots * NX, times ? times[id] : t0 + k * dt, par + (size_t)id * NP);
   if (!ok) atomicExch(bad, 1);
 }
@@ -807,6 +809,24 @@ __global__ __launch_bounds__(CMDT_THREADS) void k_command_targets(const DevModel
   if (live) it = command_item_load(alpha, v_cmd, v_filt, id);
   __syncthreads();
   if (live) command_item_store(it, dm->default_joint_state, x0, t0, horizon, id, v_filt, tt, ts);
+}
+
+// ---- ground-height estimate from the stance feet (hsqp_ground.h): one lane per (instance, foot), 32 instances per 64-lane workgroup.  A lane walks the
+// kinematics of its leg; the two lanes of an instance are neighbours in one wave and exchange their height with a lane shuffle, OUTSIDE the live guard
+// (a dead lane's partner is dead too: B instances are 2 B lanes); the lane of foot 0 applies the rule, writes g_out (the loop: the latch's shadow) and
+// both heights, and — the loop's second phase, k_ground_apply's work in the same launch — shifts the instance's three target knots and writes its
+// terrain height for k_params.  No atomics, no barrier
+constexpr int GROUND_THREADS = 64;
+__global__ __launch_bounds__(GROUND_THREADS) void k_ground_estimate(const DevModel* __restrict__ dm, GroundArgs a) {
+  const int id = blockIdx.x * GROUND_THREADS + threadIdx.x, b = id / 2, f = id % 2;
+  const bool live = b < a.B;
+  double z = 0.0;
+  if (live) z = ground_foot_height(*dm, a.x + (size_t)b * NX, f);
+  const double other = __shfl_xor(z, 1);
+  if (live && f == 0) {
+    const double both[2] = {z, other};
+    ground_instance_finish(a, b, both);
+  }
 }
 
 // ---- gait schedule and ladder (hsqp_gait.h): one wave per instance, the work row of its schedule in LDS; reads the live state `in`, writes the shadow
@@ -1286,6 +1306,14 @@ struct hsqp_handle {
     int grid_cur = 0;
     struct GridRec { int* ni; double* dts; double* nts; } grid_rec[2] = {};
     int* grid_status = nullptr; int* grid_bad = nullptr;
+    // the ground-height estimate (include/hsqp_ground.h): off after every start.  In d_ground (ground_layout): the latch and its shadow, gnd_g[ground_cur] the
+    // live one (a cycle writes the other, which becomes the live one at step 5), the contact-frame heights [B][2] likewise, g_init [B] and the terrain
+    // height of step 2 [B]
+    bool ground = false;
+    hsqp_ground_settings ground_st = {};
+    int ground_cur = 0;
+    double* gnd_g[2] = {nullptr, nullptr}; double* gnd_fz[2] = {nullptr, nullptr};
+    double* gnd_init = nullptr; double* gnd_terrain = nullptr;
   } loop;
   // the resident gait state (include/hsqp_gait.h): two copies in d_gait (gait_layout), s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
   struct Gait {
@@ -1297,7 +1325,8 @@ struct hsqp_handle {
     int* status = nullptr; int* ne = nullptr; int* seq = nullptr;
     double* ev = nullptr; double* v = nullptr; double* x = nullptr;
   } gait;
-  DevBuf<char> d_gait, d_episode, d_metrics, d_grid;
+  DevBuf<char> d_gait, d_episode, d_metrics, d_grid, d_ground;
+  DevBuf<char> d_ground_stage;    // staging of hsqp_ground_estimate's host arrays and of hsqp_upload_reference_ground's heights (ground_stage_layout)
   DevBuf<char> d_grid_stage;      // staging of hsqp_event_grid's host arrays (grid_stage_layout)
   DevBuf<char> d_loop, d_loop_log;   // the loop's resident arrays; staging of hsqp_loop_run's host logs and of hsqp_command_targets' host arrays
   double kernel_ms[5] = {0, 0, 0, 0, 0};
@@ -1398,6 +1427,19 @@ static size_t grid_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t N) {
 struct GridStage { int* ne; int* ni; int* status; double* ev; double* dts; double* nts; size_t bytes; };
 static GridStage grid_stage_layout(Carve c, size_t B, size_t N, size_t E, bool host) {
   return {c.take<int>(B, host), c.take<int>(B, host), c.take<int>(B), c.take<double>(B * E, host), c.take<double>(B * N, host), c.take<double>(B * (N + 1), host), c.bytes()};
+}
+// d_ground: the loop's latch and its shadow, the contact-frame heights of the two, g_init, the terrain height of step 2
+static size_t ground_layout(Carve c, hsqp_handle::Loop& L, size_t B) {
+  for (int i = 0; i < 2; ++i) { L.gnd_g[i] = c.take<double>(B); L.gnd_fz[i] = c.take<double>(2 * B); }
+  L.gnd_init = c.take<double>(B); L.gnd_terrain = c.take<double>(B);
+  return c.bytes();
+}
+// d_ground_stage.  hsqp_ground_estimate (host arrays): n_events [B], mode_sequence [B][E + 1], x [B][58], event_times [B][E], g [B], foot_z [B][2];
+// hsqp_upload_reference_ground: terrain_heights [B] alone
+struct GroundStage { int* ne; int* seq; double* x; double* ev; double* g; double* fz; double* terrain; size_t bytes; };
+static GroundStage ground_stage_layout(Carve c, size_t B, size_t E, bool estimate) {
+  return {c.take<int>(B, estimate), c.take<int>(B * (E + 1), estimate), c.take<double>(B * NX, estimate), c.take<double>(B * E, estimate), c.take<double>(B, estimate),
+          c.take<double>(2 * B, estimate), c.take<double>(B, !estimate), c.bytes()};
 }
 // d_observe: the loop's ring of plant states (absent without a delay) and the observations of the even and the odd cycles
 static size_t observe_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t slots) {
@@ -1848,6 +1890,7 @@ struct RefDev {
   bool sorted;
   const int* warm_b = nullptr;     // [B] HSQP_WARM_SHIFT / _COLD per instance (the isolated loop; `warm` is then SHIFT), or null: `warm` for all
   const int* grid_bad = nullptr;   // one int the builder of a device-built grid has set if an instance has none (the loop on the event grid), or null
+  const double* terrain_b = nullptr;   // [B] one terrain height per instance in place of terrain_height (include/hsqp_ground.h), or null
 };
 
 // The device side of hsqp_upload_reference, behind the copies `step` has queued on the stream (x_init in d_xinit, the grid in d_dt, the CALLER warm start
@@ -1857,7 +1900,7 @@ static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& 
   if (step.rc == HSQP_OK) {
     const int total = (int)(B * (N + 1));
     HSQP_LAUNCH(k_params, dim3((total + 63) / 64), dim3(64), 0, h->stream, h->d_dm, r.swing, r.terrain_height, r.arm_swing, r.E, r.ne, r.ev, r.seq,
-                       r.K, r.tt, r.ts, r.t0, r.dt, r.nt, (int)N, (int)B, h->d_par, r.bad);
+                       r.K, r.tt, r.ts, r.t0, r.dt, r.nt, (int)N, (int)B, h->d_par, r.bad, r.terrain_b);
     if (h->hdm.formulation == HSQP_FORM_CENTROIDAL)   // torso task-space reference of every row
       HSQP_LAUNCH(k_params_cent_torso, dim3(total), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_par);
     step(hipGetLastError(), "k_params");
@@ -1886,7 +1929,8 @@ static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& 
   return HSQP_OK;
 }
 
-int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r) {
+// hsqp_upload_reference, and hsqp_upload_reference_ground (terrain_heights != null: [B] host, checked by the caller, staged here)
+static int upload_reference_impl(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r, const double* terrain_heights) {
   if (!h) return HSQP_ERR_BAD_ARG;
   h->have_policy = false;
   h->loop.started = false;
@@ -1939,9 +1983,16 @@ int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_refe
     step(hipMemcpyAsync(h->d_x, p->x_traj, B * (N + 1) * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
     step(hipMemcpyAsync(h->d_u, p->u_traj, B * N * NU * 8, hipMemcpyHostToDevice, h->stream), "upload u");
   }
-  const RefDev rd{(int)E, (int)K, d_ne, d_seq, d_ev, d_tt, d_ts, d_nt, d_bad, r->t0, r->dt, r->swing, r->terrain_height, r->arm_swing, warm, N_prev, sorted};
+  RefDev rd{(int)E, (int)K, d_ne, d_seq, d_ev, d_tt, d_ts, d_nt, d_bad, r->t0, r->dt, r->swing, r->terrain_height, r->arm_swing, warm, N_prev, sorted};
+  if (terrain_heights) {
+    DEV_ENSURE(h->d_ground_stage, ground_stage_layout(Carve{}, B, E, false).bytes, "terrain-height staging");
+    double* d_terrain = ground_stage_layout(Carve{h->d_ground_stage.p}, B, E, false).terrain;
+    step(hipMemcpyAsync(d_terrain, terrain_heights, B * 8, hipMemcpyHostToDevice, h->stream), "upload terrain_heights");
+    rd.terrain_b = d_terrain;
+  }
   return reference_build(h, p, rd, step);
 }
+int hsqp_upload_reference(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r) { return upload_reference_impl(h, p, r, nullptr); }
 
 // The backward sweep of an iteration: serial recursion, or — one or two instances on a long horizon, or on request — the associative scan over the
 // stages (hsqp_scan.h), or on request the two-level sweep with P segments per instance (hsqp_segment.h).  The scan inverts I + C1 J2 of partial
@@ -3247,6 +3298,11 @@ static void launch_command_targets(hsqp_handle* h, int B, const double* d_v_cmd,
               t0, horizon, B, d_tt, d_ts);
 }
 
+// queues k_ground_estimate on the handle's stream (device arrays)
+static void launch_ground_estimate(hsqp_handle* h, const GroundArgs& a) {
+  HSQP_LAUNCH(k_ground_estimate, dim3((unsigned)((2 * (size_t)a.B + GROUND_THREADS - 1) / GROUND_THREADS)), dim3(GROUND_THREADS), 0, h->stream, h->d_dm, a);
+}
+
 static int command_targets_impl(hsqp_handle* h, int batch, const double* v_cmd, double* v_filt, double alpha, const double* x0, double t0, double horizon,
                                 double* tt, double* ts, bool dev) {
   if (!h) return HSQP_ERR_BAD_ARG;
@@ -3357,6 +3413,7 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
   L.isolate = false;
   L.metrics = false; L.metrics_made = false;
   L.grid = false; L.grid_have = false;
+  L.ground = false;
   L.gait = gait != nullptr;
   L.started = true;
   return HSQP_OK;
@@ -3587,6 +3644,7 @@ static int loop_metrics_cycle(hsqp_handle* h) {
   MetricsArgs a{};
   a.isolate = L.isolate ? 1 : 0; a.cycle = L.cycle; a.period = L.st.period;
   if (L.isolate) { a.st = L.ep_st; a.ep_state = L.ep.state; }
+  if (L.isolate && L.ground && L.ground_st.box_above_ground) a.ground = L.gnd_g[L.ground_cur ^ 1];   // (before step 5: the cycle's value is still the shadow)
   a.it_status = h->d_status; a.perf = h->d_perf_after; a.ro_status = L.ro_status;
   a.xs = L.xs; a.x_before = L.x; a.cmd = L.isolate ? L.v_use : L.v_cmd;
   a.steps = L.met_steps; a.rejected = L.met_rejected;
@@ -3671,6 +3729,19 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
     const int rc = gait_launch_and_check(h, "hsqp_loop_run", L.B, tp, st.n_nodes * st.dt, vf_next, xm, L.ne, L.ev, L.seq);
     if (rc != HSQP_OK) return rc;
   }
+  // the ground-height estimate between the targets (and the gait update) and step 2 (include/hsqp_ground.h): from the state the MPC reads and this cycle's
+  // schedule the latch advances into its shadow, the knots of step 1 are shifted by it and step 2 takes it as the instance's terrain height
+  const bool gnd = L.ground;
+  if (gnd) {
+    GroundArgs ga{};
+    ga.B = L.B; ga.E = L.E; ga.t = tp; ga.filter_alpha = L.ground_st.filter_alpha;
+    ga.x = xm; ga.ne = L.ne; ga.ev = L.ev; ga.seq = L.seq;
+    ga.g_in = L.gnd_g[L.ground_cur]; ga.g_out = L.gnd_g[L.ground_cur ^ 1]; ga.foot_z = L.gnd_fz[L.ground_cur ^ 1];
+    ga.g_init = L.gnd_init; ga.mode_b = iso ? L.ep.mode : nullptr; ga.parked = iso ? L.ep.state : nullptr;
+    ga.ts = L.ts; ga.terrain_b = L.gnd_terrain;
+    if (step.rc == HSQP_OK) launch_ground_estimate(h, ga);
+    step(hipGetLastError(), "k_ground_estimate");
+  }
   // 2. hsqp_upload_reference's work on the resident arrays
   h->have_problem = false; h->have_solution = false; h->have_stamps = false;
   if (grid) {   // the grid of every instance from this cycle's schedule, into d_dt and the shadow record; set_grid's part is the builder's
@@ -3687,6 +3758,7 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   RefDev rd{L.E, CMD_KNOTS, L.ne, L.seq, L.ev, L.tt, L.ts, grid ? gr->nts : nullptr, L.bad, tp, st.dt, st.swing, st.terrain_height, st.arm_swing, warm, N_prev, true};
   if (iso && warm == HSQP_WARM_SHIFT) rd.warm_b = L.ep.mode;
   if (grid) rd.grid_bad = L.grid_bad;
+  if (gnd) rd.terrain_b = L.gnd_terrain;
   { const int rc = reference_build(h, &p, rd, step);
     if (rc != HSQP_OK) return grid ? loop_grid_failure(h, "hsqp_loop_run", rc) : rc; }
   // 3. the iteration
@@ -3702,9 +3774,11 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   if (d_xlog) HCHECK(hipMemcpyAsync(d_xlog, L.xs, B * NX * 8, hipMemcpyDeviceToDevice, h->stream));
   if (d_ulog) HCHECK(hipMemcpyAsync(d_ulog, L.us, B * NU * 8, hipMemcpyDeviceToDevice, h->stream));
   if (L.gait) h->gait.cur ^= 1;
+  if (gnd) L.ground_cur ^= 1;   // the shadow is the latch
   L.t += st.period;
   if (iso) {   // 6. the triage of every instance, and with a resident gait the reset of those that start a new episode at the new loop time
-    const TriageArgs a{L.ep_st, L.cycle, h->d_status, h->d_perf_after, L.ro_status, L.xs, L.x_reset, L.v_cmd, L.ep, L.x, L.v_filt, L.v_use, d_xlog, d_ulog};
+    const TriageArgs a{L.ep_st, L.cycle, h->d_status, h->d_perf_after, L.ro_status, L.xs, L.x_reset, L.v_cmd, L.ep, L.x, L.v_filt, L.v_use, d_xlog, d_ulog,
+                       gnd && L.ground_st.box_above_ground ? L.gnd_g[L.ground_cur] : nullptr};
     HSQP_LAUNCH(k_loop_triage, dim3(L.B), dim3(64), 0, h->stream, a);
     if (L.gait)
       HSQP_LAUNCH(k_gait_reset_instances, dim3(L.B), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)nullptr, (const int*)L.ep.reset,
@@ -3901,6 +3975,129 @@ int hsqp_loop_grid(hsqp_handle* h, int32_t* n_intervals, double* dt_nodes, doubl
 int hsqp_loop_grid_device(hsqp_handle* h, int32_t* d_n_intervals, double* d_dt_nodes, double* d_node_times) {
   return loop_grid_impl(h, d_n_intervals, d_dt_nodes, d_node_times, true);
 }
+
+// ---- the ground-height estimate (include/hsqp_ground.h, csrc/hsqp_ground.h): the stand-alone estimate, the upload with per-instance terrain heights, the
+// loop's switch and its latches
+void hsqp_ground_defaults(hsqp_ground_settings* s) {
+  if (!s) return;
+  memset(s, 0, sizeof(*s));
+  s->enabled = 1;
+}
+
+static int ground_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) return loop_bad(h, who, "whole-body handles only (the contact frames' heights come from the whole-body configuration)");
+  return HSQP_OK;
+}
+
+static int ground_estimate_impl(hsqp_handle* h, int batch, double t, const double* x, int max_events, const int32_t* ne, const double* ev, const int32_t* seq,
+                                double alpha, double* g, double* foot_z, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_ground_estimate_device" : "hsqp_ground_estimate";
+  { const int rc = ground_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (!x || !ne || !ev || !seq || !g) return loop_bad(h, who, "null array");
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (!(alpha >= 0.0 && alpha < 1.0)) return loop_bad(h, who, "filter_alpha outside [0, 1)");
+  if (!std::isfinite(t)) return loop_bad(h, who, "t not finite");
+  if (max_events < 1) return loop_bad(h, who, "max_events < 1");
+  const size_t B = batch, E = max_events;
+  if (!dev) {
+    for (size_t b = 0; b < B; ++b)
+      if (ne[b] < 1 || ne[b] > max_events) return loop_bad(h, who, "n_events outside [1, max_events]");
+    if (!all_finite(g, B)) return loop_bad(h, who, "non-finite g");
+  }
+  HCHECK(hipSetDevice(h->device));
+  GroundArgs a{};
+  a.B = batch; a.E = max_events; a.t = t; a.filter_alpha = alpha;
+  StickyError step{h};
+  if (dev) {
+    a.x = x; a.ne = ne; a.ev = ev; a.seq = seq; a.g_in = g; a.g_out = g; a.foot_z = foot_z;
+    launch_ground_estimate(h, a);
+    step(hipGetLastError(), "k_ground_estimate");
+  } else {
+    DEV_ENSURE(h->d_ground_stage, ground_stage_layout(Carve{}, B, E, true).bytes, "ground-estimate staging");
+    const GroundStage sg = ground_stage_layout(Carve{h->d_ground_stage.p}, B, E, true);
+    step(hipMemcpyAsync(sg.ne, ne, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
+    step(hipMemcpyAsync(sg.seq, seq, B * (E + 1) * 4, hipMemcpyHostToDevice, h->stream), "upload mode_sequence");
+    step(hipMemcpyAsync(sg.x, x, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
+    step(hipMemcpyAsync(sg.ev, ev, B * E * 8, hipMemcpyHostToDevice, h->stream), "upload event_times");
+    step(hipMemcpyAsync(sg.g, g, B * 8, hipMemcpyHostToDevice, h->stream), "upload g");
+    a.x = sg.x; a.ne = sg.ne; a.ev = sg.ev; a.seq = sg.seq; a.g_in = sg.g; a.g_out = sg.g; a.foot_z = sg.fz;
+    if (step.rc == HSQP_OK) {
+      launch_ground_estimate(h, a);
+      step(hipGetLastError(), "k_ground_estimate");
+    }
+    step(hipMemcpyAsync(g, sg.g, B * 8, hipMemcpyDeviceToHost, h->stream), "download g");
+    if (foot_z) step(hipMemcpyAsync(foot_z, sg.fz, 2 * B * 8, hipMemcpyDeviceToHost, h->stream), "download foot_z");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+int hsqp_ground_estimate(hsqp_handle* h, int batch, double t, const double* x, int max_events, const int32_t* n_events, const double* event_times,
+                         const int32_t* mode_sequence, double filter_alpha, double* g, double* foot_z) {
+  return ground_estimate_impl(h, batch, t, x, max_events, n_events, event_times, mode_sequence, filter_alpha, g, foot_z, false);
+}
+int hsqp_ground_estimate_device(hsqp_handle* h, int batch, double t, const double* d_x, int max_events, const int32_t* d_n_events, const double* d_event_times,
+                                const int32_t* d_mode_sequence, double filter_alpha, double* d_g, double* d_foot_z) {
+  return ground_estimate_impl(h, batch, t, d_x, max_events, d_n_events, d_event_times, d_mode_sequence, filter_alpha, d_g, d_foot_z, true);
+}
+
+int hsqp_upload_reference_ground(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r, const double* terrain_heights) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_upload_reference_ground";
+  { const int rc = ground_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (!p || !r || !terrain_heights) return loop_bad(h, who, "null problem / reference / terrain_heights");
+  if (p->batch < 1 || p->batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (!all_finite(terrain_heights, (size_t)p->batch)) return loop_bad(h, who, "non-finite terrain_heights");
+  return upload_reference_impl(h, p, r, terrain_heights);
+}
+
+int hsqp_loop_ground(hsqp_handle* h, const hsqp_ground_settings* gs, const double* g_init) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_ground";
+  { const int rc = ground_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Loop& L = h->loop;
+  if (gs && ((gs->enabled != 0 && gs->enabled != 1) || (gs->box_above_ground != 0 && gs->box_above_ground != 1)))
+    return loop_bad(h, who, "hsqp_ground_settings::enabled and box_above_ground must be 0 or 1");
+  if (!gs || !gs->enabled) { L.ground = false; return HSQP_OK; }
+  if (!(gs->filter_alpha >= 0.0 && gs->filter_alpha < 1.0)) return loop_bad(h, who, "hsqp_ground_settings::filter_alpha outside [0, 1)");
+  if (!std::isfinite(gs->initial_height)) return loop_bad(h, who, "hsqp_ground_settings::initial_height not finite");
+  const size_t B = L.B;
+  if (g_init && !all_finite(g_init, B)) return loop_bad(h, who, "non-finite g_init");
+  HCHECK(hipSetDevice(h->device));
+  L.ground = false;   // (a failure below leaves no half-made state switched on)
+  DEV_ENSURE(h->d_ground, ground_layout(Carve{}, L, B), "loop ground latches");
+  ground_layout(Carve{h->d_ground.p}, L, B);
+  const std::vector<double> init(B, gs->initial_height);
+  StickyError step{h};
+  step(hipMemcpyAsync(L.gnd_init, g_init ? g_init : init.data(), B * 8, hipMemcpyHostToDevice, h->stream), "upload g_init");
+  step(hipMemcpyAsync(L.gnd_g[0], g_init ? g_init : init.data(), B * 8, hipMemcpyHostToDevice, h->stream), "upload g");
+  step(hipMemsetAsync(L.gnd_fz[0], 0, 2 * B * 8, h->stream), "memset foot_z");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  L.ground_cur = 0;
+  L.ground_st = *gs;
+  L.ground = true;
+  return HSQP_OK;
+}
+
+static int loop_ground_state_impl(hsqp_handle* h, double* g, double* foot_z, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_loop_ground_state_device" : "hsqp_loop_ground_state";
+  { const int rc = ground_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  const hsqp_handle::Loop& L = h->loop;
+  if (!L.ground) return loop_bad(h, who, "the ground-height estimate is off (hsqp_loop_ground; every hsqp_loop_start turns it off)");
+  HCHECK(hipSetDevice(h->device));
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t B = L.B;
+  if (g) HCHECK(hipMemcpyAsync(g, L.gnd_g[L.ground_cur], B * 8, kind, h->stream));
+  if (foot_z) HCHECK(hipMemcpyAsync(foot_z, L.gnd_fz[L.ground_cur], 2 * B * 8, kind, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_loop_ground_state(hsqp_handle* h, double* g, double* foot_z) { return loop_ground_state_impl(h, g, foot_z, false); }
+int hsqp_loop_ground_state_device(hsqp_handle* h, double* d_g, double* d_foot_z) { return loop_ground_state_impl(h, d_g, d_foot_z, true); }
 
 // ---- the observation model of the loop (include/hsqp_observe.h, csrc/hsqp_observe.h): the resident settings and table, the evaluation, the last observation
 void hsqp_observe_defaults(hsqp_observe_settings* s) { if (s) memset(s, 0, sizeof(*s)); }

@@ -35,6 +35,7 @@ struct TriageArgs {
   double* v_filt;                // [B][CMD_N] the filter state of the next cycle (already advanced)
   double* v_use;                 // [B][CMD_N] the command in use from the next cycle on
   double* x_log; double* u_log;  // row `cycle` of the logs, [B][NX] / [B][NU], or null
+  const double* ground;          // [B] the estimated ground (include/hsqp_ground.h, box_above_ground): the height test is on xs[2] - ground[b]; or null
 };
 
 HSQP_HD bool episode_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and +-inf
@@ -52,11 +53,14 @@ HSQP_HD bool episode_row_finite(const Ctx& ctx, const double* row, int n) {
 }
 
 // the verdict on one instance (include/hsqp_episode.h, step 6): HSQP_EP_ALIVE or the first cause that applies
-HSQP_HD int episode_verdict(const Ctx& ctx, const hsqp_episode_settings& st, int it_status, const hsqp_perf& perf, int ro_status, const double* xs) {
+// ground (may be null): the estimated ground under the instance, the base-height box is then above it
+HSQP_HD int episode_verdict(const Ctx& ctx, const hsqp_episode_settings& st, int it_status, const hsqp_perf& perf, int ro_status, const double* xs,
+                            const double* ground = nullptr) {
   if (it_status != 0 || !episode_finite(perf.merit) || !episode_finite(perf.cost) || !episode_finite(perf.dynamics_sse) || !episode_finite(perf.equality_sse))
     return HSQP_EP_FAILED_NUMERIC;
   if (ro_status != HSQP_ROLLOUT_OK || !episode_row_finite(ctx, xs, NX)) return HSQP_EP_FAILED_ROLLOUT;
-  if (xs[2] < st.min_base_height || xs[2] > st.max_base_height || fabs(xs[4]) > st.max_tilt || fabs(xs[5]) > st.max_tilt) return HSQP_EP_FAILED_BOUNDS;
+  const double height = ground ? xs[2] - *ground : xs[2];
+  if (height < st.min_base_height || height > st.max_base_height || fabs(xs[4]) > st.max_tilt || fabs(xs[5]) > st.max_tilt) return HSQP_EP_FAILED_BOUNDS;
   return HSQP_EP_ALIVE;
 }
 
@@ -76,7 +80,7 @@ HSQP_HD int triage_instance(const Ctx& ctx, const TriageArgs& a, int b) {
   const double* xr = a.x_reset + (size_t)b * NX;
   const double* vc = a.v_cmd + (size_t)b * CMD_N;
   const int before = ep.state[b];
-  const int cause = episode_verdict(ctx, a.st, a.it_status[b], a.perf[b], a.ro_status[b], xs);
+  const int cause = episode_verdict(ctx, a.st, a.it_status[b], a.perf[b], a.ro_status[b], xs, a.ground ? a.ground + b : nullptr);
   const bool failed = cause != HSQP_EP_ALIVE;
   const int after = failed ? (a.st.on_failure == HSQP_EPISODE_RESET ? HSQP_EP_ALIVE : cause) : before;
   WG_SYNC(ctx);   // every lane has read the words lane 0 rewrites below

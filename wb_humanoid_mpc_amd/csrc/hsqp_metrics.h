@@ -41,6 +41,7 @@ struct MetricsArgs {
   const double* act_limit;       // [NJ] the resident effort limits
   hsqp_metrics* rec;             // [B][2] CURRENT, PREVIOUS
   int* feet;                     // [B][2] per foot: loaded in the open record's last ground sample
+  const double* ground;          // [B] the estimated ground the triage's height box stands on (include/hsqp_ground.h, box_above_ground), or null
 };
 
 struct MetricsNoGround {};
@@ -181,7 +182,7 @@ HSQP_HD void metrics_instance(const Ctx& ctx, const DevModel& dm, MetricsWST<CT>
   if (a.isolate) {
     before = a.ep_state[b];
     if (ctx.tid < 64) {   // (one wave: episode_row_finite is a one-wave ballot)
-      const int v = episode_verdict(ctx, a.st, a.it_status[b], a.perf[b], a.ro_status[b], xs);
+      const int v = episode_verdict(ctx, a.st, a.it_status[b], a.perf[b], a.ro_status[b], xs, a.ground ? a.ground + b : nullptr);
       if (ctx.tid == 0) w.verdict = v;
     }
     WG_SYNC(ctx);

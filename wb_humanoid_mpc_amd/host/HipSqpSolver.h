@@ -22,6 +22,7 @@
 #include "../../include/hsqp_episode.h"
 #include "../../include/hsqp_metrics.h"
 #include "../../include/hsqp_grid.h"
+#include "../../include/hsqp_ground.h"
 #include "../../include/hsqp_push.h"
 #include "../../include/hsqp_plant.h"
 #include "../../include/hsqp_contact.h"
@@ -546,6 +547,47 @@ class HipSqpSolver {
     const int rc = hsqp_loop_grid(h_, g.nIntervals.data(), g.dtNodes.data(), g.nodeTimes.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_grid failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     return g;
+  }
+
+  /** The ground height under every instance estimated from its stance feet (include/hsqp_ground.h): the new latches [batch] from the measured states
+   *  [batch][58], the mode schedules at time t and the latches g; footHeights (optional): the heights of both contact frames [batch][2]. */
+  hsqp_ground_settings groundDefaults() const { hsqp_ground_settings st; hsqp_ground_defaults(&st); return st; }
+  std::vector<double> groundEstimate(double t, const std::vector<double>& x, int maxEvents, const std::vector<int32_t>& nEvents, const std::vector<double>& eventTimes,
+                                     const std::vector<int32_t>& modeSequence, std::vector<double> g, double filterAlpha = 0.0, std::vector<double>* footHeights = nullptr) {
+    const size_t B = nEvents.size();
+    if (B == 0 || maxEvents < 1 || x.size() != B * HSQP_NX || eventTimes.size() != B * (size_t)maxEvents || modeSequence.size() != B * (size_t)(maxEvents + 1) || g.size() != B)
+      throw std::runtime_error("[HipSqpSolver] groundEstimate: inconsistent array sizes");
+    if (footHeights) footHeights->assign(2 * B, 0.0);
+    const int rc = hsqp_ground_estimate(h_, (int)B, t, x.data(), maxEvents, nEvents.data(), eventTimes.data(), modeSequence.data(), filterAlpha, g.data(),
+                                        footHeights ? footHeights->data() : nullptr);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_ground_estimate failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return g;
+  }
+  /** hsqp_upload_reference with one terrain height per instance (terrainHeights [batch]) in place of reference.terrain_height. */
+  void uploadReferenceGround(const hsqp_problem& problem, const hsqp_reference& reference, const std::vector<double>& terrainHeights) {
+    if (problem.batch < 1 || terrainHeights.size() != (size_t)problem.batch) throw std::runtime_error("[HipSqpSolver] uploadReferenceGround: inconsistent array sizes");
+    const int rc = hsqp_upload_reference_ground(h_, &problem, &reference, terrainHeights.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_upload_reference_ground failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    loopBatch_ = 0;   // (every upload ends a loop)
+    shiftable_ = false;
+  }
+  /** The started loop follows the ground under its stance feet from its next cycle on: the command's height entry means height above the estimated
+   *  ground, step 2 takes the estimate as the instance's terrain height (settings == nullptr or enabled 0: off).  gInit [batch] or empty
+   *  (settings->initial_height): the latches' start values.  Off after every start. */
+  void setLoopGround(const hsqp_ground_settings* settings, const std::vector<double>& gInit = {}) {
+    if (!gInit.empty() && gInit.size() != loopBatch_) throw std::runtime_error("[HipSqpSolver] setLoopGround: gInit must hold one value per instance of the loop");
+    const int rc = hsqp_loop_ground(h_, settings, gInit.empty() ? nullptr : gInit.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_ground failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** The latches [batch] and the contact-frame heights [batch][2] of the loop's last completed cycle. */
+  struct LoopGround { std::vector<double> g, footHeights; };
+  LoopGround loopGround() {
+    if (loopBatch_ == 0) throw std::runtime_error("[HipSqpSolver] loopGround: no loop started (startLoop, setLoopGround)");
+    LoopGround out;
+    out.g.assign(loopBatch_, 0.0); out.footHeights.assign(2 * loopBatch_, 0.0);
+    const int rc = hsqp_loop_ground_state(h_, out.g.data(), out.footHeights.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_ground_state failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return out;
   }
 
   const PrimalSolution& getPrimalSolution() const { return solution_; }

@@ -211,6 +211,16 @@ def load_library():
     lib.hsqp_loop_event_grid.argtypes = [C.c_void_p, _gr]
     lib.hsqp_loop_grid.argtypes = [C.c_void_p, _ip, _dp, _dp]
     lib.hsqp_loop_grid_device.argtypes = [C.c_void_p, _ip, _dp, _dp]
+    # include/hsqp_ground.h
+    _gs = C.POINTER(_abi.GroundSettings)
+    lib.hsqp_ground_defaults.argtypes = [_gs]
+    lib.hsqp_ground_defaults.restype = None
+    lib.hsqp_ground_estimate.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, C.c_int, _ip, _dp, _ip, C.c_double, _dp, _dp]
+    lib.hsqp_ground_estimate_device.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, C.c_int, _ip, _dp, _ip, C.c_double, _dp, _dp]
+    lib.hsqp_upload_reference_ground.argtypes = [C.c_void_p, C.POINTER(_abi.Problem), C.POINTER(_abi.Reference), _dp]
+    lib.hsqp_loop_ground.argtypes = [C.c_void_p, _gs, _dp]
+    lib.hsqp_loop_ground_state.argtypes = [C.c_void_p, _dp, _dp]
+    lib.hsqp_loop_ground_state_device.argtypes = [C.c_void_p, _dp, _dp]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -389,7 +399,7 @@ class HipSqpSolver:
                                target_states, swing, terrain_height, arm_swing, node_times, warm)
 
     def _upload_reference(self, B, N, x_init, x_traj, u_traj, dt, t0, n_events, event_times, mode_sequence, target_times, target_states,
-                          swing, terrain_height, arm_swing, node_times, warm):
+                          swing, terrain_height, arm_swing, node_times, warm, terrain_heights=None):
         n_events = np.ascontiguousarray(n_events, dtype=np.int32)
         mode_sequence = np.ascontiguousarray(mode_sequence, dtype=np.int32)
         event_times, target_times, target_states = _c(event_times), _c(target_times), _c(target_states)
@@ -406,7 +416,11 @@ class HipSqpSolver:
                            n_knots=target_times.shape[1], target_times=target_times.ctypes.data_as(_dp),
                            target_states=target_states.ctypes.data_as(_dp), swing=swing, terrain_height=terrain_height,
                            arm_swing=1 if arm_swing else 0, warm_start=warm)
-        self._check(self.lib.hsqp_upload_reference(self.h, C.byref(p), C.byref(r)))
+        if terrain_heights is None:
+            self._check(self.lib.hsqp_upload_reference(self.h, C.byref(p), C.byref(r)))
+        else:   # include/hsqp_ground.h: one terrain height per instance
+            th = _c(np.broadcast_to(np.asarray(terrain_heights, dtype=np.float64), (B,)))
+            self._check(self.lib.hsqp_upload_reference_ground(self.h, C.byref(p), C.byref(r), th.ctypes.data_as(_dp)))
         self._shape = (B, N)
 
     def device_trajectory(self):
@@ -1230,6 +1244,77 @@ class HipSqpSolver:
         cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
         icast = lambda a: C.cast(C.c_void_p(int(a)), _ip) if a else None  # noqa: E731
         self._check(self.lib.hsqp_loop_grid_device(self.h, icast(n_intervals_ptr), cast(dt_nodes_ptr), cast(node_times_ptr)))
+
+    # ---- include/hsqp_ground.h: per-instance ground-height estimate from the stance feet
+    def ground_settings(self, enabled=True, box_above_ground=False, filter_alpha=None, initial_height=None):
+        """hsqp_ground_settings: hsqp_ground_defaults (on, absolute box, the raw estimate, initial height 0) with the given values."""
+        st = _abi.GroundSettings()
+        self.lib.hsqp_ground_defaults(C.byref(st))
+        st.enabled, st.box_above_ground = int(enabled), int(box_above_ground)
+        if filter_alpha is not None:
+            st.filter_alpha = float(filter_alpha)
+        if initial_height is not None:
+            st.initial_height = float(initial_height)
+        return st
+
+    def ground_estimate(self, x, t, n_events, event_times, mode_sequence, g=None, filter_alpha=0.0):
+        """hsqp_ground_estimate: (g[B], foot_z[B, 2]) — the new latch of every instance from its state x [B][58], its mode schedule at time t and its latch
+        g (None: zeros), and the heights of both contact frames."""
+        x = _c(np.atleast_2d(x))
+        B = x.shape[0]
+        n_events, mode_sequence, event_times = np.ascontiguousarray(n_events, dtype=np.int32), np.ascontiguousarray(mode_sequence, dtype=np.int32), _c(event_times)
+        if x.shape != (B, _abi.NX) or n_events.shape != (B,) or event_times.ndim != 2 or event_times.shape[0] != B or mode_sequence.shape != (B, event_times.shape[1] + 1):
+            raise ValueError("inconsistent ground-estimate array shapes")
+        g = np.zeros(B) if g is None else _c(np.broadcast_to(g, (B,))).copy()
+        fz = np.zeros((B, 2))
+        self._check(self.lib.hsqp_ground_estimate(self.h, B, C.c_double(t), x.ctypes.data_as(_dp), event_times.shape[1], n_events.ctypes.data_as(_ip),
+                                                  event_times.ctypes.data_as(_dp), mode_sequence.ctypes.data_as(_ip), C.c_double(filter_alpha), g.ctypes.data_as(_dp),
+                                                  fz.ctypes.data_as(_dp)))
+        return g, fz
+
+    def ground_estimate_device(self, batch, t, x_ptr, max_events, n_events_ptr, event_times_ptr, mode_sequence_ptr, g_ptr, foot_z_ptr=0, filter_alpha=0.0):
+        """hsqp_ground_estimate_device: the same with every array in device memory (addresses); g is updated in place."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        icast = lambda a: C.cast(C.c_void_p(int(a)), _ip) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_ground_estimate_device(self.h, int(batch), C.c_double(t), cast(x_ptr), int(max_events), icast(n_events_ptr), cast(event_times_ptr),
+                                                         icast(mode_sequence_ptr), C.c_double(filter_alpha), cast(g_ptr), cast(foot_z_ptr)))
+
+    def upload_reference_ground(self, x_init, n_nodes, dt, t0, n_events, event_times, mode_sequence, target_times, target_states, swing, terrain_heights,
+                                arm_swing=True, mode="cold", node_times=None, x_traj=None, u_traj=None):
+        """hsqp_upload_reference_ground: upload_reference_warm (mode "shift" / "cold") or, with x_traj and u_traj, upload_reference, with one terrain
+        height per instance (terrain_heights [B]) in place of the reference's terrain_height."""
+        x_init = _c(np.atleast_2d(x_init))
+        caller = x_traj is not None
+        warm = _abi.WARM_CALLER if caller else {"shift": _abi.WARM_SHIFT, "cold": _abi.WARM_COLD}[mode]
+        if caller:
+            x_traj, u_traj = _c(x_traj), _c(u_traj)
+            if x_traj.ndim == 2:
+                x_traj, u_traj = x_traj[None], u_traj[None]
+        self._upload_reference(x_init.shape[0], int(n_nodes), x_init, x_traj, u_traj, dt, t0, n_events, event_times, mode_sequence, target_times, target_states,
+                               swing, 0.0, arm_swing, node_times, warm, terrain_heights=terrain_heights)
+
+    def loop_ground(self, settings=None, g_init=None, on=True):
+        """hsqp_loop_ground on the started loop: from the next cycle every instance's ground height is estimated from its stance feet, the command's
+        height entry means height above it and step 2 takes it as the instance's terrain height (settings: ground_settings(); g_init [B]: the latches'
+        start values, None: settings.initial_height).  on=False: off again."""
+        if not on:
+            self._check(self.lib.hsqp_loop_ground(self.h, None, None))
+            return
+        settings = self.ground_settings() if settings is None else settings
+        if g_init is not None:
+            g_init = _c(np.broadcast_to(g_init, (max(self._loop_batch, 1),)))
+        self._check(self.lib.hsqp_loop_ground(self.h, C.byref(settings), g_init.ctypes.data_as(_dp) if g_init is not None else None))
+
+    def loop_ground_state(self):
+        """hsqp_loop_ground_state: (g[B], foot_z[B, 2]) — the latches and the contact-frame heights of the last completed cycle."""
+        B = max(self._loop_batch, 1)
+        g, fz = np.zeros(B), np.zeros((B, 2))
+        self._check(self.lib.hsqp_loop_ground_state(self.h, g.ctypes.data_as(_dp), fz.ctypes.data_as(_dp)))
+        return g, fz
+
+    def loop_ground_state_device(self, g_ptr=0, foot_z_ptr=0):
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_loop_ground_state_device(self.h, cast(g_ptr), cast(foot_z_ptr)))
 
     # ---- include/hsqp_gait.h: per-instance gait schedule and ladder
     def gait_reset(self, settings, batch, t0=0.0):
