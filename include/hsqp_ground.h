@@ -47,8 +47,9 @@
  * terrain_heights (host arrays), max_events < 1, n_events outside [1, max_events] (host arrays), enabled / box_above_ground other than 0 / 1, the loop
  * entry points without a started loop, hsqp_loop_ground_state while the setting is off.  A refused call leaves the previous setting in place.
  *
- * Out of scope: per-foot lift-off / touch-down height sequences (the planner's three-argument update), the MPC reading the height map or its slope,
- * contact detection from forces, metrics relative to the ground, centroidal handles, several GPUs.
+ * Out of scope: the MPC reading the map's slope, contact detection from forces, metrics relative to the ground, centroidal handles, several GPUs.
+ * (Per-foot lift-off / touch-down height sequences — the planner's three-argument update — read from the height map are include/hsqp_perceive.h; with
+ * both settings on this one keeps its shift of the knots and its box, and step 2 takes that header's rows for the stance z, lift-off and touch-down.)
  *
  * ABI: additions only — no public struct and no entry point of the other headers changes, HSQP_ABI_VERSION stays.
  */

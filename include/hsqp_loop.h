@@ -58,6 +58,8 @@
  * built per instance on the device in every cycle.
  * The command's height entry is a world height and terrain_height one constant unless include/hsqp_ground.h switches the started loop to the
  * per-instance ground-height estimate from the stance feet.
+ * The swing references take that one height for both feet, lift-off and touch-down alike, unless include/hsqp_perceive.h switches the started loop to
+ * per-foot lift-off and touch-down heights read from the resident height maps.
  * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, the centroidal formulation, several GPUs.
  *
  * ABI: additions only — no public struct and no entry point of hsqp.h, hsqp_feedback.h or hsqp_rollout.h changes, HSQP_ABI_VERSION stays.

@@ -41,6 +41,7 @@
  *   T4. There is no edge or corner contact of the sole other than its eight points.
  *   T5. The MPC, the triage box of hsqp_episode.h (absolute base height) and hsqp_loop_settings::terrain_height do not see the map.
  *       (It holds while the ground-height estimate of include/hsqp_ground.h is off: with it on the loop follows the ground under the stance feet.)
+ *       With the per-foot swing heights of include/hsqp_perceive.h on, the swing references of the MPC read the map: lift-off and touch-down height per foot.
  *
  * Lifetime: that of the contact table (hsqp_upload*, hsqp_solve, hsqp_loop_start*, the weight updates, hsqp_plant_set / _clear, hsqp_contact_set
  * keep it).  The terrain acts only while the plant kind is HSQP_PLANT_TORQUE, contact is enabled, and both maps and a placement table are

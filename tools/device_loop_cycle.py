@@ -14,7 +14,7 @@ iteration and the rollout, and its rollout keeps no step counters).
                                       [--inertia] [--mass-spread 0.15] [--payload KG]
                                       [--terrain ramp|ledge|rubble] [--terrain-seed 2026]
                                       [--observe] [--obs-noise 0.005] [--obs-bias 0.02] [--sensor-delay 1] [--compute-delay 1] [--obs-seed 2026]
-                                      [--metrics]
+                                      [--metrics] [--perceive]
     python tools/device_loop_cycle.py --push [--batch 16] [--nodes 40] [--cycles 120] [--push-max 400] [--push-at 0.5] [--push-for 0.2]
                                       [--plant torque [--contact ...] [--actuator ...] [--inertia ...]]
 --with-push: the timed run with one push per instance resident (include/hsqp_push.h): a constant lateral force at the pelvis over the whole run.
@@ -69,6 +69,11 @@ base-height box of the triage on the height above the estimate.  The line carrie
 and the base height above the LOCAL ground at the end (the height map under the base with --terrain, the plane at 0 without), mean and range over
 the instances alive.  off: the same report from a loop that does not follow the ground (the partner of an A/B pair).  Opt-in: without the flag the
 tool's output is what it was.
+--perceive: hsqp_loop_perceive (include/hsqp_perceive.h) behind the start; requires --terrain.  Every cycle reads, per instance and foot, the lift-off and
+touch-down height of every phase of the schedule from the height map — under the foot where it stands, under the foothold the targets carry to the
+touch-down time where it will land — and step 2 takes them in place of the one terrain height.  The line carries `perceive`: the range of the last
+cycle's lift-off heights over the instances alive and the largest difference between a swing's touch-down and lift-off height (offset removed).
+Opt-in: without the flag the tool's output is what it was.
 --gait: the loop is started through hsqp_loop_start_gait (include/hsqp_gait.h): every instance starts in stance with the resident gait schedule
 and ladder instead of an uploaded walk schedule.  ladder: the scenario of tests/test_gpu_gait.py across the batch (instance b mod 4: zero
 command; 0.2 m/s from cycle 10; 0.2 m/s from cycle 10 and zero again from cycle 40; a yaw rate of 0.3 rad/s from cycle 10), and the line
@@ -300,6 +305,7 @@ def main():
     ap.add_argument("--schedule", default="walk", choices=("walk", "run"))
     ap.add_argument("--ground-adapt", nargs="?", const="on", default=None, choices=("on", "off"))
     ap.add_argument("--box-above-ground", action="store_true")
+    ap.add_argument("--perceive", action="store_true")
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -317,6 +323,8 @@ def main():
         ap.error("--terrain requires --plant torque --contact (the terrain lies under the ground of the torque plant)")
     if not args.observe and given & {"--obs-noise", "--obs-bias", "--sensor-delay", "--compute-delay", "--obs-seed"}:
         ap.error("--obs-noise, --obs-bias, --sensor-delay, --compute-delay and --obs-seed belong to --observe (without it the MPC measures the plant exactly)")
+    if args.perceive and not args.terrain:
+        ap.error("--perceive requires --terrain (the swing heights are read from the resident height maps)")
     if args.box_above_ground and args.ground_adapt != "on":
         ap.error("--box-above-ground belongs to --ground-adapt (the box stands on the estimated ground)")
     if args.push:
@@ -427,6 +435,8 @@ def timed_run(args, observe):
             s.loop_event_grid(s.grid_settings(event_nodes=args.event_grid))
         if args.ground_adapt == "on":
             s.loop_ground(s.ground_settings(box_above_ground=args.box_above_ground))
+        if args.perceive:
+            s.loop_perceive()
         last_pos = x_init[:, :3].copy()
         masses = None
         if args.inertia:
@@ -476,6 +486,13 @@ def timed_run(args, observe):
                           height_above_ground_range=[round(float(above.min()), 4), round(float(above.max()), 4)] if alive.any() else None,
                           estimate_range=[round(float(est.min()), 4), round(float(est.max()), 4)] if est is not None and alive.any() else None,
                           estimate_error_max=round(float(np.abs(est - local[alive]).max()), 4) if est is not None and alive.any() else None)
+        perceive = None
+        if args.perceive:
+            alive = np.isfinite(x_end).all(axis=1) & (ep["state"] == 0)
+            lift, touch, _ = s.loop_foot_heights()
+            step = np.abs(touch - lift - st.swing.touch_down_height_offset)[alive]
+            perceive = dict(alive=int(alive.sum()), lift_off_range=[round(float(lift[alive].min()), 4), round(float(lift[alive].max()), 4)] if alive.any() else None,
+                            step_max=round(float(step.max()), 4) if alive.any() else None)
     finally:
         s.close()
     heights = np.concatenate(heights)
@@ -502,6 +519,8 @@ def timed_run(args, observe):
     extra = {"metrics": metrics} if args.metrics else {}
     if args.ground_adapt:
         extra["ground"] = ground
+    if args.perceive:
+        extra["perceive"] = perceive
     if args.event_grid is not None:
         extra["event_grid"] = dict(event_nodes=args.event_grid, schedule=args.schedule, intervals=N + args.event_grid, n_intervals_range=[int(counts.min()), int(counts.max())])
     return dict({"metric": "device_loop_cycle", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,

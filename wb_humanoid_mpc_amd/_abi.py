@@ -297,6 +297,16 @@ class GroundSettings(C.Structure):   # hsqp_ground_settings
 GROUND_ENTRY_POINTS = ("hsqp_ground_defaults", "hsqp_ground_estimate", "hsqp_ground_estimate_device", "hsqp_upload_reference_ground", "hsqp_loop_ground",
                        "hsqp_loop_ground_state", "hsqp_loop_ground_state_device")
 
+
+# include/hsqp_perceive.h
+class PerceiveSettings(C.Structure):   # hsqp_perceive_settings
+    _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32)]
+
+
+# entry points of include/hsqp_perceive.h (tests/test_perceive.py checks that the library exports each of them and the binding declares it)
+PERCEIVE_ENTRY_POINTS = ("hsqp_perceive_defaults", "hsqp_upload_reference_heights", "hsqp_foot_heights", "hsqp_foot_heights_device", "hsqp_loop_perceive",
+                         "hsqp_loop_foot_heights", "hsqp_loop_foot_heights_device")
+
 ROLLOUT_ODE45, ROLLOUT_RK4 = 0, 1
 ROLLOUT_FEEDFORWARD, ROLLOUT_FEEDBACK = 0, 1
 ROLLOUT_OK, ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE = 0, 1, 2

@@ -26,6 +26,7 @@
 #include "hsqp_gait.h"
 #include "hsqp_grid.h"
 #include "hsqp_ground.h"
+#include "hsqp_perceive.h"
 #include "hsqp_episode.h"
 #include "hsqp_metrics.h"
 #include "hsqp_observe.h"
@@ -786,13 +787,17 @@ __global__ __launch_bounds__(256, 4) void k_kkt_boundaries(const double* __restr
 __global__ __launch_bounds__(64) void k_params(const DevModel* __restrict__ dm, hsqp_swing_config cfg, double terrain, int arm_swing, int max_events,
                                                const int* __restrict__ n_events, const double* __restrict__ ev, const int* __restrict__ seq, int n_knots,
                                                const double* __restrict__ tt, const double* __restrict__ ts, double t0, double dt, const double* __restrict__ times,
-                                               int N, int B, double* __restrict__ par, int* __restrict__ bad, const double* __restrict__ terrain_b) {
+                                               int N, int B, double* __restrict__ par, int* __restrict__ bad, const double* __restrict__ terrain_b,
+                                               const double* __restrict__ lift_rows, const double* __restrict__ touch_rows) {
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= B * (N + 1)) return;
   const int b = id / (N + 1), k = id % (N + 1);
   // terrain_b (may be null): one terrain height per instance in place of `terrain` (include/hsqp_ground.h)
+  // lift_rows, touch_rows (both null or both given): [B][2][max_events + 1], the planner's three-argument update (include/hsqp_perceive.h)
+  const size_t rows = (size_t)b * 2 * (max_events + 1);
   const bool ok = node_params_eval(cfg, terrain_b ? terrain_b[b] : terrain, arm_swing, n_events[b], ev + (size_t)b * max_events, seq + (size_t)b * (max_events + 1), n_knots,
-                                   tt + (size_t)b * n_knots, ts + (size_t)b * n_knots * NX, times ? times[id] : t0 + k * dt, par + (size_t)id * NP);
+                                   tt + (size_t)b * n_knots, ts + (size_t)b * n_knots * NX, times ? times[id] : t0 + k * dt, par + (size_t)id * NP,
+                                   lift_rows ? lift_rows + rows : nullptr, lift_rows ? touch_rows + rows : nullptr, max_events + 1);
   if (!ok) atomicExch(bad, 1);
 }
 
@@ -827,6 +832,16 @@ __global__ __launch_bounds__(GROUND_THREADS) void k_ground_estimate(const DevMod
     const double both[2] = {z, other};
     ground_instance_finish(a, b, both);
   }
+}
+
+// ---- per-foot swing heights from the height map (hsqp_perceive.h): one lane per (instance, foot), 32 instances per 64-lane workgroup.  A lane walks the
+// kinematics of its leg and the phases of its schedule and writes its own rows; lanes exchange nothing.  A dead lane (b >= B) reads and writes nothing.
+// No atomics, no barrier, no cross-lane operation
+constexpr int PERCEIVE_THREADS = 64;
+__global__ __launch_bounds__(PERCEIVE_THREADS) void k_foot_heights(const DevModel* __restrict__ dm, ContactParams cp, TerrainParams tp, PerceiveArgs a) {
+  const int id = blockIdx.x * PERCEIVE_THREADS + threadIdx.x, b = id / 2, f = id % 2;
+  if (b >= a.B) return;
+  perceive_lane(*dm, cp, tp, a, b, f);
 }
 
 // ---- gait schedule and ladder (hsqp_gait.h): one wave per instance, the work row of its schedule in LDS; reads the live state `in`, writes the shadow
@@ -1314,6 +1329,10 @@ struct hsqp_handle {
     int ground_cur = 0;
     double* gnd_g[2] = {nullptr, nullptr}; double* gnd_fz[2] = {nullptr, nullptr};
     double* gnd_init = nullptr; double* gnd_terrain = nullptr;
+    // the per-foot swing heights from the height map (include/hsqp_perceive.h): off after every start.  In d_perceive (perceive_layout): the rows a cycle
+    // writes and step 2 reads — lift, touch [B][2][E + 1], footholds [B][2][E + 1][2]
+    bool perceive = false;
+    double* pcv_lift = nullptr; double* pcv_touch = nullptr; double* pcv_fxy = nullptr;
   } loop;
   // the resident gait state (include/hsqp_gait.h): two copies in d_gait (gait_layout), s[cur] the live one; ne / ev / seq: the cycle's schedule of the host entry point
   struct Gait {
@@ -1325,7 +1344,8 @@ struct hsqp_handle {
     int* status = nullptr; int* ne = nullptr; int* seq = nullptr;
     double* ev = nullptr; double* v = nullptr; double* x = nullptr;
   } gait;
-  DevBuf<char> d_gait, d_episode, d_metrics, d_grid, d_ground;
+  DevBuf<char> d_gait, d_episode, d_metrics, d_grid, d_ground, d_perceive;
+  DevBuf<char> d_perceive_stage;  // staging of hsqp_foot_heights' host arrays and of hsqp_upload_reference_heights' rows (perceive_stage_layout)
   DevBuf<char> d_ground_stage;    // staging of hsqp_ground_estimate's host arrays and of hsqp_upload_reference_ground's heights (ground_stage_layout)
   DevBuf<char> d_grid_stage;      // staging of hsqp_event_grid's host arrays (grid_stage_layout)
   DevBuf<char> d_loop, d_loop_log;   // the loop's resident arrays; staging of hsqp_loop_run's host logs and of hsqp_command_targets' host arrays
@@ -1440,6 +1460,19 @@ struct GroundStage { int* ne; int* seq; double* x; double* ev; double* g; double
 static GroundStage ground_stage_layout(Carve c, size_t B, size_t E, bool estimate) {
   return {c.take<int>(B, estimate), c.take<int>(B * (E + 1), estimate), c.take<double>(B * NX, estimate), c.take<double>(B * E, estimate), c.take<double>(B, estimate),
           c.take<double>(2 * B, estimate), c.take<double>(B, !estimate), c.bytes()};
+}
+// d_perceive: the loop's rows of the per-foot swing heights
+static size_t perceive_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t E) {
+  L.pcv_lift = c.take<double>(B * 2 * (E + 1)); L.pcv_touch = c.take<double>(B * 2 * (E + 1)); L.pcv_fxy = c.take<double>(B * 4 * (E + 1));
+  return c.bytes();
+}
+// d_perceive_stage.  The rows lift, touch [B][2][E + 1] and footholds [B][2][E + 1][2] (hsqp_upload_reference_heights: the two rows alone; the _device
+// entry of hsqp_foot_heights without foothold_xy: the footholds alone); hsqp_foot_heights (host arrays) behind them: n_events [B], mode_sequence
+// [B][E + 1], x [B][58], event_times [B][E], target_times [B][K], target_states [B][K][58]
+struct PerceiveStage { double* lift; double* touch; double* fxy; int* ne; int* seq; double* x; double* ev; double* tt; double* ts; size_t bytes; };
+static PerceiveStage perceive_stage_layout(Carve c, size_t B, size_t E, size_t K, bool inputs) {
+  return {c.take<double>(B * 2 * (E + 1)), c.take<double>(B * 2 * (E + 1)), c.take<double>(B * 4 * (E + 1)), c.take<int>(B, inputs), c.take<int>(B * (E + 1), inputs),
+          c.take<double>(B * NX, inputs), c.take<double>(B * E, inputs), c.take<double>(B * K, inputs), c.take<double>(B * K * NX, inputs), c.bytes()};
 }
 // d_observe: the loop's ring of plant states (absent without a delay) and the observations of the even and the odd cycles
 static size_t observe_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t slots) {
@@ -1891,6 +1924,8 @@ struct RefDev {
   const int* warm_b = nullptr;     // [B] HSQP_WARM_SHIFT / _COLD per instance (the isolated loop; `warm` is then SHIFT), or null: `warm` for all
   const int* grid_bad = nullptr;   // one int the builder of a device-built grid has set if an instance has none (the loop on the event grid), or null
   const double* terrain_b = nullptr;   // [B] one terrain height per instance in place of terrain_height (include/hsqp_ground.h), or null
+  const double* lift_rows = nullptr;   // [B][2][E + 1] the planner's lift-off and touch-down height per foot and phase (include/hsqp_perceive.h), or both null
+  const double* touch_rows = nullptr;
 };
 
 // The device side of hsqp_upload_reference, behind the copies `step` has queued on the stream (x_init in d_xinit, the grid in d_dt, the CALLER warm start
@@ -1900,7 +1935,7 @@ static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& 
   if (step.rc == HSQP_OK) {
     const int total = (int)(B * (N + 1));
     HSQP_LAUNCH(k_params, dim3((total + 63) / 64), dim3(64), 0, h->stream, h->d_dm, r.swing, r.terrain_height, r.arm_swing, r.E, r.ne, r.ev, r.seq,
-                       r.K, r.tt, r.ts, r.t0, r.dt, r.nt, (int)N, (int)B, h->d_par, r.bad, r.terrain_b);
+                       r.K, r.tt, r.ts, r.t0, r.dt, r.nt, (int)N, (int)B, h->d_par, r.bad, r.terrain_b, r.lift_rows, r.touch_rows);
     if (h->hdm.formulation == HSQP_FORM_CENTROIDAL)   // torso task-space reference of every row
       HSQP_LAUNCH(k_params_cent_torso, dim3(total), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, h->d_par);
     step(hipGetLastError(), "k_params");
@@ -1929,8 +1964,14 @@ static int reference_build(hsqp_handle* h, const hsqp_problem* p, const RefDev& 
   return HSQP_OK;
 }
 
-// hsqp_upload_reference, and hsqp_upload_reference_ground (terrain_heights != null: [B] host, checked by the caller, staged here)
-static int upload_reference_impl(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r, const double* terrain_heights) {
+static int loop_bad(hsqp_handle* h, const char* who, const char* what);   // (below, with the entry points of include/hsqp_loop.h)
+static bool all_finite(const double* v, size_t n);
+
+// hsqp_upload_reference, hsqp_upload_reference_ground (terrain_heights != null: [B] host, checked by the caller, staged here) and
+// hsqp_upload_reference_heights (lift_off, touch_down != null: [B][2][E + 1] host, staged here; who: that entry point, which checks the rows here, where
+// the schedule has been checked)
+static int upload_reference_impl(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r, const double* terrain_heights, const double* lift_off = nullptr,
+                                 const double* touch_down = nullptr, const char* who = nullptr) {
   if (!h) return HSQP_ERR_BAD_ARG;
   h->have_policy = false;
   h->loop.started = false;
@@ -1958,6 +1999,13 @@ static int upload_reference_impl(hsqp_handle* h, const hsqp_problem* p, const hs
   }
   for (int b = 0; b < r->batch; ++b)
     if (r->n_events[b] < 1 || r->n_events[b] > r->max_events) { h->err = "n_events outside [1, max_events]"; return HSQP_ERR_BAD_ARG; }
+  if (lift_off)   // (a refused call leaves the resident problem as it was)
+    for (size_t b = 0; b < (size_t)r->batch; ++b)
+      for (size_t f = 0; f < 2; ++f) {
+        const size_t row = (b * 2 + f) * ((size_t)r->max_events + 1);
+        if (!all_finite(lift_off + row, (size_t)r->n_events[b] + 1) || !all_finite(touch_down + row, (size_t)r->n_events[b] + 1))
+          return loop_bad(h, who, ("non-finite lift_off / touch_down entry of instance " + std::to_string(b) + " in its phases 0 .. n_events").c_str());
+      }
   if (!padding_is_zero(h, p)) return HSQP_ERR_BAD_ARG;
   bool sorted = true;   // raw stamps of the new grid non-decreasing (always on a uniform grid): what the interpolation of a later SHIFT needs
   for (size_t i = 1; r->node_times && sorted && i < (size_t)p->batch * (p->n_nodes + 1); ++i)
@@ -1989,6 +2037,13 @@ static int upload_reference_impl(hsqp_handle* h, const hsqp_problem* p, const hs
     double* d_terrain = ground_stage_layout(Carve{h->d_ground_stage.p}, B, E, false).terrain;
     step(hipMemcpyAsync(d_terrain, terrain_heights, B * 8, hipMemcpyHostToDevice, h->stream), "upload terrain_heights");
     rd.terrain_b = d_terrain;
+  }
+  if (lift_off) {
+    DEV_ENSURE(h->d_perceive_stage, perceive_stage_layout(Carve{}, B, E, K, false).bytes, "height-row staging");
+    const PerceiveStage sg = perceive_stage_layout(Carve{h->d_perceive_stage.p}, B, E, K, false);
+    step(hipMemcpyAsync(sg.lift, lift_off, B * 2 * (E + 1) * 8, hipMemcpyHostToDevice, h->stream), "upload lift_off");
+    step(hipMemcpyAsync(sg.touch, touch_down, B * 2 * (E + 1) * 8, hipMemcpyHostToDevice, h->stream), "upload touch_down");
+    rd.lift_rows = sg.lift; rd.touch_rows = sg.touch;
   }
   return reference_build(h, p, rd, step);
 }
@@ -3303,6 +3358,23 @@ static void launch_ground_estimate(hsqp_handle* h, const GroundArgs& a) {
   HSQP_LAUNCH(k_ground_estimate, dim3((unsigned)((2 * (size_t)a.B + GROUND_THREADS - 1) / GROUND_THREADS)), dim3(GROUND_THREADS), 0, h->stream, h->d_dm, a);
 }
 
+// the resident terrain as k_foot_heights needs it: maps and a placement table (include/hsqp_perceive.h)
+static int perceive_terrain_ok(hsqp_handle* h, const char* who) {
+  if (h->terrain_maps.empty() || !h->terrain_B)
+    return loop_bad(h, who, "no terrain resident: height maps and a placement table are needed (hsqp_terrain_set_maps, hsqp_terrain_set_instances)");
+  return HSQP_OK;
+}
+// queues k_foot_heights on the handle's stream (device arrays), on the resident terrain and contact ground
+static int launch_foot_heights(hsqp_handle* h, const char* who, const PerceiveArgs& a) {
+  { const int rc = perceive_terrain_ok(h, who); if (rc != HSQP_OK) return rc; }
+  ContactParams cp;
+  if (const int rc = contact_params(h, cp)) return rc;
+  TerrainParams tp;
+  if (const int rc = terrain_params(h, tp)) return rc;
+  HSQP_LAUNCH(k_foot_heights, dim3((unsigned)((2 * (size_t)a.B + PERCEIVE_THREADS - 1) / PERCEIVE_THREADS)), dim3(PERCEIVE_THREADS), 0, h->stream, h->d_dm, cp, tp, a);
+  return HSQP_OK;
+}
+
 static int command_targets_impl(hsqp_handle* h, int batch, const double* v_cmd, double* v_filt, double alpha, const double* x0, double t0, double horizon,
                                 double* tt, double* ts, bool dev) {
   if (!h) return HSQP_ERR_BAD_ARG;
@@ -3414,6 +3486,7 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
   L.metrics = false; L.metrics_made = false;
   L.grid = false; L.grid_have = false;
   L.ground = false;
+  L.perceive = false;
   L.gait = gait != nullptr;
   L.started = true;
   return HSQP_OK;
@@ -3742,6 +3815,17 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
     if (step.rc == HSQP_OK) launch_ground_estimate(h, ga);
     step(hipGetLastError(), "k_ground_estimate");
   }
+  // the per-foot swing heights behind the targets, the gait update and the ground estimate (include/hsqp_perceive.h): from the state the MPC reads, this
+  // cycle's schedule and this cycle's (shifted) knots every instance's rows, which step 2 takes in place of the terrain height
+  const bool pcv = L.perceive;
+  if (pcv) {
+    PerceiveArgs pa{};
+    pa.B = L.B; pa.E = L.E; pa.K = CMD_KNOTS; pa.t = tp; pa.offset = st.swing.touch_down_height_offset;
+    pa.x = xm; pa.ne = L.ne; pa.ev = L.ev; pa.seq = L.seq; pa.tt = L.tt; pa.ts = L.ts;
+    pa.lift = L.pcv_lift; pa.touch = L.pcv_touch; pa.fxy = L.pcv_fxy;
+    if (step.rc == HSQP_OK) { const int rc = launch_foot_heights(h, "hsqp_loop_run", pa); if (rc != HSQP_OK) return rc; }
+    step(hipGetLastError(), "k_foot_heights");
+  }
   // 2. hsqp_upload_reference's work on the resident arrays
   h->have_problem = false; h->have_solution = false; h->have_stamps = false;
   if (grid) {   // the grid of every instance from this cycle's schedule, into d_dt and the shadow record; set_grid's part is the builder's
@@ -3759,6 +3843,7 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   if (iso && warm == HSQP_WARM_SHIFT) rd.warm_b = L.ep.mode;
   if (grid) rd.grid_bad = L.grid_bad;
   if (gnd) rd.terrain_b = L.gnd_terrain;
+  if (pcv) { rd.lift_rows = L.pcv_lift; rd.touch_rows = L.pcv_touch; }
   { const int rc = reference_build(h, &p, rd, step);
     if (rc != HSQP_OK) return grid ? loop_grid_failure(h, "hsqp_loop_run", rc) : rc; }
   // 3. the iteration
@@ -4098,6 +4183,130 @@ static int loop_ground_state_impl(hsqp_handle* h, double* g, double* foot_z, boo
 }
 int hsqp_loop_ground_state(hsqp_handle* h, double* g, double* foot_z) { return loop_ground_state_impl(h, g, foot_z, false); }
 int hsqp_loop_ground_state_device(hsqp_handle* h, double* d_g, double* d_foot_z) { return loop_ground_state_impl(h, d_g, d_foot_z, true); }
+
+// ---- the per-foot swing heights from the height map (include/hsqp_perceive.h, csrc/hsqp_perceive.h): the upload with the planner's three-argument
+// update, the stand-alone rows, the loop's switch and its rows
+void hsqp_perceive_defaults(hsqp_perceive_settings* s) {
+  if (!s) return;
+  memset(s, 0, sizeof(*s));
+  s->enabled = 1;
+}
+
+static int perceive_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_WB) return loop_bad(h, who, "whole-body handles only (the footholds come from the whole-body configuration)");
+  return HSQP_OK;
+}
+
+int hsqp_upload_reference_heights(hsqp_handle* h, const hsqp_problem* p, const hsqp_reference* r, const double* lift_off, const double* touch_down) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_upload_reference_heights";
+  { const int rc = perceive_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (!p || !r || !lift_off || !touch_down) return loop_bad(h, who, "null problem / reference / lift_off / touch_down");
+  return upload_reference_impl(h, p, r, nullptr, lift_off, touch_down, who);
+}
+
+static int foot_heights_impl(hsqp_handle* h, int batch, double t, const double* x, int max_events, const int32_t* ne, const double* ev, const int32_t* seq, int n_knots,
+                             const double* tt, const double* ts, double offset, double* lift, double* touch, double* fxy, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_foot_heights_device" : "hsqp_foot_heights";
+  { const int rc = perceive_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (!x || !ne || !ev || !seq || !tt || !ts || !lift || !touch) return loop_bad(h, who, "null array");
+  if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
+  if (!std::isfinite(t)) return loop_bad(h, who, "t not finite");
+  if (!std::isfinite(offset)) return loop_bad(h, who, "touch_down_height_offset not finite");
+  if (max_events < 1) return loop_bad(h, who, "max_events < 1");
+  if (n_knots < 1) return loop_bad(h, who, "n_knots < 1");
+  if (!h->hdm.has_default_joint_state) return loop_bad(h, who, "no default joint state: call hsqp_set_default_joint_state first");
+  { const int rc = perceive_terrain_ok(h, who); if (rc != HSQP_OK) return rc; }
+  const size_t B = batch, E = max_events, K = n_knots;
+  if (!dev)
+    for (size_t b = 0; b < B; ++b)
+      if (ne[b] < 1 || ne[b] > max_events) return loop_bad(h, who, "n_events outside [1, max_events]");
+  HCHECK(hipSetDevice(h->device));
+  PerceiveArgs a{};
+  a.B = batch; a.E = max_events; a.K = n_knots; a.t = t; a.offset = offset;
+  StickyError step{h};
+  DEV_ENSURE(h->d_perceive_stage, perceive_stage_layout(Carve{}, B, E, K, !dev).bytes, "foot-height staging");
+  const PerceiveStage sg = perceive_stage_layout(Carve{h->d_perceive_stage.p}, B, E, K, !dev);
+  if (dev) {
+    a.x = x; a.ne = ne; a.ev = ev; a.seq = seq; a.tt = tt; a.ts = ts; a.lift = lift; a.touch = touch; a.fxy = fxy ? fxy : sg.fxy;
+  } else {
+    step(hipMemcpyAsync(sg.ne, ne, B * 4, hipMemcpyHostToDevice, h->stream), "upload n_events");
+    step(hipMemcpyAsync(sg.seq, seq, B * (E + 1) * 4, hipMemcpyHostToDevice, h->stream), "upload mode_sequence");
+    step(hipMemcpyAsync(sg.x, x, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x");
+    step(hipMemcpyAsync(sg.ev, ev, B * E * 8, hipMemcpyHostToDevice, h->stream), "upload event_times");
+    step(hipMemcpyAsync(sg.tt, tt, B * K * 8, hipMemcpyHostToDevice, h->stream), "upload target_times");
+    step(hipMemcpyAsync(sg.ts, ts, B * K * NX * 8, hipMemcpyHostToDevice, h->stream), "upload target_states");
+    a.x = sg.x; a.ne = sg.ne; a.ev = sg.ev; a.seq = sg.seq; a.tt = sg.tt; a.ts = sg.ts; a.lift = sg.lift; a.touch = sg.touch; a.fxy = sg.fxy;
+  }
+  if (step.rc == HSQP_OK) {
+    const int rc = launch_foot_heights(h, who, a);
+    if (rc != HSQP_OK) return rc;
+    step(hipGetLastError(), "k_foot_heights");
+  }
+  if (!dev) {
+    step(hipMemcpyAsync(lift, sg.lift, B * 2 * (E + 1) * 8, hipMemcpyDeviceToHost, h->stream), "download lift_off");
+    step(hipMemcpyAsync(touch, sg.touch, B * 2 * (E + 1) * 8, hipMemcpyDeviceToHost, h->stream), "download touch_down");
+    if (fxy) step(hipMemcpyAsync(fxy, sg.fxy, B * 4 * (E + 1) * 8, hipMemcpyDeviceToHost, h->stream), "download foothold_xy");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+int hsqp_foot_heights(hsqp_handle* h, int batch, double t, const double* x, int max_events, const int32_t* n_events, const double* event_times,
+                      const int32_t* mode_sequence, int n_knots, const double* target_times, const double* target_states, double touch_down_height_offset,
+                      double* lift_off, double* touch_down, double* foothold_xy) {
+  return foot_heights_impl(h, batch, t, x, max_events, n_events, event_times, mode_sequence, n_knots, target_times, target_states, touch_down_height_offset, lift_off,
+                           touch_down, foothold_xy, false);
+}
+int hsqp_foot_heights_device(hsqp_handle* h, int batch, double t, const double* d_x, int max_events, const int32_t* d_n_events, const double* d_event_times,
+                             const int32_t* d_mode_sequence, int n_knots, const double* d_target_times, const double* d_target_states,
+                             double touch_down_height_offset, double* d_lift_off, double* d_touch_down, double* d_foothold_xy) {
+  return foot_heights_impl(h, batch, t, d_x, max_events, d_n_events, d_event_times, d_mode_sequence, n_knots, d_target_times, d_target_states, touch_down_height_offset,
+                           d_lift_off, d_touch_down, d_foothold_xy, true);
+}
+
+int hsqp_loop_perceive(hsqp_handle* h, const hsqp_perceive_settings* ps) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = "hsqp_loop_perceive";
+  { const int rc = perceive_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  hsqp_handle::Loop& L = h->loop;
+  if (ps && ((ps->enabled != 0 && ps->enabled != 1) || ps->reserved != 0)) return loop_bad(h, who, "hsqp_perceive_settings::enabled must be 0 or 1 and reserved 0");
+  if (!ps || !ps->enabled) { L.perceive = false; return HSQP_OK; }
+  { const int rc = perceive_terrain_ok(h, who); if (rc != HSQP_OK) return rc; }
+  if (L.perceive) return HSQP_OK;   // (on already: the rows of the last cycle stay)
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = L.B, E = L.E;
+  DEV_ENSURE(h->d_perceive, perceive_layout(Carve{}, L, B, E), "loop foot-height rows");
+  const size_t bytes = perceive_layout(Carve{h->d_perceive.p}, L, B, E);
+  StickyError step{h};
+  step(hipMemsetAsync(h->d_perceive.p, 0, bytes, h->stream), "memset rows");
+  step(hipStreamSynchronize(h->stream), "sync");
+  if (step.rc != HSQP_OK) return step.rc;
+  L.perceive = true;
+  return HSQP_OK;
+}
+
+static int loop_foot_heights_impl(hsqp_handle* h, double* lift, double* touch, double* fxy, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_loop_foot_heights_device" : "hsqp_loop_foot_heights";
+  { const int rc = perceive_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  { const int rc = loop_started(h, who); if (rc != HSQP_OK) return rc; }
+  const hsqp_handle::Loop& L = h->loop;
+  if (!L.perceive) return loop_bad(h, who, "the per-foot swing heights are off (hsqp_loop_perceive; every hsqp_loop_start turns them off)");
+  HCHECK(hipSetDevice(h->device));
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t rows = (size_t)L.B * 2 * (size_t)(L.E + 1);
+  if (lift) HCHECK(hipMemcpyAsync(lift, L.pcv_lift, rows * 8, kind, h->stream));
+  if (touch) HCHECK(hipMemcpyAsync(touch, L.pcv_touch, rows * 8, kind, h->stream));
+  if (fxy) HCHECK(hipMemcpyAsync(fxy, L.pcv_fxy, rows * 2 * 8, kind, h->stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  return HSQP_OK;
+}
+int hsqp_loop_foot_heights(hsqp_handle* h, double* lift_off, double* touch_down, double* foothold_xy) { return loop_foot_heights_impl(h, lift_off, touch_down, foothold_xy, false); }
+int hsqp_loop_foot_heights_device(hsqp_handle* h, double* d_lift_off, double* d_touch_down, double* d_foothold_xy) {
+  return loop_foot_heights_impl(h, d_lift_off, d_touch_down, d_foothold_xy, true);
+}
 
 // ---- the observation model of the loop (include/hsqp_observe.h, csrc/hsqp_observe.h): the resident settings and table, the evaluation, the last observation
 void hsqp_observe_defaults(hsqp_observe_settings* s) { if (s) memset(s, 0, sizeof(*s)); }

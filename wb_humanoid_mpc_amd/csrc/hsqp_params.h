@@ -40,8 +40,13 @@ HSQP_HD int ev_upper(const double* ev, int n, double t) { int i = 0; while (i < 
 
 // One node's parameter record (HSQP_NODE_PARAMS doubles).  Returns false if a swing phase has no lift-off / touch-down
 // inside the schedule (the reference throws in that case).
+// lift_rows / touch_rows (both null, or both given: [2][row_stride], foot the outer index, phase the inner): the planner's three-argument update
+// (SwingTrajectoryPlanner.cpp:101-191, include/hsqp_perceive.h) — phase p of foot f reads lift_rows[f][p] and touch_rows[f][p] where the reference reads
+// liftOffHeightSequence[j][p] and touchDownHeightSequence[j][p]; touch_rows already holds touchDownHeightOffset.  Null: the two-argument form, the
+// constants `terrain` and `terrain + touch_down_height_offset`.
 HSQP_HD bool node_params_eval(const hsqp_swing_config& cfg, double terrain, int arm_swing, int n_ev, const double* ev, const int* seq,
-                              int n_knots, const double* tt, const double* ts /*[n_knots][NX]*/, double t, double* par) {
+                              int n_knots, const double* tt, const double* ts /*[n_knots][NX]*/, double t, double* par,
+                              const double* lift_rows = nullptr, const double* touch_rows = nullptr, int row_stride = 0) {
   const int n = n_ev + 1;           // number of phases
   const int p = ev_lower(ev, n_ev, t);
   const int mode = seq[p];
@@ -69,7 +74,8 @@ HSQP_HD bool node_params_eval(const hsqp_swing_config& cfg, double terrain, int 
   bool ok = true;
   for (int leg = 0; leg < 2; ++leg) {
     par[HSQP_P_CONTACT + leg] = mode_contact(mode, leg) ? 1.0 : 0.0;
-    double z[3] = {terrain, 0.0, 0.0}, ip[3] = {1.0, 0.0, 0.0};
+    const double lift = lift_rows ? lift_rows[(size_t)leg * row_stride + p] : terrain;
+    double z[3] = {lift, 0.0, 0.0}, ip[3] = {1.0, 0.0, 0.0};
     if (!mode_contact(mode, leg)) {
       int start = p - 1;
       while (start >= 0 && !mode_contact(seq[start], leg)) --start;
@@ -79,7 +85,7 @@ HSQP_HD bool node_params_eval(const hsqp_swing_config& cfg, double terrain, int 
       if (start < 0 || fin >= n - 1) { ok = false; }
       else {
         const double t0 = ev[start], t1 = ev[fin];
-        const double lift = terrain, touch = terrain + cfg.touch_down_height_offset, mp = cfg.impact_mid;
+        const double touch = touch_rows ? touch_rows[(size_t)leg * row_stride + p] : terrain + cfg.touch_down_height_offset, mp = cfg.impact_mid;
         const double scaling = fmin(1.0, (t1 - t0) / cfg.swing_time_scale);
         const bool before = mode_contact(seq[p - 1], leg), after = mode_contact(seq[p + 1], leg);
         if (before && after) {

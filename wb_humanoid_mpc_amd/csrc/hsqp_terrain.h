@@ -38,20 +38,23 @@ struct TerrainSet {
   double cell, ox, oy, cy, sy;
 };
 
+// instance b of the terrain, by the calling lane alone (no barrier): terrain_load's work, and a lane-per-instance kernel's whole load (csrc/hsqp_perceive.h)
+HSQP_HD void terrain_load_lane(const TerrainParams& tp, int b, TerrainSet& ts) {
+  const hsqp_terrain_placement pl = tp.place[b];
+  int m = pl.map;
+  m = m < -1 ? -1 : (m > tp.n_maps - 1 ? tp.n_maps - 1 : m);
+  if (m < 0) {
+    ts.H = nullptr; ts.nx = ts.ny = 2; ts.cell = 1.0; ts.ox = ts.oy = 0.0; ts.cy = 1.0; ts.sy = 0.0;
+  } else {
+    const TerrainMap mp = tp.maps[m];
+    ts.H = tp.pool + mp.first; ts.nx = mp.nx; ts.ny = mp.ny; ts.cell = mp.cell;
+    ts.ox = pl.origin_x; ts.oy = pl.origin_y; ts.cy = cos(pl.yaw); ts.sy = sin(pl.yaw);
+  }
+}
+
 // instance b of the terrain into the workspace.  Ends with a barrier.
 HSQP_HD void terrain_load(const Ctx& ctx, const TerrainParams& tp, int b, TerrainSet& ts) {
-  WG_FOR(ctx, i, 1) {
-    const hsqp_terrain_placement pl = tp.place[b];
-    int m = pl.map;
-    m = m < -1 ? -1 : (m > tp.n_maps - 1 ? tp.n_maps - 1 : m);
-    if (m < 0) {
-      ts.H = nullptr; ts.nx = ts.ny = 2; ts.cell = 1.0; ts.ox = ts.oy = 0.0; ts.cy = 1.0; ts.sy = 0.0;
-    } else {
-      const TerrainMap mp = tp.maps[m];
-      ts.H = tp.pool + mp.first; ts.nx = mp.nx; ts.ny = mp.ny; ts.cell = mp.cell;
-      ts.ox = pl.origin_x; ts.oy = pl.origin_y; ts.cy = cos(pl.yaw); ts.sy = sin(pl.yaw);
-    }
-  }
+  WG_FOR(ctx, i, 1) terrain_load_lane(tp, b, ts);
   WG_SYNC(ctx);
 }
 

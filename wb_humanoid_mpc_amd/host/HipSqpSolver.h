@@ -23,6 +23,7 @@
 #include "../../include/hsqp_metrics.h"
 #include "../../include/hsqp_grid.h"
 #include "../../include/hsqp_ground.h"
+#include "../../include/hsqp_perceive.h"
 #include "../../include/hsqp_push.h"
 #include "../../include/hsqp_plant.h"
 #include "../../include/hsqp_contact.h"
@@ -587,6 +588,53 @@ class HipSqpSolver {
     out.g.assign(loopBatch_, 0.0); out.footHeights.assign(2 * loopBatch_, 0.0);
     const int rc = hsqp_loop_ground_state(h_, out.g.data(), out.footHeights.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_ground_state failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return out;
+  }
+
+  /** Per-foot swing heights read from the resident height map (include/hsqp_perceive.h): for every instance and foot the lift-off and touch-down height
+   *  of every phase of its schedule, [batch][2][maxEvents + 1] each, and the footholds they were read at, [batch][2][maxEvents + 1][2], from the states
+   *  [batch][58] at time t, the mode schedules and the target knots ([batch][nKnots], [batch][nKnots][58]).  Needs maps and a placement table. */
+  struct FootHeights { std::vector<double> liftOff, touchDown, footholdXY; };
+  FootHeights footHeights(double t, const std::vector<double>& x, int maxEvents, const std::vector<int32_t>& nEvents, const std::vector<double>& eventTimes,
+                          const std::vector<int32_t>& modeSequence, int nKnots, const std::vector<double>& targetTimes, const std::vector<double>& targetStates,
+                          double touchDownHeightOffset) {
+    const size_t B = nEvents.size();
+    if (B == 0 || maxEvents < 1 || nKnots < 1 || x.size() != B * HSQP_NX || eventTimes.size() != B * (size_t)maxEvents || modeSequence.size() != B * (size_t)(maxEvents + 1) ||
+        targetTimes.size() != B * (size_t)nKnots || targetStates.size() != B * (size_t)nKnots * HSQP_NX)
+      throw std::runtime_error("[HipSqpSolver] footHeights: inconsistent array sizes");
+    FootHeights out;
+    const size_t rows = B * 2 * (size_t)(maxEvents + 1);
+    out.liftOff.assign(rows, 0.0); out.touchDown.assign(rows, 0.0); out.footholdXY.assign(2 * rows, 0.0);
+    const int rc = hsqp_foot_heights(h_, (int)B, t, x.data(), maxEvents, nEvents.data(), eventTimes.data(), modeSequence.data(), nKnots, targetTimes.data(),
+                                     targetStates.data(), touchDownHeightOffset, out.liftOff.data(), out.touchDown.data(), out.footholdXY.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_foot_heights failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    return out;
+  }
+  /** hsqp_upload_reference with the swing planner's three-argument update: liftOff, touchDown [batch][2][max_events + 1] in place of
+   *  reference.terrain_height (touchDown holds the touch-down height offset). */
+  void uploadReferenceHeights(const hsqp_problem& problem, const hsqp_reference& reference, const std::vector<double>& liftOff, const std::vector<double>& touchDown) {
+    const size_t rows = problem.batch < 1 || reference.max_events < 1 ? 0 : (size_t)problem.batch * 2 * (size_t)(reference.max_events + 1);
+    if (rows == 0 || liftOff.size() != rows || touchDown.size() != rows) throw std::runtime_error("[HipSqpSolver] uploadReferenceHeights: inconsistent array sizes");
+    const int rc = hsqp_upload_reference_heights(h_, &problem, &reference, liftOff.data(), touchDown.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_upload_reference_heights failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    loopBatch_ = 0;   // (every upload ends a loop)
+    shiftable_ = false;
+  }
+  /** The started loop reads every instance's per-foot lift-off and touch-down heights from the height map from its next cycle on (settings == nullptr or
+   *  enabled 0: off).  Off after every start. */
+  void setLoopPerception(const hsqp_perceive_settings* settings) {
+    const int rc = hsqp_loop_perceive(h_, settings);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_perceive failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** The rows of the loop's last completed cycle; maxEvents: that of the loop's schedule. */
+  FootHeights loopFootHeights(int maxEvents) {
+    if (loopBatch_ == 0) throw std::runtime_error("[HipSqpSolver] loopFootHeights: no loop started (startLoop, setLoopPerception)");
+    if (maxEvents < 1) throw std::runtime_error("[HipSqpSolver] loopFootHeights: maxEvents < 1");
+    FootHeights out;
+    const size_t rows = loopBatch_ * 2 * (size_t)(maxEvents + 1);
+    out.liftOff.assign(rows, 0.0); out.touchDown.assign(rows, 0.0); out.footholdXY.assign(2 * rows, 0.0);
+    const int rc = hsqp_loop_foot_heights(h_, out.liftOff.data(), out.touchDown.data(), out.footholdXY.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_foot_heights failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     return out;
   }
 

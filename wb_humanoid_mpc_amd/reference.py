@@ -111,9 +111,13 @@ class SplineCpg:
 
 
 class SwingTrajectoryPlanner:
-    """Per-leg z-height and impact-proximity splines over a mode schedule, flat terrain."""
+    """Per-leg z-height and impact-proximity splines over a mode schedule: flat terrain at terrain_height (the reference's two-argument update), or,
+    with lift and touch ([2][phases] each, foot the outer index), its three-argument update (SwingTrajectoryPlanner.cpp:101-191): phase p of leg j reads
+    lift[j][p] and touch[j][p]; touch already holds touchDownHeightOffset."""
 
-    def __init__(self, cfg, schedule, terrain_height=0.0):
+    def __init__(self, cfg, schedule, terrain_height=0.0, lift=None, touch=None):
+        assert (lift is None) == (touch is None)
+        rows, lift_rows, touch_rows = lift is not None, lift, touch
         self.schedule = schedule
         seq, ev = schedule.mode_sequence, schedule.event_times
         n = len(seq)
@@ -121,9 +125,9 @@ class SwingTrajectoryPlanner:
         self.impact = [[], []]
         for leg in range(2):
             flags = [mode_to_contact_flags(m)[leg] for m in seq]
-            lift = terrain_height
-            touch = terrain_height + cfg["touchDownHeightOffset"]
             for p in range(n):
+                lift = float(lift_rows[leg][p]) if rows else terrain_height
+                touch = float(touch_rows[leg][p]) if rows else terrain_height + cfg["touchDownHeightOffset"]
                 if flags[p]:
                     self.height[leg].append(SplineCpg((0.0, lift, 0.0), lift, (1.0, lift, 0.0)))
                     self.impact[leg].append(SplineCpg((0.0, 1.0, 0.0), 1.0, (1.0, 1.0, 0.0)))
@@ -248,9 +252,10 @@ def weight_compensating_input(model, flags):
     return u
 
 
-def build_node_params(model, schedule, targets, t0, dt, n_nodes, arm_swing=True):
-    """[N+1][HSQP_NODE_PARAMS] table for one instance on the uniform grid t_k = t0 + k dt."""
-    planner = SwingTrajectoryPlanner(model.swing, schedule)
+def build_node_params(model, schedule, targets, t0, dt, n_nodes, arm_swing=True, terrain_height=0.0, lift=None, touch=None):
+    """[N+1][HSQP_NODE_PARAMS] table for one instance on the uniform grid t_k = t0 + k dt.  lift, touch ([2][phases]): the planner's three-argument
+    update (include/hsqp_perceive.h) in place of terrain_height."""
+    planner = SwingTrajectoryPlanner(model.swing, schedule, terrain_height, lift, touch)
     par = np.zeros((n_nodes + 1, _abi.NODE_PARAMS))
     for k in range(n_nodes + 1):
         t = t0 + k * dt
@@ -454,9 +459,9 @@ def host_warm_start(total_mass, x_init, times, contact, prev=None, nx=_abi.NX):
     return x, u
 
 
-def build_node_params_at(model, schedule, targets, node_times, arm_swing=True):
+def build_node_params_at(model, schedule, targets, node_times, arm_swing=True, terrain_height=0.0, lift=None, touch=None):
     """build_node_params on explicit node times (non-uniform grid / event nodes)."""
-    planner = SwingTrajectoryPlanner(model.swing, schedule)
+    planner = SwingTrajectoryPlanner(model.swing, schedule, terrain_height, lift, touch)
     par = np.zeros((len(node_times), _abi.NODE_PARAMS))
     for k, t in enumerate(node_times):
         flags = mode_to_contact_flags(schedule.mode_at(t))
@@ -531,6 +536,58 @@ def body_placements(model, q):
         R[i] = R[par] @ np.array(b["R"]).reshape(3, 3) @ _rot_axis(b["axis"], q[5 + i])
         p[i] = p[par] + R[par] @ np.array(b["p"])
     return R, p
+
+
+def contact_frame_xy(model, q, f):
+    """World xy of contact frame f at q = [p_b, eulerZYX, q_j]."""
+    R, p = body_placements(model, q)
+    fr = model.raw["frames"]["contact"][f]
+    return (p[fr["body"]] + R[fr["body"]] @ np.array(fr["p"], dtype=float))[:2]
+
+
+def foot_height_sequences(model, x, t, schedule, targets, ground, offset=None):
+    """The rule of include/hsqp_perceive.h for one instance (OURS, not the reference's): (lift[2][n], touch[2][n], foothold_xy[2][n][2]) over the n
+    phases of `schedule` from the state x at time t; targets: the TargetTrajectories; ground(X, Y): the instance's ground height under a world point
+    (hsqp_terrain_eval's answer); offset: touchDownHeightOffset (None: the model's).  A contact run that began at or before the phase of t stands where
+    the foot is; a run ahead lands where the targets carry the nominal foothold (the contact frame at the default joint state, base at the origin) at
+    its touch-down time.  A non-finite state: NaN rows."""
+    offset = model.swing["touchDownHeightOffset"] if offset is None else offset
+    seq, ev = schedule.mode_sequence, schedule.event_times
+    n = len(seq)
+    lift, touch, fxy = np.zeros((2, n)), np.zeros((2, n)), np.zeros((2, n, 2))
+    x = np.asarray(x, dtype=float)
+    if not np.isfinite(x).all():
+        return lift + np.nan, touch + np.nan, fxy + np.nan
+    p_now = schedule.index_at(t)
+    nv = 6 + model.nj
+    q_nominal = np.concatenate([np.zeros(6), model.default_joint_state])
+    for f in range(2):
+        c = [mode_to_contact_flags(m)[f] for m in seq]
+        P, o = contact_frame_xy(model, x[:nv], f), contact_frame_xy(model, q_nominal, f)
+        h_run, F_run = [None] * n, [None] * n
+        for p in range(n):
+            if not c[p]:
+                continue
+            if p > 0 and c[p - 1]:
+                h_run[p], F_run[p] = h_run[p - 1], F_run[p - 1]
+                continue
+            if p <= p_now:
+                F = P
+            else:
+                d = targets.desired_state(ev[p - 1])
+                X, Y, psi = d[0], d[1], d[3]
+                F = np.array([X + math.cos(psi) * o[0] - math.sin(psi) * o[1], Y + math.sin(psi) * o[0] + math.cos(psi) * o[1]])
+            h_run[p], F_run[p] = ground(F[0], F[1]), F
+        for p in range(n):
+            if c[p]:
+                lift[f, p], touch[f, p], fxy[f, p] = h_run[p], h_run[p] + offset, F_run[p]
+                continue
+            before = next((q for q in range(p - 1, -1, -1) if c[q]), None)
+            after = next((q for q in range(p + 1, n) if c[q]), None)
+            lift[f, p] = h_run[before] if before is not None else ground(P[0], P[1])
+            touch[f, p] = (h_run[after] if after is not None else lift[f, p]) + offset
+            fxy[f, p] = F_run[after] if after is not None else P
+    return lift, touch, fxy
 
 
 def euler_rate_axes(q):

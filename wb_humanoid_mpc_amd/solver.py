@@ -221,6 +221,16 @@ def load_library():
     lib.hsqp_loop_ground.argtypes = [C.c_void_p, _gs, _dp]
     lib.hsqp_loop_ground_state.argtypes = [C.c_void_p, _dp, _dp]
     lib.hsqp_loop_ground_state_device.argtypes = [C.c_void_p, _dp, _dp]
+    # include/hsqp_perceive.h
+    _ps = C.POINTER(_abi.PerceiveSettings)
+    lib.hsqp_perceive_defaults.argtypes = [_ps]
+    lib.hsqp_perceive_defaults.restype = None
+    lib.hsqp_upload_reference_heights.argtypes = [C.c_void_p, C.POINTER(_abi.Problem), C.POINTER(_abi.Reference), _dp, _dp]
+    lib.hsqp_foot_heights.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, C.c_int, _ip, _dp, _ip, C.c_int, _dp, _dp, C.c_double, _dp, _dp, _dp]
+    lib.hsqp_foot_heights_device.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, C.c_int, _ip, _dp, _ip, C.c_int, _dp, _dp, C.c_double, _dp, _dp, _dp]
+    lib.hsqp_loop_perceive.argtypes = [C.c_void_p, _ps]
+    lib.hsqp_loop_foot_heights.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    lib.hsqp_loop_foot_heights_device.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.hsqp_linesearch_defaults.argtypes = [C.POINTER(_abi.LinesearchSettings)]
     lib.hsqp_linesearch_defaults.restype = None
     lib.hsqp_set_linesearch.argtypes = [C.c_void_p, C.POINTER(_abi.LinesearchSettings)]
@@ -399,7 +409,7 @@ class HipSqpSolver:
                                target_states, swing, terrain_height, arm_swing, node_times, warm)
 
     def _upload_reference(self, B, N, x_init, x_traj, u_traj, dt, t0, n_events, event_times, mode_sequence, target_times, target_states,
-                          swing, terrain_height, arm_swing, node_times, warm, terrain_heights=None):
+                          swing, terrain_height, arm_swing, node_times, warm, terrain_heights=None, heights=None):
         n_events = np.ascontiguousarray(n_events, dtype=np.int32)
         mode_sequence = np.ascontiguousarray(mode_sequence, dtype=np.int32)
         event_times, target_times, target_states = _c(event_times), _c(target_times), _c(target_states)
@@ -416,7 +426,12 @@ class HipSqpSolver:
                            n_knots=target_times.shape[1], target_times=target_times.ctypes.data_as(_dp),
                            target_states=target_states.ctypes.data_as(_dp), swing=swing, terrain_height=terrain_height,
                            arm_swing=1 if arm_swing else 0, warm_start=warm)
-        if terrain_heights is None:
+        if heights is not None:   # include/hsqp_perceive.h: one lift-off and one touch-down height per foot and phase
+            lift, touch = (_c(a) for a in heights)
+            if lift.shape != (B, 2, event_times.shape[1] + 1) or touch.shape != lift.shape:
+                raise ValueError("lift_off and touch_down must be [B][2][max_events + 1]")
+            self._check(self.lib.hsqp_upload_reference_heights(self.h, C.byref(p), C.byref(r), lift.ctypes.data_as(_dp), touch.ctypes.data_as(_dp)))
+        elif terrain_heights is None:
             self._check(self.lib.hsqp_upload_reference(self.h, C.byref(p), C.byref(r)))
         else:   # include/hsqp_ground.h: one terrain height per instance
             th = _c(np.broadcast_to(np.asarray(terrain_heights, dtype=np.float64), (B,)))
@@ -1041,7 +1056,7 @@ class HipSqpSolver:
             self._loop_batch = 0
             self._check(self.lib.hsqp_loop_start_gait(self.h, C.byref(settings), C.byref(gait), B, C.c_double(t0), x0.ctypes.data_as(_dp), v_cmd.ctypes.data_as(_dp)))
             self._loop_batch = self._gait_batch = B
-            self._gait_events = int(gait.max_events)
+            self._gait_events = self._loop_events = int(gait.max_events)
             self._shape = (B, int(settings.n_nodes))
             self._loop_nodes = int(settings.n_nodes)
             return
@@ -1056,6 +1071,7 @@ class HipSqpSolver:
         self._check(self.lib.hsqp_loop_start(self.h, C.byref(settings), B, C.c_double(t0), x0.ctypes.data_as(_dp), v_cmd.ctypes.data_as(_dp), event_times.shape[1],
                                              n_events.ctypes.data_as(ip), event_times.ctypes.data_as(_dp), mode_sequence.ctypes.data_as(ip)))
         self._loop_batch = B
+        self._loop_events = int(event_times.shape[1])
         self._shape = (B, int(settings.n_nodes))
         self._loop_nodes = int(settings.n_nodes)
 
@@ -1315,6 +1331,77 @@ class HipSqpSolver:
     def loop_ground_state_device(self, g_ptr=0, foot_z_ptr=0):
         cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
         self._check(self.lib.hsqp_loop_ground_state_device(self.h, cast(g_ptr), cast(foot_z_ptr)))
+
+    # ---- include/hsqp_perceive.h: per-foot swing heights read from the height map
+    def perceive_settings(self, enabled=True):
+        """hsqp_perceive_settings: hsqp_perceive_defaults (on) with the given value."""
+        st = _abi.PerceiveSettings()
+        self.lib.hsqp_perceive_defaults(C.byref(st))
+        st.enabled = int(enabled)
+        return st
+
+    def foot_heights(self, x, t, n_events, event_times, mode_sequence, target_times, target_states, touch_down_height_offset):
+        """hsqp_foot_heights: (lift_off[B, 2, E + 1], touch_down[B, 2, E + 1], foothold_xy[B, 2, E + 1, 2]) — for every instance and foot the lift-off and
+        touch-down height of every phase of its schedule, read from the resident height map under the foot (a contact run that has begun) or under the
+        foothold the targets carry to its touch-down time (a run ahead), from the state x [B][58] at time t."""
+        x = _c(np.atleast_2d(x))
+        B = x.shape[0]
+        n_events, mode_sequence, event_times = np.ascontiguousarray(n_events, dtype=np.int32), np.ascontiguousarray(mode_sequence, dtype=np.int32), _c(event_times)
+        target_times, target_states = _c(target_times), _c(target_states)
+        if (x.shape != (B, _abi.NX) or n_events.shape != (B,) or event_times.ndim != 2 or event_times.shape[0] != B or mode_sequence.shape != (B, event_times.shape[1] + 1)
+                or target_times.ndim != 2 or target_times.shape[0] != B or target_states.shape != (B, target_times.shape[1], _abi.NX)):
+            raise ValueError("inconsistent foot-height array shapes")
+        E = event_times.shape[1]
+        lift, touch, fxy = np.zeros((B, 2, E + 1)), np.zeros((B, 2, E + 1)), np.zeros((B, 2, E + 1, 2))
+        self._check(self.lib.hsqp_foot_heights(self.h, B, C.c_double(t), x.ctypes.data_as(_dp), E, n_events.ctypes.data_as(_ip), event_times.ctypes.data_as(_dp),
+                                               mode_sequence.ctypes.data_as(_ip), target_times.shape[1], target_times.ctypes.data_as(_dp),
+                                               target_states.ctypes.data_as(_dp), C.c_double(touch_down_height_offset), lift.ctypes.data_as(_dp),
+                                               touch.ctypes.data_as(_dp), fxy.ctypes.data_as(_dp)))
+        return lift, touch, fxy
+
+    def foot_heights_device(self, batch, t, x_ptr, max_events, n_events_ptr, event_times_ptr, mode_sequence_ptr, n_knots, target_times_ptr, target_states_ptr,
+                            touch_down_height_offset, lift_off_ptr, touch_down_ptr, foothold_xy_ptr=0):
+        """hsqp_foot_heights_device: the same with every array in device memory (addresses)."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        icast = lambda a: C.cast(C.c_void_p(int(a)), _ip) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_foot_heights_device(self.h, int(batch), C.c_double(t), cast(x_ptr), int(max_events), icast(n_events_ptr), cast(event_times_ptr),
+                                                      icast(mode_sequence_ptr), int(n_knots), cast(target_times_ptr), cast(target_states_ptr),
+                                                      C.c_double(touch_down_height_offset), cast(lift_off_ptr), cast(touch_down_ptr), cast(foothold_xy_ptr)))
+
+    def upload_reference_heights(self, x_init, n_nodes, dt, t0, n_events, event_times, mode_sequence, target_times, target_states, swing, lift_off, touch_down,
+                                 arm_swing=True, mode="cold", node_times=None, x_traj=None, u_traj=None):
+        """hsqp_upload_reference_heights: upload_reference_warm (mode "shift" / "cold") or, with x_traj and u_traj, upload_reference, with the planner's
+        three-argument update: lift_off, touch_down [B][2][max_events + 1] in place of the reference's terrain_height (touch_down holds the offset)."""
+        x_init = _c(np.atleast_2d(x_init))
+        caller = x_traj is not None
+        warm = _abi.WARM_CALLER if caller else {"shift": _abi.WARM_SHIFT, "cold": _abi.WARM_COLD}[mode]
+        if caller:
+            x_traj, u_traj = _c(x_traj), _c(u_traj)
+            if x_traj.ndim == 2:
+                x_traj, u_traj = x_traj[None], u_traj[None]
+        self._upload_reference(x_init.shape[0], int(n_nodes), x_init, x_traj, u_traj, dt, t0, n_events, event_times, mode_sequence, target_times, target_states,
+                               swing, 0.0, arm_swing, node_times, warm, heights=(lift_off, touch_down))
+
+    def loop_perceive(self, settings=None, on=True):
+        """hsqp_loop_perceive on the started loop: from the next cycle step 2 takes every instance's per-foot lift-off and touch-down heights from the
+        resident height map (settings: perceive_settings()).  on=False: off again."""
+        if not on:
+            self._check(self.lib.hsqp_loop_perceive(self.h, None))
+            return
+        settings = self.perceive_settings() if settings is None else settings
+        self._check(self.lib.hsqp_loop_perceive(self.h, C.byref(settings)))
+
+    def loop_foot_heights(self):
+        """hsqp_loop_foot_heights: (lift_off[B, 2, E + 1], touch_down[B, 2, E + 1], foothold_xy[B, 2, E + 1, 2]) of the last completed cycle; E the
+        max_events of the loop's schedule (a resident gait: its settings')."""
+        B, E = max(self._loop_batch, 1), max(getattr(self, "_loop_events", 1), 1)
+        lift, touch, fxy = np.zeros((B, 2, E + 1)), np.zeros((B, 2, E + 1)), np.zeros((B, 2, E + 1, 2))
+        self._check(self.lib.hsqp_loop_foot_heights(self.h, lift.ctypes.data_as(_dp), touch.ctypes.data_as(_dp), fxy.ctypes.data_as(_dp)))
+        return lift, touch, fxy
+
+    def loop_foot_heights_device(self, lift_off_ptr=0, touch_down_ptr=0, foothold_xy_ptr=0):
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_loop_foot_heights_device(self.h, cast(lift_off_ptr), cast(touch_down_ptr), cast(foothold_xy_ptr)))
 
     # ---- include/hsqp_gait.h: per-instance gait schedule and ladder
     def gait_reset(self, settings, batch, t0=0.0):
