@@ -50,7 +50,9 @@
  * settings pointer, an unknown on_failure, NaN bounds, min_base_height > max_base_height, max_tilt < 0, a non-finite x_reset / x0 / v_cmd
  * (host arrays), n < 1, NULL ids, ids outside [0, B) or repeated, hsqp_loop_reset_instances / hsqp_loop_episodes without hsqp_loop_isolate.
  *
- * Out of scope: fall detection beyond the caller's box, per-instance loop time, centroidal handles, several GPUs.  (On the event-node
+ * On a loop started by hsqp_loop_start_centroidal (include/hsqp_cent_loop.h) the box is read at the centroidal pose (x[8], x[10], x[11]), a parked
+ * instance's stance command takes x_reset[8], and x_reset / x0 rows must have zero padding.
+ * Out of scope: fall detection beyond the caller's box, per-instance loop time, several GPUs.  (On the event-node
  * grid of include/hsqp_grid.h an instance whose schedule overflows the grid stops the cycle for all: it is a fault of the schedule, not of an episode.)
  * The base-height box is absolute unless include/hsqp_ground.h (box_above_ground) puts it on the height above the estimated ground.
  *

@@ -8,7 +8,7 @@
  *  (2) the cycle itself — targets, hsqp_upload_reference with the device-built warm start, hsqp_iterate_device,
  *      hsqp_rollout_policy_device over one MPC period, the rolled-out state as the next measured state: hsqp_loop_*.
  * Whole-body handles only: on a centroidal handle every entry point below returns HSQP_ERR_BAD_ARG with a message saying so (its generator
- * needs the base velocity from the centroidal momentum).
+ * needs the base velocity from the centroidal momentum); the centroidal forms are in include/hsqp_cent_loop.h.
  *
  * ---- velocity-command targets
  * v_cmd [B][4] = {vx, vy, height, yaw rate} (WalkingVelocityCommand::toVector), v_filt [B][4] the filter state (in / out), x0 [B][58]:
@@ -60,7 +60,8 @@
  * per-instance ground-height estimate from the stance feet.
  * The swing references take that one height for both feet, lift-off and touch-down alike, unless include/hsqp_perceive.h switches the started loop to
  * per-foot lift-off and touch-down heights read from the resident height maps.
- * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, the centroidal formulation, several GPUs.
+ * Out of scope: the motion manager's own BreakFrequencyAlphaFilter in front of the generator, several GPUs.  The centroidal formulation:
+ * hsqp_centroidal_command_targets and hsqp_loop_start_centroidal of include/hsqp_cent_loop.h, after which the run / command / state calls below work.
  *
  * ABI: additions only — no public struct and no entry point of hsqp.h, hsqp_feedback.h or hsqp_rollout.h changes, HSQP_ABI_VERSION stays.
  */

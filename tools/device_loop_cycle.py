@@ -81,7 +81,14 @@ reports the rungs at the end; walk: --commands from the start (feet lift about o
 --isolate: hsqp_loop_isolate (include/hsqp_episode.h) behind the start, with the bounds off: every cycle also runs the triage (and, with --gait, the
 per-instance gait reset); the line reports the episode counters at the end.
 --commands same: every instance is commanded (0.3, 0, 0.7925, 0), the other tool's command; spread: vx from 0 to 0.6 m/s and yaw rates from
--0.2 to 0.2 rad/s across the batch.
+-0.2 to 0.2 rad/s across the batch; stand: (0, 0, 0.7925, 0), with --schedule stance a standing robot.
+--formulation centroidal: the loop of include/hsqp_cent_loop.h on the centroidal model (BASELINE configs 1-2; dt from the model's sqp block, --period as
+given).  The line carries the per-cycle time of the resident loop (`cycle_ms_*`: one hsqp_loop_run(1) per cycle; `run_ms_per_cycle`: one call for all) and,
+from the same run, of the same cycles driven from the host through the public calls (`driven_ms_*`: hsqp_centroidal_command_targets,
+hsqp_upload_reference with the device-built warm start, hsqp_iterate_device, hsqp_rollout_policy).  --isolate, --with-push and --push work; the plant,
+contact, actuator, inertia, terrain, gait, event-grid, ground, perceive, observe and metrics options are whole-body only and refused up front.
+A cycle the MPC does not survive (HSQP_ERR_NUMERIC) ends the driven or the resident part there; the line says where (`driven_stopped`, `resident_stopped`,
+`run_stopped`) and the times are those of the cycles that ran.  profiles/cent_loop.txt: the walk at 0.3 m/s on the 2 s horizon does not survive.
 """
 import argparse
 import json
@@ -94,12 +101,29 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from wb_humanoid_mpc_amd import load_model  # noqa: E402
-from wb_humanoid_mpc_amd.reference import gait_settings, pack_reference, tile_gait, velocity_command_targets  # noqa: E402
+from wb_humanoid_mpc_amd.reference import (centroidal_velocity_command_targets, gait_settings, pack_reference, pad_targets, swing_config, tile_gait,  # noqa: E402
+                                           velocity_command_targets)
 from wb_humanoid_mpc_amd.solver import HipSqpSolver  # noqa: E402
 
 
+def padded_state(m):
+    """The model's initial state as a [58] row (centroidal: 35 live entries, zero padding)."""
+    x = np.zeros(58)
+    x[:len(m.initial_state)] = m.initial_state
+    return x
+
+
+def dummy_knots(m, cent, t_final):
+    """Knots for pack_reference (only the schedules are taken from its result)."""
+    if cent:
+        return pad_targets(centroidal_velocity_command_targets(m, (0.3, 0.0, 0.7925, 0.0), 0.0, m.initial_state, t_final))
+    return velocity_command_targets(m, (0.3, 0.0, 0.7925, 0.0), 0.0, m.initial_state, t_final)
+
+
 def push_sweep(args):
-    m = load_model()
+    cent = args.formulation == "centroidal"
+    m = load_model(formulation="centroidal") if cent else load_model()
+    pose = 6 if cent else 0                                    # where the base pose starts in a state row
     given = {a.split("=")[0] for a in sys.argv[1:]}
     B = args.batch if "--batch" in given else 16
     N = args.nodes if "--nodes" in given else 40
@@ -107,9 +131,9 @@ def push_sweep(args):
     dt = m.sqp["dt"]
     t_final = cycles * args.period + N * dt + 1.0
     schedule = tile_gait(m.gaits["walk"], 0.3, t_final)
-    knots = velocity_command_targets(m, (0.3, 0.0, 0.7925, 0.0), 0.0, m.initial_state, t_final)
+    knots = dummy_knots(m, cent, t_final)
     n_events, event_times, mode_sequence = pack_reference([schedule] * B, [knots] * B)[:3]
-    x_init = np.tile(m.initial_state, (B, 1))
+    x_init = np.tile(padded_state(m), (B, 1))
     cmd = np.tile((0.3, 0.0, 0.7925, 0.0), (B, 1))
     force = args.push_max * np.arange(B) / max(B - 1, 1)
     pushes = [[dict(body=0, t_start=args.push_at, duration=args.push_for, point=(0.0, 0.0, 0.0), force=(0.0, f, 0.0))] for f in force]
@@ -135,7 +159,7 @@ def push_sweep(args):
             r = s.loop_run(cycles)
             ep = s.loop_episodes()
             x = r["x"]                                         # [cycle][instance][58], NaN rows once parked
-            sway = np.nanmax(np.abs(x[:, :, 1] - x[:, :1, 1]), axis=0)
+            sway = np.nanmax(np.abs(x[:, :, pose + 1] - x[:, :1, pose + 1]), axis=0)
             rows[controller] = (ep, sway)
             if args.contact:                                   # ground reaction at every logged state (parked rows: no force)
                 fn_peak, ratio_peak = np.zeros(B), np.zeros(B)
@@ -268,7 +292,7 @@ def main():
     ap.add_argument("--nodes", type=int, default=100)
     ap.add_argument("--period", type=float, default=1.0 / 60.0)
     ap.add_argument("--controller", default="feedforward", choices=("feedforward", "feedback"))
-    ap.add_argument("--commands", default="same", choices=("same", "spread"))
+    ap.add_argument("--commands", default="same", choices=("same", "spread", "stand"))
     ap.add_argument("--filter-alpha", type=float, default=0.8)
     ap.add_argument("--gait", default=None, choices=("ladder", "walk"))
     ap.add_argument("--isolate", default=None, choices=("park", "reset"))
@@ -302,10 +326,11 @@ def main():
     ap.add_argument("--obs-seed", type=int, default=2026)
     ap.add_argument("--metrics", action="store_true")
     ap.add_argument("--event-grid", type=int, nargs="?", const=32, default=None, metavar="EVENT_NODES")
-    ap.add_argument("--schedule", default="walk", choices=("walk", "run"))
+    ap.add_argument("--schedule", default="walk", choices=("walk", "run", "stance"))
     ap.add_argument("--ground-adapt", nargs="?", const="on", default=None, choices=("on", "off"))
     ap.add_argument("--box-above-ground", action="store_true")
     ap.add_argument("--perceive", action="store_true")
+    ap.add_argument("--formulation", default="wb", choices=("wb", "centroidal"))
     ap.add_argument("--push-max", type=float, default=400.0)
     ap.add_argument("--push-at", type=float, default=0.5)
     ap.add_argument("--push-for", type=float, default=0.2)
@@ -327,8 +352,17 @@ def main():
         ap.error("--perceive requires --terrain (the swing heights are read from the resident height maps)")
     if args.box_above_ground and args.ground_adapt != "on":
         ap.error("--box-above-ground belongs to --ground-adapt (the box stands on the estimated ground)")
+    if args.formulation == "centroidal":
+        wb_only = [o for o, on in (("--plant", args.plant), ("--contact", args.contact), ("--actuator", args.actuator), ("--inertia", args.inertia), ("--terrain", args.terrain),
+                                   ("--gait", args.gait), ("--event-grid", args.event_grid is not None), ("--ground-adapt", args.ground_adapt), ("--perceive", args.perceive),
+                                   ("--observe", args.observe), ("--metrics", args.metrics)) if on]
+        if wb_only:
+            ap.error("--formulation centroidal: " + ", ".join(wb_only) + " act on whole-body handles only (include/hsqp_cent_loop.h lists what the centroidal loop has)")
     if args.push:
         return push_sweep(args)
+    if args.formulation == "centroidal":
+        print(json.dumps(centroidal_run(args)))
+        return
     line = timed_run(args, args.observe)
     if args.observe:
         off = timed_run(args, False)
@@ -373,6 +407,95 @@ def metrics_report(s, args, ep):
     return sm, cur, prev
 
 
+def centroidal_run(args):
+    """The centroidal loop (include/hsqp_cent_loop.h): resident cycles and, from the same run, the same cycles driven by the public calls."""
+    m = load_model(formulation="centroidal")
+    B, N, dt = args.batch, args.nodes, m.sqp["dt"]
+    total = args.warmup + 2 * args.cycles
+    t_final = 2 * total * args.period + N * dt + 1.0
+    schedules = [tile_gait(m.gaits[args.schedule], 0.3 + 0.5 * b / B, t_final) for b in range(B)]
+    n_events, event_times, mode_sequence = pack_reference(schedules, [dummy_knots(m, True, t_final)] * B)[:3]
+    rng = np.random.default_rng(20250808)
+    x_init = np.tile(padded_state(m), (B, 1))
+    x_init[:, 12:12 + m.nj] += 0.01 * rng.standard_normal((B, m.nj))
+    cmd = np.tile((0.3, 0.0, 0.7925, 0.0), (B, 1))
+    if args.commands == "spread":
+        cmd[:, 0] = np.linspace(0.0, 0.6, B)
+        cmd[:, 3] = np.linspace(-0.2, 0.2, B)
+    if args.commands == "stand":
+        cmd[:, 0] = 0.0
+    # (no persistent back-off of the KKT gate: the driven and the resident cycles share this handle and must take the same sweeps)
+    s = HipSqpSolver(m, max_nodes=N, max_batch=B, linesearch=True, riccati="serial" if args.isolate else "auto")
+    st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True, controller=args.controller)
+    sw = swing_config(m)
+    cycle_ms, driven_ms, heights = [], [], []
+    try:
+        if args.with_push is not None:
+            s.set_pushes([[dict(body=0, t_start=0.0, duration=1e6, point=(0.0, 0.0, 0.0), force=(0.0, args.with_push, 0.0))]] * B)
+        # the cycles driven from the host through the public calls
+        from wb_humanoid_mpc_amd.solver import HsqpError
+        x, vf, t = x_init.copy(), cmd.copy(), 0.0
+        driven_stopped = resident_stopped = None
+        for c in range(args.warmup + args.cycles):
+            t_a = time.perf_counter()
+            try:
+                tt, ts, vf = s.command_targets(cmd, x, t, N * dt, filter_alpha=args.filter_alpha, v_filt=vf)
+                s.upload_reference_warm(x, N, dt, t, n_events, event_times, mode_sequence, tt, ts, sw, mode="cold" if c == 0 else "shift")
+                s.iterate(1, take_step=True, linesearch=True)
+                x = s.rollout_policy(np.zeros(B), x, args.period, 1, controller=args.controller)["x"][:, 0].copy()
+            except HsqpError as e:
+                driven_stopped = f"cycle {c}: {e}"
+                break
+            t_b = time.perf_counter()
+            t += args.period
+            if c >= args.warmup:
+                driven_ms.append(1e3 * (t_b - t_a))
+        driven_x, driven_cycles = x, c + (driven_stopped is None)
+        # the resident loop
+        s.loop_start(st, 0.0, x_init, cmd, n_events, event_times, mode_sequence)
+        if args.isolate:
+            s.loop_isolate(s.episode_settings(args.isolate))
+        same = None
+        for c in range(args.warmup + args.cycles):
+            t_a = time.perf_counter()
+            try:
+                r = s.loop_run(1)
+            except HsqpError as e:
+                resident_stopped = f"cycle {c}: {e}"
+                break
+            t_b = time.perf_counter()
+            heights.append(r["x"][0, :, 8].copy())
+            if c >= args.warmup:
+                cycle_ms.append(1e3 * (t_b - t_a))
+            if c + 1 == driven_cycles:                            # the state after as many cycles as the driven part completed
+                same = bool(np.array_equal(r["x"][0], driven_x))
+        t_a = time.perf_counter()
+        done, stopped = 0, None
+        try:
+            if resident_stopped is None:
+                done = s.loop_run(args.cycles, log=False)["cycles_done"]
+        except HsqpError as e:
+            done, stopped = e.result["cycles_done"], str(e)
+        run_ms = 1e3 * (time.perf_counter() - t_a) / max(done, 1)
+        t_end, x_end, _ = s.loop_state()
+        ep = s.loop_episodes() if args.isolate else None
+    finally:
+        s.close()
+    heights = np.concatenate(heights + [x_end[:, 8]])
+    stat = lambda v, f: round(float(f(v)), 3) if len(v) else None  # noqa: E731
+    q = [stat(cycle_ms, lambda v: np.percentile(v, 25)), stat(cycle_ms, lambda v: np.percentile(v, 75))]
+    qd = [stat(driven_ms, lambda v: np.percentile(v, 25)), stat(driven_ms, lambda v: np.percentile(v, 75))]
+    return {"metric": "device_loop_cycle", "formulation": "centroidal", "batch": B, "nodes": N, "dt": dt, "period": args.period, "cycles": args.cycles,
+            "controller": args.controller, "commands": args.commands, "filter_alpha": args.filter_alpha, "isolate": args.isolate, "with_push": args.with_push,
+            "episodes": {"failed_now": int((ep["state"] != 0).sum()), "failures": int(ep["n_failures"].sum()), "episodes": int(ep["n_episodes"].sum())} if ep else None,
+            "schedule": args.schedule,
+            "cycle_ms_median": stat(cycle_ms, np.median), "cycle_ms_mean": stat(cycle_ms, np.mean), "cycle_ms_quartiles": q, "cycle_ms_min": stat(cycle_ms, np.min),
+            "run_ms_per_cycle": round(float(run_ms), 3) if done else None, "run_cycles_done": int(done), "run_stopped": stopped,
+            "driven_ms_median": stat(driven_ms, np.median), "driven_ms_mean": stat(driven_ms, np.mean), "driven_ms_quartiles": qd, "driven_ms_min": stat(driven_ms, np.min),
+            "driven_stopped": driven_stopped, "resident_stopped": resident_stopped, "resident_equals_driven": same, "t_end": round(float(t_end), 6), "finite": bool(np.isfinite(x_end).all()),
+            "base_height_range": [round(float(np.nanmin(heights)), 5), round(float(np.nanmax(heights)), 5)]}
+
+
 def timed_run(args, observe):
     """The timed loop (with the observation model of --observe on or off): the fields of the JSON line."""
     m = load_model()
@@ -388,6 +511,8 @@ def timed_run(args, observe):
     if args.commands == "spread":
         cmd[:, 0] = np.linspace(0.0, 0.6, B)
         cmd[:, 3] = np.linspace(-0.2, 0.2, B)
+    if args.commands == "stand":
+        cmd[:, 0] = 0.0
     s = HipSqpSolver(m, max_nodes=N + (args.event_grid or 0), max_batch=B, linesearch=True)
     s.set_scan_backoff_persistent(True)
     st = s.loop_settings(N, dt, period=args.period, filter_alpha=args.filter_alpha, iterations=1, take_step=True, linesearch=True,

@@ -126,6 +126,8 @@ CMD_N, CMD_KNOTS = 4, 3   # HSQP_CMD_N, HSQP_CMD_KNOTS
 # entry points of include/hsqp_loop.h (tests/test_loop.py checks that the library exports each of them and the binding declares it)
 LOOP_ENTRY_POINTS = ("hsqp_set_default_joint_state", "hsqp_command_targets", "hsqp_command_targets_device", "hsqp_loop_defaults", "hsqp_loop_start",
                      "hsqp_loop_command", "hsqp_loop_command_device", "hsqp_loop_run", "hsqp_loop_run_device", "hsqp_loop_state", "hsqp_loop_state_device")
+# entry points of include/hsqp_cent_loop.h (tests/test_cent_loop.py)
+CENT_LOOP_ENTRY_POINTS = ("hsqp_centroidal_command_targets", "hsqp_centroidal_command_targets_device", "hsqp_loop_start_centroidal")
 
 # include/hsqp_gait.h
 GAIT_MAX_RUNGS, GAIT_MAX_PHASES, GAIT_MAX_EVENTS, GAIT_NAME_LEN = 16, 6, 256, 16

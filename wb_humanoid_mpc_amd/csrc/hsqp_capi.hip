@@ -23,6 +23,8 @@
 #include "hsqp_rollout.h"
 #include "hsqp_loop.h"
 #include "../../include/hsqp_loop.h"
+#include "hsqp_cent_loop.h"
+#include "../../include/hsqp_cent_loop.h"
 #include "hsqp_gait.h"
 #include "hsqp_grid.h"
 #include "hsqp_ground.h"
@@ -816,6 +818,19 @@ __global__ __launch_bounds__(CMDT_THREADS) void k_command_targets(const DevModel
   if (live) command_item_store(it, dm->default_joint_state, x0, t0, horizon, id, v_filt, tt, ts);
 }
 
+// ---- velocity-command targets of the centroidal formulation (hsqp_cent_loop.h): one wave per instance on a CentWST<false> workspace in LDS (the launch shape of
+// k_params_cent_torso and k_cent_policy_map: eight such workgroups per CU).  The tree walk of the base-velocity solve runs across the lanes, one lane closes the
+// solve, three lanes write the knots; the lane of knot 0 writes the new filter state and base_vel [B][6] (may be null).  No atomics, nothing but the grid depends on B
+__global__ __launch_bounds__(64) void k_command_targets_cent(const DevModel* __restrict__ dm, double alpha, const double* __restrict__ v_cmd, double* v_filt,
+                                                             const double* __restrict__ x0, double t0, double horizon, double* __restrict__ tt, double* __restrict__ ts,
+                                                             double* __restrict__ base_vel) {
+  CentWST<false>& w = *reinterpret_cast<CentWST<false>*>(hsqp_smem);
+  const Ctx ctx{(int)threadIdx.x, 64, nullptr};
+  const size_t b = blockIdx.x;
+  cent_command_targets_instance(ctx, *dm, w, alpha, v_cmd + b * CMD_N, v_filt + b * CMD_N, x0 + b * NX, t0, horizon, tt + b * CMD_KNOTS, ts + b * CMD_KNOTS * NX,
+                                base_vel ? base_vel + b * 6 : nullptr);
+}
+
 // ---- ground-height estimate from the stance feet (hsqp_ground.h): one lane per (instance, foot), 32 instances per 64-lane workgroup.  A lane walks the
 // kinematics of its leg; the two lanes of an instance are neighbours in one wave and exchange their height with a lane shuffle, OUTSIDE the live guard
 // (a dead lane's partner is dead too: B instances are 2 B lanes); the lane of foot 0 applies the rule, writes g_out (the loop: the latch's shadow) and
@@ -887,9 +902,9 @@ __global__ __launch_bounds__(OBS_THREADS) void k_observe(ObserveArgs a) {
 __global__ __launch_bounds__(64) void k_episode_host_reset(HostResetArgs a) { host_reset_instance(Ctx{(int)threadIdx.x, 64, nullptr}, a, blockIdx.x); }
 // the command in use of every instance from its state (behind hsqp_loop_isolate and hsqp_loop_command): one thread per entry
 __global__ __launch_bounds__(64) void k_episode_commands(const int* __restrict__ state, const double* __restrict__ v_cmd, const double* __restrict__ x_reset, int B,
-                                                         double* __restrict__ v_use) {
+                                                         double* __restrict__ v_use, int pose) {
   const int id = blockIdx.x * 64 + threadIdx.x, b = id / CMD_N, i = id % CMD_N;
-  if (b < B) v_use[id] = episode_command_entry(state[b], v_cmd + (size_t)b * CMD_N, x_reset + (size_t)b * NX, i);
+  if (b < B) v_use[id] = episode_command_entry(state[b], v_cmd + (size_t)b * CMD_N, x_reset + (size_t)b * NX, i, pose);
 }
 // the per-instance gait reset at time t.  ids == null: workgroup b serves instance b if flags[b] is set (behind the triage); otherwise workgroup i
 // serves instance ids[i] (hsqp_loop_reset_instances)
@@ -1406,9 +1421,12 @@ static RolloutStage rollout_stage_layout(Carve c, size_t B, size_t n, bool host,
           c.take<double>(B * n * NX, host && want_x), c.take<double>(B * n * NU, host && want_u), c.bytes()};
 }
 // d_loop_log, hsqp_command_targets (host arrays)
-struct CommandStage { double* v_cmd; double* v_filt; double* x0; double* tt; double* ts; size_t bytes; };
-static CommandStage command_stage_layout(Carve c, size_t B) {
-  return {c.take<double>(B * CMD_N), c.take<double>(B * CMD_N), c.take<double>(B * NX), c.take<double>(B * CMD_KNOTS), c.take<double>(B * CMD_KNOTS * NX), c.bytes()};
+struct CommandStage { double* v_cmd; double* v_filt; double* x0; double* tt; double* ts; double* base_vel; size_t bytes; };
+static CommandStage command_stage_layout(Carve c, size_t B, bool base_vel = false) {   // base_vel [B][6]: the centroidal generator's by-product (hsqp_cent_loop.h)
+  CommandStage sg{c.take<double>(B * CMD_N), c.take<double>(B * CMD_N), c.take<double>(B * NX), c.take<double>(B * CMD_KNOTS), c.take<double>(B * CMD_KNOTS * NX), nullptr, 0};
+  if (base_vel) sg.base_vel = c.take<double>(B * 6);
+  sg.bytes = c.bytes();
+  return sg;
 }
 // d_loop: the loop's resident arrays
 static size_t loop_layout(Carve c, hsqp_handle::Loop& L, size_t B, size_t E) {
@@ -1765,7 +1783,7 @@ int hsqp_create(const hsqp_model_desc* model, const hsqp_settings* settings, hsq
       {(const void*)k_lq<true>, (int)sizeof(LqWS)},
       {h->poison_lds ? (const void*)k_poison_lds : nullptr, POISON_LDS_BYTES},
       {(const void*)k_lq<false>, (int)sizeof(LqWST<false>)}, {(const void*)k_step_value, (int)sizeof(LqWST<false>)},
-      {(const void*)k_lq_cent2, (int)sizeof(CentWST<true>)},
+      {(const void*)k_lq_cent2, (int)sizeof(CentWST<true>)}, {(const void*)k_command_targets_cent, (int)sizeof(CentWST<false>)},
       {(const void*)k_project, (int)sizeof(ProjWS)},
       {(const void*)k_riccati<NX>, (int)sizeof(RicWS)}, {(const void*)k_riccati_fact, (int)sizeof(RicFWS)}, {(const void*)k_riccati<CNX>, (int)sizeof(RicWS)},
       {(const void*)k_scan_init<CNX>, (int)sizeof(ScanInitWS<CNX>)}, {(const void*)k_scan_combine<CNX>, (int)sizeof(ScanCombWS<CNX>)},
@@ -3328,10 +3346,27 @@ int hsqp_inertia_eval_device(hsqp_handle* h, int batch, const double* d_x, doubl
 }
 
 static int loop_bad(hsqp_handle* h, const char* who, const char* what) { h->err = std::string(who) + ": " + what; return HSQP_ERR_BAD_ARG; }
+// where the base pose starts in a state row of the handle's formulation (csrc/hsqp_episode.h: the triage's box, the stance command)
+static int episode_pose_offset(const hsqp_handle* h) { return h->hdm.formulation == HSQP_FORM_CENTROIDAL ? EPISODE_POSE_CENT : EPISODE_POSE_WB; }
 // whole-body handle with a default joint state
 static int loop_handle_ok(hsqp_handle* h, const char* who) {
-  if (h->hdm.formulation != HSQP_FORM_WB) return loop_bad(h, who, "whole-body handles only (the centroidal generator needs the base velocity from the centroidal momentum)");
+  if (h->hdm.formulation != HSQP_FORM_WB)
+    return loop_bad(h, who, "whole-body handles only (the centroidal generator needs the base velocity from the centroidal momentum): hsqp_centroidal_command_targets, "
+                            "hsqp_loop_start_centroidal (include/hsqp_cent_loop.h)");
   if (!h->hdm.has_default_joint_state) return loop_bad(h, who, "no default joint state: call hsqp_set_default_joint_state first");
+  return HSQP_OK;
+}
+// centroidal handle with a default joint state (include/hsqp_cent_loop.h)
+static int cent_loop_handle_ok(hsqp_handle* h, const char* who) {
+  if (h->hdm.formulation != HSQP_FORM_CENTROIDAL) return loop_bad(h, who, "centroidal handles only (whole-body handles: the entry points of include/hsqp_loop.h)");
+  if (!h->hdm.has_default_joint_state) return loop_bad(h, who, "no default joint state: call hsqp_set_default_joint_state first");
+  return HSQP_OK;
+}
+// host state rows of a centroidal handle: the padding must be zero (the message of hsqp_upload)
+static int cent_rows_padding_ok(hsqp_handle* h, const double* x, size_t rows) {
+  for (size_t r = 0; r < rows; ++r)
+    for (int i = HSQP_CNX; i < NX; ++i)
+      if (x[r * NX + i] != 0.0) { h->err = "centroidal formulation: entries 35..57 of every state row must be zero"; return HSQP_ERR_BAD_ARG; }
   return HSQP_OK;
 }
 static bool all_finite(const double* v, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false; return true; }
@@ -3351,6 +3386,12 @@ static void launch_command_targets(hsqp_handle* h, int B, const double* d_v_cmd,
                                    double* d_tt, double* d_ts) {
   HSQP_LAUNCH(k_command_targets, dim3((B * CMD_KNOTS + CMDT_THREADS - 1) / CMDT_THREADS), dim3(CMDT_THREADS), 0, h->stream, h->d_dm, alpha, d_v_cmd, d_v_filt, d_x0,
               t0, horizon, B, d_tt, d_ts);
+}
+
+// queues k_command_targets_cent on the handle's stream (device arrays; d_base_vel may be null)
+static void launch_command_targets_cent(hsqp_handle* h, int B, const double* d_v_cmd, double* d_v_filt, double alpha, const double* d_x0, double t0, double horizon,
+                                        double* d_tt, double* d_ts, double* d_base_vel) {
+  HSQP_LAUNCH(k_command_targets_cent, dim3(B), dim3(64), sizeof(CentWST<false>), h->stream, h->d_dm, alpha, d_v_cmd, d_v_filt, d_x0, t0, horizon, d_tt, d_ts, d_base_vel);
 }
 
 // queues k_ground_estimate on the handle's stream (device arrays)
@@ -3375,32 +3416,38 @@ static int launch_foot_heights(hsqp_handle* h, const char* who, const PerceiveAr
   return HSQP_OK;
 }
 
+// cent: the centroidal entry points (include/hsqp_cent_loop.h); base_vel [B][6] is theirs and may be null
 static int command_targets_impl(hsqp_handle* h, int batch, const double* v_cmd, double* v_filt, double alpha, const double* x0, double t0, double horizon,
-                                double* tt, double* ts, bool dev) {
+                                double* tt, double* ts, bool dev, bool cent = false, double* base_vel = nullptr) {
   if (!h) return HSQP_ERR_BAD_ARG;
-  const char* who = dev ? "hsqp_command_targets_device" : "hsqp_command_targets";
-  { const int rc = loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  const char* who = cent ? (dev ? "hsqp_centroidal_command_targets_device" : "hsqp_centroidal_command_targets") : (dev ? "hsqp_command_targets_device" : "hsqp_command_targets");
+  const char* kernel = cent ? "k_command_targets_cent" : "k_command_targets";
+  { const int rc = cent ? cent_loop_handle_ok(h, who) : loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
   if (!v_cmd || !v_filt || !x0 || !tt || !ts) return loop_bad(h, who, "null array");
   if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
   if (!(alpha >= 0.0 && alpha < 1.0)) return loop_bad(h, who, "filter_alpha outside [0, 1)");
   if (!std::isfinite(t0) || !std::isfinite(horizon) || !(horizon > 0.0)) return loop_bad(h, who, "t0 not finite, or horizon not finite and > 0");
   const size_t B = batch;
   if (!dev && !all_finite(v_cmd, B * CMD_N)) return loop_bad(h, who, "non-finite command");
+  if (!dev && cent) { const int rc = cent_rows_padding_ok(h, x0, B); if (rc != HSQP_OK) return rc; }
   HCHECK(hipSetDevice(h->device));
   StickyError step{h};
   if (dev) {
-    launch_command_targets(h, batch, v_cmd, v_filt, alpha, x0, t0, horizon, tt, ts);
-    step(hipGetLastError(), "k_command_targets");
+    if (cent) launch_command_targets_cent(h, batch, v_cmd, v_filt, alpha, x0, t0, horizon, tt, ts, base_vel);
+    else launch_command_targets(h, batch, v_cmd, v_filt, alpha, x0, t0, horizon, tt, ts);
+    step(hipGetLastError(), kernel);
   } else {
-    DEV_ENSURE(h->d_loop_log, command_stage_layout(Carve{}, B).bytes, "command-target staging");
-    const CommandStage sg = command_stage_layout(Carve{h->d_loop_log.p}, B);
+    DEV_ENSURE(h->d_loop_log, command_stage_layout(Carve{}, B, base_vel != nullptr).bytes, "command-target staging");
+    const CommandStage sg = command_stage_layout(Carve{h->d_loop_log.p}, B, base_vel != nullptr);
     step(hipMemcpyAsync(sg.v_cmd, v_cmd, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_cmd");
     step(hipMemcpyAsync(sg.v_filt, v_filt, B * CMD_N * 8, hipMemcpyHostToDevice, h->stream), "upload v_filt");
     step(hipMemcpyAsync(sg.x0, x0, B * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x0");
     if (step.rc == HSQP_OK) {
-      launch_command_targets(h, batch, sg.v_cmd, sg.v_filt, alpha, sg.x0, t0, horizon, sg.tt, sg.ts);
-      step(hipGetLastError(), "k_command_targets");
+      if (cent) launch_command_targets_cent(h, batch, sg.v_cmd, sg.v_filt, alpha, sg.x0, t0, horizon, sg.tt, sg.ts, sg.base_vel);
+      else launch_command_targets(h, batch, sg.v_cmd, sg.v_filt, alpha, sg.x0, t0, horizon, sg.tt, sg.ts);
+      step(hipGetLastError(), kernel);
     }
+    if (base_vel) step(hipMemcpyAsync(base_vel, sg.base_vel, B * 6 * 8, hipMemcpyDeviceToHost, h->stream), "download base_vel");
     step(hipMemcpyAsync(v_filt, sg.v_filt, B * CMD_N * 8, hipMemcpyDeviceToHost, h->stream), "download v_filt");
     step(hipMemcpyAsync(tt, sg.tt, B * CMD_KNOTS * 8, hipMemcpyDeviceToHost, h->stream), "download target_times");
     step(hipMemcpyAsync(ts, sg.ts, B * CMD_KNOTS * NX * 8, hipMemcpyDeviceToHost, h->stream), "download target_states");
@@ -3418,6 +3465,16 @@ int hsqp_command_targets_device(hsqp_handle* h, int batch, const double* d_v_cmd
   return command_targets_impl(h, batch, d_v_cmd, d_v_filt, filter_alpha, d_x0, t0, horizon, d_target_times, d_target_states, true);
 }
 
+int hsqp_centroidal_command_targets(hsqp_handle* h, int batch, const double* v_cmd, double* v_filt, double filter_alpha, const double* x0, double t0,
+                                    double horizon, double* target_times, double* target_states, double* base_vel) {
+  return command_targets_impl(h, batch, v_cmd, v_filt, filter_alpha, x0, t0, horizon, target_times, target_states, false, true, base_vel);
+}
+int hsqp_centroidal_command_targets_device(hsqp_handle* h, int batch, const double* d_v_cmd, double* d_v_filt, double filter_alpha, const double* d_x0,
+                                           double t0, double horizon, double* d_target_times, double* d_target_states, double* d_base_vel) {
+  return command_targets_impl(h, batch, d_v_cmd, d_v_filt, filter_alpha, d_x0, t0, horizon, d_target_times, d_target_states, true, true, d_base_vel);
+}
+
+// (on a centroidal handle too: the values are the whole-body task file's, include/hsqp_cent_loop.h)
 void hsqp_loop_defaults(const hsqp_handle* h, hsqp_loop_settings* s) {
   if (!s) return;
   memset(s, 0, sizeof(*s));
@@ -3437,11 +3494,12 @@ static int gait_reset_impl(hsqp_handle* h, const char* who, const hsqp_gait_sett
 static bool observe_in_force(const hsqp_handle* h);
 
 // hsqp_loop_start (schedules uploaded once) and hsqp_loop_start_gait (gait != null: the resident gait state owns the schedule, max_events is its capacity)
+// cent: hsqp_loop_start_centroidal (include/hsqp_cent_loop.h), never with a gait
 static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_settings* st, const hsqp_gait_settings* gait, int batch, double t0, const double* x0,
-                           const double* v_cmd, int max_events, const int32_t* n_events, const double* event_times, const int32_t* mode_sequence) {
+                           const double* v_cmd, int max_events, const int32_t* n_events, const double* event_times, const int32_t* mode_sequence, bool cent = false) {
   if (!h) return HSQP_ERR_BAD_ARG;
   h->loop.started = false;
-  { const int rc = loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
+  { const int rc = cent ? cent_loop_handle_ok(h, who) : loop_handle_ok(h, who); if (rc != HSQP_OK) return rc; }
   if (!st || !x0 || !v_cmd || (!gait && (!n_events || !event_times || !mode_sequence))) return loop_bad(h, who, "null settings or array");
   if (batch < 1 || batch > h->st.max_batch) return loop_bad(h, who, "batch outside [1, max_batch]");
   if (st->n_nodes < 1 || st->n_nodes > h->st.max_nodes) return loop_bad(h, who, "n_nodes outside [1, max_nodes]");
@@ -3459,6 +3517,7 @@ static int loop_start_impl(hsqp_handle* h, const char* who, const hsqp_loop_sett
     for (size_t b = 0; b < B; ++b)
       if (n_events[b] < 1 || n_events[b] > max_events) return loop_bad(h, who, "n_events outside [1, max_events]");
   if (!all_finite(v_cmd, B * CMD_N)) return loop_bad(h, who, "non-finite command");
+  if (cent) { const int rc = cent_rows_padding_ok(h, x0, B); if (rc != HSQP_OK) return rc; }
   HCHECK(hipSetDevice(h->device));
   // the gait's clock is the problem time (include/hsqp_observe.h): compute_delay periods behind the loop's time
   const double t_gait = observe_in_force(h) ? observe_problem_time(t0, observe_policy_time(h->observe.compute_delay, st->period)) : t0;
@@ -3497,6 +3556,11 @@ int hsqp_loop_start(hsqp_handle* h, const hsqp_loop_settings* st, int batch, dou
   return loop_start_impl(h, "hsqp_loop_start", st, nullptr, batch, t0, x0, v_cmd, max_events, n_events, event_times, mode_sequence);
 }
 
+int hsqp_loop_start_centroidal(hsqp_handle* h, const hsqp_loop_settings* st, int batch, double t0, const double* x0, const double* v_cmd, int max_events,
+                               const int32_t* n_events, const double* event_times, const int32_t* mode_sequence) {
+  return loop_start_impl(h, "hsqp_loop_start_centroidal", st, nullptr, batch, t0, x0, v_cmd, max_events, n_events, event_times, mode_sequence, true);
+}
+
 static int loop_started(hsqp_handle* h, const char* who) {
   if (!h->loop.started) return loop_bad(h, who, "no loop started (hsqp_loop_start; every hsqp_upload* / hsqp_solve call ends a loop)");
   return HSQP_OK;
@@ -3512,7 +3576,8 @@ static int loop_command_impl(hsqp_handle* h, const double* v_cmd, bool dev) {
   HCHECK(hipSetDevice(h->device));
   HCHECK(hipMemcpyAsync(h->loop.v_cmd, v_cmd, n * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
   if (h->loop.isolate) {   // the command in use: a parked instance keeps the stance command
-    HSQP_LAUNCH(k_episode_commands, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->loop.ep.state, h->loop.v_cmd, h->loop.x_reset, h->loop.B, h->loop.v_use);
+    HSQP_LAUNCH(k_episode_commands, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->loop.ep.state, h->loop.v_cmd, h->loop.x_reset, h->loop.B, h->loop.v_use,
+                episode_pose_offset(h));
     HCHECK(hipGetLastError());
   }
   HCHECK(hipStreamSynchronize(h->stream));
@@ -3794,8 +3859,10 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   // 1. the targets; the filter state advances in the second half of its buffer
   double* vf_next = L.v_filt + B * CMD_N;
   step(hipMemcpyAsync(vf_next, L.v_filt, B * CMD_N * 8, hipMemcpyDeviceToDevice, h->stream), "copy v_filt");
-  launch_command_targets(h, L.B, iso ? L.v_use : L.v_cmd, vf_next, st.filter_alpha, xm, tp, st.n_nodes * st.dt, L.tt, L.ts);
-  step(hipGetLastError(), "k_command_targets");
+  const bool cent = h->hdm.formulation == HSQP_FORM_CENTROIDAL;   // (a loop started by hsqp_loop_start_centroidal, include/hsqp_cent_loop.h)
+  if (cent) launch_command_targets_cent(h, L.B, iso ? L.v_use : L.v_cmd, vf_next, st.filter_alpha, xm, tp, st.n_nodes * st.dt, L.tt, L.ts, nullptr);
+  else launch_command_targets(h, L.B, iso ? L.v_use : L.v_cmd, vf_next, st.filter_alpha, xm, tp, st.n_nodes * st.dt, L.tt, L.ts);
+  step(hipGetLastError(), cent ? "k_command_targets_cent" : "k_command_targets");
   // the gait update between steps 1 and 2 (include/hsqp_gait.h): this cycle's schedule into ne / ev / seq; the shadow state becomes the live one with step 5
   if (L.gait) {
     if (step.rc != HSQP_OK) return step.rc;
@@ -3863,7 +3930,7 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   L.t += st.period;
   if (iso) {   // 6. the triage of every instance, and with a resident gait the reset of those that start a new episode at the new loop time
     const TriageArgs a{L.ep_st, L.cycle, h->d_status, h->d_perf_after, L.ro_status, L.xs, L.x_reset, L.v_cmd, L.ep, L.x, L.v_filt, L.v_use, d_xlog, d_ulog,
-                       gnd && L.ground_st.box_above_ground ? L.gnd_g[L.ground_cur] : nullptr};
+                       gnd && L.ground_st.box_above_ground ? L.gnd_g[L.ground_cur] : nullptr, episode_pose_offset(h)};
     HSQP_LAUNCH(k_loop_triage, dim3(L.B), dim3(64), 0, h->stream, a);
     if (L.gait)
       HSQP_LAUNCH(k_gait_reset_instances, dim3(L.B), dim3(64), 0, h->stream, h->gait.s[h->gait.cur], h->gait.st.max_events, (const int*)nullptr, (const int*)L.ep.reset,
@@ -4452,6 +4519,7 @@ int hsqp_loop_isolate(hsqp_handle* h, const hsqp_episode_settings* es, const dou
   if (es->max_tilt < 0.0) return loop_bad(h, who, "max_tilt < 0");
   const size_t B = L.B;
   if (x_reset && !all_finite(x_reset, B * NX)) return loop_bad(h, who, "non-finite x_reset");
+  if (x_reset && h->hdm.formulation == HSQP_FORM_CENTROIDAL) { const int rc = cent_rows_padding_ok(h, x_reset, B); if (rc != HSQP_OK) return rc; }
   // the gated sweeps take ONE verdict per batch (choose_sweep, the gate in hsqp_iterate_device): one instance's NaN would change the others' bits
   const int flags = h->st.flags;
   if ((flags & (HSQP_FLAG_SEGMENTED_RICCATI | HSQP_FLAG_PARALLEL_RICCATI)) ||
@@ -4508,6 +4576,7 @@ int hsqp_loop_reset_instances(hsqp_handle* h, int n, const int32_t* ids, const d
   hsqp_handle::Loop& L = h->loop;
   { const int rc = loop_ids_ok(h, who, n, ids); if (rc != HSQP_OK) return rc; }
   if (x0 && !all_finite(x0, (size_t)n * NX)) return loop_bad(h, who, "non-finite x0");
+  if (x0 && h->hdm.formulation == HSQP_FORM_CENTROIDAL) { const int rc = cent_rows_padding_ok(h, x0, (size_t)n); if (rc != HSQP_OK) return rc; }
   if (v_cmd && !all_finite(v_cmd, (size_t)n * CMD_N)) return loop_bad(h, who, "non-finite command");
   HCHECK(hipSetDevice(h->device));
   StickyError step{h};

@@ -36,7 +36,9 @@ struct TriageArgs {
   double* v_use;                 // [B][CMD_N] the command in use from the next cycle on
   double* x_log; double* u_log;  // row `cycle` of the logs, [B][NX] / [B][NU], or null
   const double* ground;          // [B] the estimated ground (include/hsqp_ground.h, box_above_ground): the height test is on xs[2] - ground[b]; or null
+  int pose = 0;                  // where the base pose [x, y, z, yaw, pitch, roll] starts in a state row: EPISODE_POSE_WB or EPISODE_POSE_CENT
 };
+constexpr int EPISODE_POSE_WB = 0, EPISODE_POSE_CENT = 6;   // whole-body rows begin with the pose; centroidal rows carry the normalised momentum in front of it
 
 HSQP_HD bool episode_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and +-inf
 
@@ -53,24 +55,25 @@ HSQP_HD bool episode_row_finite(const Ctx& ctx, const double* row, int n) {
 }
 
 // the verdict on one instance (include/hsqp_episode.h, step 6): HSQP_EP_ALIVE or the first cause that applies
-// ground (may be null): the estimated ground under the instance, the base-height box is then above it
+// ground (may be null): the estimated ground under the instance, the base-height box is then above it; pose: the row's pose offset
 HSQP_HD int episode_verdict(const Ctx& ctx, const hsqp_episode_settings& st, int it_status, const hsqp_perf& perf, int ro_status, const double* xs,
-                            const double* ground = nullptr) {
+                            const double* ground = nullptr, int pose = 0) {
   if (it_status != 0 || !episode_finite(perf.merit) || !episode_finite(perf.cost) || !episode_finite(perf.dynamics_sse) || !episode_finite(perf.equality_sse))
     return HSQP_EP_FAILED_NUMERIC;
   if (ro_status != HSQP_ROLLOUT_OK || !episode_row_finite(ctx, xs, NX)) return HSQP_EP_FAILED_ROLLOUT;
-  const double height = ground ? xs[2] - *ground : xs[2];
-  if (height < st.min_base_height || height > st.max_base_height || fabs(xs[4]) > st.max_tilt || fabs(xs[5]) > st.max_tilt) return HSQP_EP_FAILED_BOUNDS;
+  const double* p = xs + pose;
+  const double height = ground ? p[2] - *ground : p[2];
+  if (height < st.min_base_height || height > st.max_base_height || fabs(p[4]) > st.max_tilt || fabs(p[5]) > st.max_tilt) return HSQP_EP_FAILED_BOUNDS;
   return HSQP_EP_ALIVE;
 }
 
-// the command an instance in `state` uses: its own, or parked the stance command {0, 0, x_reset[2], 0}
-HSQP_HD double episode_command_entry(int state, const double* v_cmd, const double* x_reset, int i) {
+// the command an instance in `state` uses: its own, or parked the stance command {0, 0, x_reset[pose + 2], 0}
+HSQP_HD double episode_command_entry(int state, const double* v_cmd, const double* x_reset, int i, int pose = 0) {
   if (state == HSQP_EP_ALIVE) return v_cmd[i];
-  return i == 2 ? x_reset[2] : 0.0;
+  return i == 2 ? x_reset[pose + 2] : 0.0;
 }
-HSQP_HD void episode_command_in_use(const Ctx& ctx, int state, const double* v_cmd, const double* x_reset, double* v_use) {
-  WG_FOR(ctx, i, CMD_N) v_use[i] = episode_command_entry(state, v_cmd, x_reset, i);
+HSQP_HD void episode_command_in_use(const Ctx& ctx, int state, const double* v_cmd, const double* x_reset, double* v_use, int pose = 0) {
+  WG_FOR(ctx, i, CMD_N) v_use[i] = episode_command_entry(state, v_cmd, x_reset, i, pose);
 }
 
 // Instance b behind the rollout of cycle a.cycle.  Returns the verdict.
@@ -80,15 +83,15 @@ HSQP_HD int triage_instance(const Ctx& ctx, const TriageArgs& a, int b) {
   const double* xr = a.x_reset + (size_t)b * NX;
   const double* vc = a.v_cmd + (size_t)b * CMD_N;
   const int before = ep.state[b];
-  const int cause = episode_verdict(ctx, a.st, a.it_status[b], a.perf[b], a.ro_status[b], xs, a.ground ? a.ground + b : nullptr);
+  const int cause = episode_verdict(ctx, a.st, a.it_status[b], a.perf[b], a.ro_status[b], xs, a.ground ? a.ground + b : nullptr, a.pose);
   const bool failed = cause != HSQP_EP_ALIVE;
   const int after = failed ? (a.st.on_failure == HSQP_EPISODE_RESET ? HSQP_EP_ALIVE : cause) : before;
   WG_SYNC(ctx);   // every lane has read the words lane 0 rewrites below
   if (failed) {
     WG_FOR(ctx, i, NX) a.x[(size_t)b * NX + i] = xr[i];
-    WG_FOR(ctx, i, CMD_N) a.v_filt[(size_t)b * CMD_N + i] = episode_command_entry(after, vc, xr, i);
+    WG_FOR(ctx, i, CMD_N) a.v_filt[(size_t)b * CMD_N + i] = episode_command_entry(after, vc, xr, i, a.pose);
   }
-  episode_command_in_use(ctx, after, vc, xr, a.v_use + (size_t)b * CMD_N);
+  episode_command_in_use(ctx, after, vc, xr, a.v_use + (size_t)b * CMD_N, a.pose);
   if (failed || before != HSQP_EP_ALIVE) {   // the row of a failed cycle, and every row of a parked instance
     const double nan = __builtin_nan("");
     if (a.x_log) WG_FOR(ctx, i, NX) a.x_log[(size_t)b * NX + i] = nan;

@@ -18,6 +18,7 @@
 #include "../../include/hsqp_feedback.h"
 #include "../../include/hsqp_rollout.h"
 #include "../../include/hsqp_loop.h"
+#include "../../include/hsqp_cent_loop.h"
 #include "../../include/hsqp_gait.h"
 #include "../../include/hsqp_episode.h"
 #include "../../include/hsqp_metrics.h"
@@ -440,6 +441,36 @@ class HipSqpSolver {
     if (B == 0 || x0.size() != B * HSQP_NX || velocityCommands.size() != B * HSQP_CMD_N) throw std::runtime_error("[HipSqpSolver] startLoopGait: inconsistent array sizes");
     const int rc = hsqp_loop_start_gait(h_, &st, &gait, (int)B, t0, x0.data(), velocityCommands.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_start_gait failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+    loopBatch_ = B;
+    loopNodes_ = (size_t)st.n_nodes; gridNodes_ = 0;
+    shiftable_ = false;
+  }
+  /** ---- the centroidal forms (include/hsqp_cent_loop.h): what CentroidalMpcSqpNode does per cycle through
+   *  CentroidalMpcTargetTrajectoriesCalculator::commandedVelocityToTargetTrajectories.  x0 [batch][HSQP_NX]: centroidal rows, entries 35..57 zero.
+   *  centroidalCommandTargets: filteredCommands [batch][4] in / out, targetTimes [batch][3], targetStates [batch][3][HSQP_NX]; baseVelocity (optional)
+   *  [batch][6], the base velocity from the centroidal momentum. */
+  void centroidalCommandTargets(const std::vector<double>& velocityCommands, std::vector<double>& filteredCommands, double filterAlpha, const std::vector<double>& x0,
+                                double t0, double horizon, std::vector<double>& targetTimes, std::vector<double>& targetStates, std::vector<double>* baseVelocity = nullptr) {
+    const size_t B = velocityCommands.size() / HSQP_CMD_N;
+    if (B == 0 || velocityCommands.size() != B * HSQP_CMD_N || filteredCommands.size() != B * HSQP_CMD_N || x0.size() != B * HSQP_NX)
+      throw std::runtime_error("[HipSqpSolver] centroidalCommandTargets: inconsistent array sizes");
+    targetTimes.assign(B * HSQP_CMD_KNOTS, 0.0); targetStates.assign(B * HSQP_CMD_KNOTS * HSQP_NX, 0.0);
+    if (baseVelocity) baseVelocity->assign(B * 6, 0.0);
+    const int rc = hsqp_centroidal_command_targets(h_, (int)B, velocityCommands.data(), filteredCommands.data(), filterAlpha, x0.data(), t0, horizon, targetTimes.data(),
+                                                   targetStates.data(), baseVelocity ? baseVelocity->data() : nullptr);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_centroidal_command_targets failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** startLoop on a centroidal handle; runLoop, setLoopCommand, loopState, isolateLoop, resetLoopInstances and loopEpisodes work after either start.
+   *  loopDefaults() gives the whole-body task file's dt and period: set them from the centroidal task. */
+  void startLoopCentroidal(const hsqp_loop_settings& st, double t0, const std::vector<double>& x0, const std::vector<double>& velocityCommands, int maxEvents,
+                           const std::vector<int32_t>& nEvents, const std::vector<double>& eventTimes, const std::vector<int32_t>& modeSequence) {
+    const size_t B = nEvents.size();
+    loopBatch_ = 0;
+    if (B == 0 || maxEvents < 1 || x0.size() != B * HSQP_NX || velocityCommands.size() != B * HSQP_CMD_N || eventTimes.size() != B * (size_t)maxEvents ||
+        modeSequence.size() != B * (size_t)(maxEvents + 1))
+      throw std::runtime_error("[HipSqpSolver] startLoopCentroidal: inconsistent array sizes");
+    const int rc = hsqp_loop_start_centroidal(h_, &st, (int)B, t0, x0.data(), velocityCommands.data(), maxEvents, nEvents.data(), eventTimes.data(), modeSequence.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_loop_start_centroidal failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     loopBatch_ = B;
     loopNodes_ = (size_t)st.n_nodes; gridNodes_ = 0;
     shiftable_ = false;

@@ -661,9 +661,19 @@ def torso_reference(model, x_ref):
     return np.concatenate([pos, matrix_to_quaternion(R[b] @ np.array(t["R"]).reshape(3, 3)), vlin, omega])
 
 
-def centroidal_velocity_command_targets(model, v_cmd, t0, x0, horizon):
+def centroidal_velocity_command_targets(model, v_cmd, t0, x0, horizon, filter_alpha=0.0, v_filt=None):
     """CentroidalMpcTargetTrajectoriesCalculator::commandedVelocityToTargetTrajectories
-    (humanoid_centroidal_mpc/src/command/CentroidalMpcTargetTrajectoriesCalculator.cpp:88-158), command filter at steady state."""
+    (humanoid_centroidal_mpc/src/command/CentroidalMpcTargetTrajectoriesCalculator.cpp:88-158).  Default: the command filter at steady state;
+    filter_alpha, v_filt: the semantics of velocity_command_targets (v_filt [4] is updated IN PLACE when it is a numpy array).  The device form
+    is hsqp_centroidal_command_targets."""
+    if filter_alpha != 0.0:
+        cmd = np.asarray(v_cmd, dtype=float)
+        new = filter_alpha * (cmd if v_filt is None else np.asarray(v_filt, dtype=float)) + (1.0 - filter_alpha) * cmd
+        if isinstance(v_filt, np.ndarray):
+            v_filt[:] = new
+        v_cmd = tuple(float(v) for v in new)
+    elif isinstance(v_filt, np.ndarray):
+        v_filt[:] = v_cmd
     vx, vy, height, wz = v_cmd
     pose = np.array(x0[6:12], dtype=float)
     pose[4] = pose[5] = 0.0

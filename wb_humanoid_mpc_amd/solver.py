@@ -171,6 +171,10 @@ def load_library():
     lib.hsqp_command_targets.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp, C.c_double, C.c_double, _dp, _dp]
     lib.hsqp_command_targets_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp, C.c_double, C.c_double, _dp, _dp]
     lib.hsqp_loop_defaults.argtypes = [C.c_void_p, _ls]
+    # include/hsqp_cent_loop.h
+    lib.hsqp_centroidal_command_targets.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp, C.c_double, C.c_double, _dp, _dp, _dp]
+    lib.hsqp_centroidal_command_targets_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp, C.c_double, C.c_double, _dp, _dp, _dp]
+    lib.hsqp_loop_start_centroidal.argtypes = [C.c_void_p, _ls, C.c_int, C.c_double, _dp, _dp, C.c_int, _ip, _dp, _ip]
     lib.hsqp_loop_defaults.restype = None
     lib.hsqp_loop_start.argtypes = [C.c_void_p, _ls, C.c_int, C.c_double, _dp, _dp, C.c_int, _ip, _dp, _ip]
     lib.hsqp_loop_command.argtypes = [C.c_void_p, _dp]
@@ -288,8 +292,8 @@ class HipSqpSolver:
         self._sol = None
         self._loop_batch = 0
         self._loop_nodes = self._grid_nodes = 0
-        if not model.centroidal:   # the velocity-command generator's joint targets (reference.info defaultJointState) are not part of hsqp_model_desc
-            self._check(self.lib.hsqp_set_default_joint_state(h, _c(model.default_joint_state).ctypes.data_as(_dp)))
+        # the velocity-command generators' joint targets (reference.info defaultJointState) are not part of hsqp_model_desc
+        self._check(self.lib.hsqp_set_default_joint_state(h, _c(model.default_joint_state).ctypes.data_as(_dp)))
 
     def close(self):
         if getattr(self, "h", None):
@@ -1004,29 +1008,50 @@ class HipSqpSolver:
         return y, tp.value
 
     # ---- include/hsqp_loop.h: velocity-command targets and the resident closed loop
-    def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None):
+    def command_targets(self, v_cmd, x0, t0, horizon, filter_alpha=0.0, v_filt=None, base_velocity=False):
         """hsqp_command_targets: (target_times[B, 3], target_states[B, 3, 58], v_filt[B, 4]) of B instances from their commands
         (vx, vy, height, yaw rate) and measured states; v_filt: the filter state before the call (None: the commands, a converged filter).
-        The arithmetic of reference.velocity_command_targets."""
+        The arithmetic of reference.velocity_command_targets.
+        A centroidal solver calls hsqp_centroidal_command_targets (include/hsqp_cent_loop.h, reference.centroidal_velocity_command_targets);
+        base_velocity=True then appends its by-product, the base velocity [B, 6] from the centroidal momentum, to the result."""
         x0 = _c(np.atleast_2d(x0))
         B = x0.shape[0]
         v_cmd = _c(np.broadcast_to(v_cmd, (B, _abi.CMD_N)))
         vf = v_cmd.copy() if v_filt is None else _c(np.broadcast_to(v_filt, (B, _abi.CMD_N))).copy()
         tt, ts = np.zeros((B, _abi.CMD_KNOTS)), np.zeros((B, _abi.CMD_KNOTS, _abi.NX))
+        if self.model.centroidal:
+            if x0.shape != (B, _abi.NX):
+                raise ValueError("x0 must be [B][58] (centroidal rows padded with zeros)")
+            bv = np.zeros((B, 6)) if base_velocity else None
+            self._check(self.lib.hsqp_centroidal_command_targets(self.h, B, v_cmd.ctypes.data_as(_dp), vf.ctypes.data_as(_dp), C.c_double(filter_alpha),
+                                                                 x0.ctypes.data_as(_dp), C.c_double(t0), C.c_double(horizon), tt.ctypes.data_as(_dp),
+                                                                 ts.ctypes.data_as(_dp), bv.ctypes.data_as(_dp) if base_velocity else None))
+            return (tt, ts, vf, bv) if base_velocity else (tt, ts, vf)
+        if base_velocity:
+            raise ValueError("base_velocity: a by-product of the centroidal generator (the whole-body state row carries the base velocity)")
         self._check(self.lib.hsqp_command_targets(self.h, B, v_cmd.ctypes.data_as(_dp), vf.ctypes.data_as(_dp), C.c_double(filter_alpha), x0.ctypes.data_as(_dp),
                                                   C.c_double(t0), C.c_double(horizon), tt.ctypes.data_as(_dp), ts.ctypes.data_as(_dp)))
         return tt, ts, vf
 
-    def command_targets_device(self, batch, v_cmd_ptr, v_filt_ptr, x0_ptr, t0, horizon, target_times_ptr, target_states_ptr, filter_alpha=0.0):
-        """hsqp_command_targets_device: the same with every array in device memory (addresses); v_filt is updated in place."""
+    def command_targets_device(self, batch, v_cmd_ptr, v_filt_ptr, x0_ptr, t0, horizon, target_times_ptr, target_states_ptr, filter_alpha=0.0, base_vel_ptr=0):
+        """hsqp_command_targets_device: the same with every array in device memory (addresses); v_filt is updated in place.  A centroidal solver
+        calls hsqp_centroidal_command_targets_device; base_vel_ptr (0: not wanted) receives its base velocities [B][6]."""
         cast = lambda a: C.cast(C.c_void_p(int(a)), _dp)  # noqa: E731
+        if self.model.centroidal:
+            self._check(self.lib.hsqp_centroidal_command_targets_device(self.h, int(batch), cast(v_cmd_ptr), cast(v_filt_ptr), C.c_double(filter_alpha), cast(x0_ptr),
+                                                                        C.c_double(t0), C.c_double(horizon), cast(target_times_ptr), cast(target_states_ptr),
+                                                                        cast(base_vel_ptr) if base_vel_ptr else None))
+            return
+        if base_vel_ptr:
+            raise ValueError("base_vel_ptr: a by-product of the centroidal generator")
         self._check(self.lib.hsqp_command_targets_device(self.h, int(batch), cast(v_cmd_ptr), cast(v_filt_ptr), C.c_double(filter_alpha), cast(x0_ptr),
                                                          C.c_double(t0), C.c_double(horizon), cast(target_times_ptr), cast(target_states_ptr)))
 
     def loop_settings(self, n_nodes, dt, period=None, filter_alpha=None, iterations=1, take_step=True, kkt=False, linesearch=True, swing=None,
                       terrain_height=0.0, arm_swing=True, integrator="ode45", controller="feedforward", **tolerances):
         """hsqp_loop_settings: hsqp_loop_defaults (period 1 / 60 s, filter_alpha 0.8) with the grid, the iteration flags of iterate(), the
-        rollout settings of rollout_settings() and the model's swing configuration."""
+        rollout settings of rollout_settings() and the model's swing configuration.  On a centroidal solver the defaults are still the
+        whole-body task file's: pass dt and period from model.sqp."""
         from .reference import swing_config
         st = _abi.LoopSettings()
         self.lib.hsqp_loop_defaults(self.h, C.byref(st))
@@ -1068,8 +1093,9 @@ class HipSqpSolver:
             raise ValueError("inconsistent loop array shapes")
         ip = C.POINTER(C.c_int32)
         self._loop_batch = 0
-        self._check(self.lib.hsqp_loop_start(self.h, C.byref(settings), B, C.c_double(t0), x0.ctypes.data_as(_dp), v_cmd.ctypes.data_as(_dp), event_times.shape[1],
-                                             n_events.ctypes.data_as(ip), event_times.ctypes.data_as(_dp), mode_sequence.ctypes.data_as(ip)))
+        start = self.lib.hsqp_loop_start_centroidal if self.model.centroidal else self.lib.hsqp_loop_start   # (include/hsqp_cent_loop.h)
+        self._check(start(self.h, C.byref(settings), B, C.c_double(t0), x0.ctypes.data_as(_dp), v_cmd.ctypes.data_as(_dp), event_times.shape[1],
+                          n_events.ctypes.data_as(ip), event_times.ctypes.data_as(_dp), mode_sequence.ctypes.data_as(ip)))
         self._loop_batch = B
         self._loop_events = int(event_times.shape[1])
         self._shape = (B, int(settings.n_nodes))
