@@ -353,7 +353,7 @@ int hsqp_download_device(hsqp_handle* h, hsqp_solution* solution);
 #define HSQP_BLK_H 3            /* [B][N][93][93]   dt * Hessian of the stage cost wrt [x;u]              */
 #define HSQP_BLK_G 4            /* [B][N][93]       dt * gradient                                         */
 #define HSQP_BLK_CDE 5          /* [B][N][14][94]   [C|D|e] active equality rows (zero padded)            */
-#define HSQP_BLK_NE 6           /* [B][N] int32     number of active equality rows                        */
+#define HSQP_BLK_NE 6           /* [B][N] int32     number of active equality rows (CDE, NE: none on a zero-length interval, which is solved as the identity jump) */
 #define HSQP_BLK_COST 7         /* [B][N+1]         dt*l_k (terminal: l_N)                                 */
 #define HSQP_BLK_DX 8           /* [B][N+1][58]                                                            */
 #define HSQP_BLK_DU 9           /* [B][N][35]                                                              */

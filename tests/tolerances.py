@@ -24,6 +24,13 @@ which inverts I + C1 J2 of partial horizons (cond ~ 1e9): its |du| error is 0.6 
 1, 2 passes), so a change of rounding upstream of the sweep can move it across the bound — the KKT gate then sends that iteration to the serial
 recursion, which is what keeps the RESULT inside the tolerance; the tests of that path assert the bound on the gated result.
 
+Per-instance event grids (tests/event_grid_cases.py: perturbed trajectories on walk / run horizons with zero-length intervals, |step| up to 2e3) are
+such a population: tests/test_event_forms.py and tests/test_gpu_event_forms.py hold them to assert_step(rel=1e-10), i.e. TRAJ_ABS + 1e-10 x the step's
+scale — the form tests/test_event_nodes.py already uses on event grids; the unrelaxed 1e-8 has no margin there (serial sweeps: worst absolute error 6.3e-9
+on the host, 4.0e-9 on the device, 1.2e-11 of the scale at most; the accepted parallel-in-time sweep 3.1e-8 = 4.6e-11 of the scale) —, the performance index
+to PERF_REL (worst 8.0e-11 on the host, 3.6e-11 on the device), the KKT residual to KKT_REL; the opt-in two-level sweep to its declared 1e-9 of the scale.
+Measured values: profiles/event_forms_parity.txt.
+
 Kernel variants of ONE quantity are held to each other more tightly than to the oracle: the value pass on quads of lanes against its
 phase form 1e-12 relative (sums over bodies / cost terms in another order), the limb-lane form of the LQ approximation against its phase form 1e-10 of the step's scale (LQ blocks: 1e-11 against the oracle, 1e-13 against each other on the host), the blocked matrix-core factorisation against numpy's
 Cholesky 50 eps sqrt(cond) (tests/test_hostemu.py), reference-compiled assembly rows against the oracle 1e-12 (tests/test_ref_assembly.py)."""

@@ -4729,6 +4729,9 @@ long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes) 
     return hipMemcpy(rec.data(), h->d_rec, rec.size() * 8, hipMemcpyDeviceToHost) == hipSuccess;
   };
   std::vector<double> rec;
+  // a zero-length interval is solved as the identity jump (k_jump overwrites its QP record): the stage has no equality rows, whatever the LQ kernels
+  // left in the node's record at dt = 0
+  auto event_node = [&](size_t n) { return h->h_dt.size() == nodes && h->h_dt[n] == 0.0; };
   switch (what) {
     case HSQP_BLK_AB: {
       if (!fetch_rec(rec)) return HSQP_ERR_HIP;
@@ -4781,13 +4784,13 @@ long long hsqp_debug_read(hsqp_handle* h, int what, void* dst, long long bytes) 
       if (!fetch_rec(rec)) return HSQP_ERR_HIP;
       out.resize(nodes * NE_MAX * (NZ + 1));
       for (size_t n = 0; n < nodes; ++n)
-        for (int r = 0; r < NE_MAX; ++r) for (int c = 0; c <= NZ; ++c) out[(n * NE_MAX + r) * (NZ + 1) + c] = rec_CDe_at(&rec[n * REC_SIZE], r, c);
+        for (int r = 0; r < NE_MAX; ++r) for (int c = 0; c <= NZ; ++c) out[(n * NE_MAX + r) * (NZ + 1) + c] = event_node(n) ? 0.0 : rec_CDe_at(&rec[n * REC_SIZE], r, c);
       break;
     }
     case HSQP_BLK_NE: {
       if (!fetch_rec(rec)) return HSQP_ERR_HIP;
       iout.resize(nodes);
-      for (size_t n = 0; n < nodes; ++n) iout[n] = (int)rec[n * REC_SIZE + REC_MISC];
+      for (size_t n = 0; n < nodes; ++n) iout[n] = event_node(n) ? 0 : (int)rec[n * REC_SIZE + REC_MISC];
       break;
     }
     case HSQP_BLK_COST: {
