@@ -22,6 +22,10 @@ BLK_PARAMS, BLK_FORMS = 11, 12
 BLK_X, BLK_U, BLK_STAMPS = 13, 14, 15
 WARM_CALLER, WARM_SHIFT, WARM_COLD = 0, 1, 2   # hsqp_reference::warm_start
 COMM_ID_BYTES = 128   # HSQP_COMM_ID_BYTES
+# hsqp_iterate_device flags (include/hsqp.h; VALUE_FUNCTION: include/hsqp_value.h)
+ITER_TAKE_STEP, ITER_KKT, ITER_LINESEARCH, ITER_UNTIL_CONVERGED, ITER_VALUE_FUNCTION = 1, 2, 4, 8, 16
+VF_SIZE = NX * NX + NX   # one node of the sweeps' value-function record: S row-major, then s
+VALUE_ENTRY_POINTS = ("hsqp_value_function", "hsqp_value_function_device", "hsqp_evaluate_value_function", "hsqp_evaluate_value_function_device")
 
 
 class Body(C.Structure):

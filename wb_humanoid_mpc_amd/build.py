@@ -26,7 +26,7 @@ def build_hip(force=False, verbose=False, extra=(), phase_profile=False):
 
 
 def _build(LIB, force, verbose, extra):
-    srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(_HERE, "..", "include", f) for f in ("hsqp.h", "hsqp_feedback.h", "hsqp_rollout.h", "hsqp_loop.h", "hsqp_gait.h", "hsqp_episode.h", "hsqp_push.h", "hsqp_plant.h", "hsqp_contact.h", "hsqp_actuator.h", "hsqp_inertia.h", "hsqp_observe.h", "hsqp_terrain.h", "hsqp_metrics.h", "hsqp_grid.h", "hsqp_ground.h", "hsqp_perceive.h")]
+    srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(_HERE, "..", "include", f) for f in ("hsqp.h", "hsqp_feedback.h", "hsqp_value.h", "hsqp_rollout.h", "hsqp_loop.h", "hsqp_gait.h", "hsqp_episode.h", "hsqp_push.h", "hsqp_plant.h", "hsqp_contact.h", "hsqp_actuator.h", "hsqp_inertia.h", "hsqp_observe.h", "hsqp_terrain.h", "hsqp_metrics.h", "hsqp_grid.h", "hsqp_ground.h", "hsqp_perceive.h")]
     if not force and os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(s) for s in srcs):
         return LIB
     # -amdgpu-sched-strategy=iterative-ilp: the kernels are chains of short dependent phases at an occupancy fixed by LDS and

@@ -20,6 +20,7 @@
 #include "hsqp_policy.h"
 #include "hsqp_feedback.h"
 #include "../../include/hsqp_feedback.h"
+#include "hsqp_value.h"
 #include "hsqp_rollout.h"
 #include "hsqp_loop.h"
 #include "../../include/hsqp_loop.h"
@@ -1029,6 +1030,29 @@ __global__ __launch_bounds__(FB_THREADS) void k_feedback_eval(const double* __re
   }
 }
 
+// ---- Riccati value function (include/hsqp_value.h, csrc/hsqp_value.h), launched by its entry points only: nothing of it runs inside an iteration.
+//  k_value_record: one workgroup per (node k0 + blockIdx.x, instance blockIdx.y) — the node's S (symmetrised), s and xbar into S [B][count][58][58] /
+//                  s [B][count][58] / xbar [B][count][58] (any may be null).
+//  k_value_eval:   one workgroup per (query blockIdx.x, instance blockIdx.y) — value_eval at (s_query, x_query) into dV [B][n] / dfdx [B][n][58] /
+//                  dfdxx [B][n][58][58] (any may be null).
+__global__ __launch_bounds__(VAL_THREADS) void k_value_record(const double* __restrict__ vf, const double* __restrict__ xbar, int N, int k0, int count, int cent,
+                                                              double* __restrict__ S, double* __restrict__ s, double* __restrict__ xb) {
+  ValueWS& w = *reinterpret_cast<ValueWS*>(hsqp_smem);
+  const int j = blockIdx.x, b = blockIdx.y;
+  const size_t node = (size_t)b * (N + 1) + k0 + j, e = (size_t)b * count + j;
+  value_record_node(Ctx{(int)threadIdx.x, VAL_THREADS, nullptr}, vf + node * VF_SIZE, xbar + node * NX, cent, S ? S + e * NX * NX : nullptr, s ? s + e * NX : nullptr,
+                    xb ? xb + e * NX : nullptr, w);
+}
+__global__ __launch_bounds__(VAL_THREADS) void k_value_eval(const double* __restrict__ vf, const double* __restrict__ xbar, const double* __restrict__ dts, int N, double dt,
+                                                            int uniform, int cent, int n, const double* __restrict__ s_query, const double* __restrict__ x_query,
+                                                            double* __restrict__ dV, double* __restrict__ dfdx, double* __restrict__ dfdxx) {
+  ValueWS& w = *reinterpret_cast<ValueWS*>(hsqp_smem);
+  const int q = blockIdx.x, b = blockIdx.y;
+  const size_t e = (size_t)b * n + q;
+  value_eval(Ctx{(int)threadIdx.x, VAL_THREADS, nullptr}, vf + (size_t)b * (N + 1) * VF_SIZE, xbar + (size_t)b * (N + 1) * NX, uniform ? nullptr : dts + (size_t)b * N, N, dt,
+             cent, s_query[e], x_query + e * NX, dV ? dV + e : nullptr, dfdx ? dfdx + e * NX : nullptr, dfdxx ? dfdxx + e * NX * NX : nullptr, w);
+}
+
 // ---- batched policy rollout (include/hsqp_rollout.h, csrc/hsqp_rollout.h), launched by the rollout entry points only.
 //  k_rollout_window: one workgroup — over the instances, the policy entries the call's times [s0, s0 + duration] reach (the feedback
 //                    controller's gain window [out[0], out[1]]) and whether an s0 is not finite (out[2]).
@@ -1255,6 +1279,11 @@ struct hsqp_handle {
   bool have_problem = false, have_solution = false;
   bool have_policy = false;       // the QP / Riccati records and the solution are those of the last successful iteration (feedback entry points)
   DevBuf<double> d_fb;            // staging of hsqp_feedback_policy (host destinations)
+  // the value-function record (include/hsqp_value.h): kept by an iteration that ran with HSQP_ITER_VALUE_FUNCTION
+  bool have_value = false;        // vf_record / d_xbar are those of the last iteration, which ran with the flag and succeeded
+  const double* vf_record = nullptr;   // d_vf or d_vf2: the value functions of the sweep whose step that iteration accepted
+  DevBuf<double> d_xbar;          // [B][N+1][58] the trajectory that iteration's QP was linearised at (a bit copy of d_x taken before any step)
+  DevBuf<double> d_val;           // staging of the value-function entry points (host arrays)
   DevBuf<double> d_ro_gain;       // gain window of the rollout's feedback controller: K [B][count][35][58], then uff [B][count][35] (allocated when first used, sized by the window)
   DevBuf<char> d_ro;              // staging of the rollout (s0, x0, outputs of the host entry point, window, statuses)
   // the resident push table (include/hsqp_push.h): n_pushes [push_B] (int32, padded to 256 bytes), then pushes [push_B][push_max]; push_B == 0: no table
@@ -1879,6 +1908,7 @@ static void commit_problem(hsqp_handle* h, const hsqp_problem* p, bool have_stam
 static int upload_impl(hsqp_handle* h, const hsqp_problem* p, bool device_src) {
   if (!h) return HSQP_ERR_BAD_ARG;
   h->have_policy = false;
+  h->have_value = false;
   h->loop.started = false;
   if (!p || !p->x_init || !p->x_traj || !p->u_traj || !p->node_params) { h->err = "null problem pointer"; return HSQP_ERR_BAD_ARG; }
   if (!fits_handle(h, p)) return HSQP_ERR_BAD_ARG;
@@ -1992,6 +2022,7 @@ static int upload_reference_impl(hsqp_handle* h, const hsqp_problem* p, const hs
                                  const double* touch_down = nullptr, const char* who = nullptr) {
   if (!h) return HSQP_ERR_BAD_ARG;
   h->have_policy = false;
+  h->have_value = false;
   h->loop.started = false;
   if (!p || !r || !p->x_init || !r->n_events || !r->event_times || !r->mode_sequence || !r->target_times || !r->target_states) {
     h->err = "null problem / reference pointer";
@@ -2108,7 +2139,11 @@ static void launch_value_pass(hsqp_handle* h, const LsState* mask) {
 int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
   const int take_step = flags & HSQP_ITER_TAKE_STEP, want_kkt = (flags & HSQP_ITER_KKT) ? 1 : 0, linesearch = (flags & HSQP_ITER_LINESEARCH) ? 1 : 0;
   if (!h) return HSQP_ERR_BAD_ARG;
+  // HSQP_ITER_VALUE_FUNCTION (include/hsqp_value.h): the sweep whose step is accepted also leaves S_k, s_k of every node (as for the KKT report, but no
+  // k_kkt launch, no joint rows, no read-back) and the iteration starts with a copy of the trajectory it linearises at
+  const int want_value = (flags & HSQP_ITER_VALUE_FUNCTION) ? 1 : 0;
   h->have_policy = false;   // (a failed iteration leaves the records half written)
+  h->have_value = false;    // (... and an iteration without the flag overwrites the sweep's part of the record's buffers or leaves them stale)
   if (!h->have_problem || n_iterations < 1) { h->err = "no problem uploaded or n_iterations < 1"; return HSQP_ERR_BAD_ARG; }
   HCHECK(hipSetDevice(h->device));
   const int B = h->B, N = h->N;
@@ -2180,7 +2215,13 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     }
     h->qp_joint_rows = joint_rows;
     if (last) HCHECK(hipEventRecord(h->ev[2], h->stream));
-    if (want_kkt) DEV_ENSURE(h->d_vf, vf_bytes(h), "value functions");
+    if (want_kkt || want_value) DEV_ENSURE(h->d_vf, vf_bytes(h), "value functions");
+    if (want_value) {   // xbar: d_x is only replaced between iterations, so the last iteration's copy is the record's
+      DEV_ENSURE(h->d_xbar, (size_t)h->st.max_batch * (h->st.max_nodes + 1) * NX * 8, "value function: linearisation trajectory");
+      HCHECK(hipMemcpyAsync(h->d_xbar, h->d_x, (size_t)B * (N + 1) * NX * 8, hipMemcpyDeviceToDevice, h->stream));
+    }
+    const bool keep_vf = want_kkt || want_value;
+    const double* vf_kept = h->d_vf;   // where the sweep whose step is accepted leaves its value functions
     const int Bm = h->st.max_batch;
     const size_t gate_bytes = h->gate.bytes;
     int ut_given = 0;   // the last sweep's roll-out left ut = k + K dx of every node in d_ut (the serial roll-out does, the scan's closed-loop roll-out does not)
@@ -2188,7 +2229,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
     auto launch_sweep = [&](bool use_scan, bool need_vf) -> int {
       ut_given = (use_scan && segP == 0) ? 0 : 1;
       fj_given = 0;
-      if (use_scan && segP > 0) return cent ? launch_segmented<CNX>(h, B, N, segP, want_kkt != 0) : launch_segmented<NX>(h, B, N, segP, want_kkt != 0);
+      if (use_scan && segP > 0) return cent ? launch_segmented<CNX>(h, B, N, segP, keep_vf) : launch_segmented<NX>(h, B, N, segP, keep_vf);
       if (use_scan) return cent ? launch_scan<CNX>(h, B, N, need_vf, 1) : launch_scan<NX>(h, B, N, need_vf, HSQP_SCAN_WB_REFINEMENTS);
       if (cent)   // the serial recursion on the 35 centroidal states only (the padding states are decoupled)
         HSQP_LAUNCH(k_riccati<CNX>, dim3(B), dim3(RIC_THREADS), sizeof(RicWS), h->stream, h->d_dm, h->d_xinit, h->d_x, h->d_par, h->d_qp,
@@ -2222,7 +2263,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
       return e;
     };
     if (scan) HCHECK(hipMemsetAsync(h->d_kkt, 0, gate_bytes, h->stream));   // also the flags the scan kernels OR into
-    { const int rc = launch_sweep(scan, want_kkt || scan); if (rc != HSQP_OK) return rc; }
+    { const int rc = launch_sweep(scan, keep_vf || scan); if (rc != HSQP_OK) return rc; }
     if (last) HCHECK(hipEventRecord(h->ev[3], h->stream));   // kernel_ms buckets: {lq, project, riccati (backward + forward sweep), step + value pass + reductions}
     launch_step();
     if (scan) {   // the gate's inputs: KKT residuals, |g|_inf and the scan kernels' flags travel to pinned host memory while the kernels below run
@@ -2256,11 +2297,11 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
         fprintf(stderr, "[hsqp seg gate] P=%d boundary-stage KKT stat %.3e prim %.3e |g| %.3e flags %d accept %d\n", segP, m0, m1, m2, fl, (int)accept);
       }
       if (accept && segP > 0 && want_kkt) HCHECK(launch_kkt(h->d_vf2, false));   // the KKT report of an accepted two-level sweep (the gate block is reused)
-      if (accept) h->seg_backoff_len = 0;   // (the back-off: choose_sweep)
+      if (accept) { h->seg_backoff_len = 0; vf_kept = h->d_vf2; }   // (the back-off: choose_sweep)
       else {
         h->seg_backoff_len = std::min(2 * h->seg_backoff_len + 1, 63); h->seg_backoff = h->seg_backoff_len;
         ++h->scan_fallbacks;
-        { const int rc = launch_sweep(false, want_kkt != 0); if (rc != HSQP_OK) return rc; }
+        { const int rc = launch_sweep(false, keep_vf); if (rc != HSQP_OK) return rc; }
         if (last) HCHECK(hipEventRecord(h->ev[3], h->stream));
         launch_step();
         if (want_kkt) HCHECK(launch_kkt(h->d_vf, false));
@@ -2299,6 +2340,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
       if (still_active) { h->err = "line search: trials exhausted with instances still undecided (internal error)"; return HSQP_ERR_NUMERIC; }
     }
     h->ls_ran = linesearch != 0;
+    h->vf_record = vf_kept;
     if (last && !ev4_early) HCHECK(hipEventRecord(h->ev[4], h->stream));
     h->last_iterations = it + 1;
     if (until_converged) {
@@ -2347,6 +2389,7 @@ int hsqp_iterate_device(hsqp_handle* h, int n_iterations, int flags) {
   h->kernel_ms[4] = h->kernel_ms[0] + h->kernel_ms[1] + h->kernel_ms[2] + h->kernel_ms[3];
   h->have_solution = true;
   h->have_policy = true;
+  h->have_value = want_value != 0;
   return HSQP_OK;
 }
 
@@ -2365,6 +2408,7 @@ int hsqp_iteration_log(const hsqp_handle* h, int iteration, hsqp_perf* perf, dou
 
 int hsqp_update_weights(hsqp_handle* h, const double* Q, const double* R, const double* Qf) {
   if (!h) return HSQP_ERR_BAD_ARG;
+  h->have_value = false;   // (the record is the cost-to-go under the weights it was swept with)
   // explicit lengths (Q: 58, R: 35, Qf: 58; the same buffer may be passed twice) and the conditions build_dev_model (hsqp_create, hsqp_update_term_weights)
   // applies to them: state weights finite and >= 0, input weights finite and > 0 (the reduced Hessian
   // Lam = R~ + B~^T S B~ of every stage has to stay positive definite)
@@ -2408,6 +2452,7 @@ int hsqp_get_term_weights(const hsqp_handle* h, hsqp_term_weights* out) {
 
 int hsqp_update_term_weights(hsqp_handle* h, const hsqp_term_weights* w) {
   if (!h) return HSQP_ERR_BAD_ARG;
+  h->have_value = false;
   if (!w) { h->err = "hsqp_update_term_weights: null argument"; return HSQP_ERR_BAD_ARG; }
   const double* all = reinterpret_cast<const double*>(w);
   for (size_t i = 0; i < sizeof(hsqp_term_weights) / sizeof(double); ++i)
@@ -2596,6 +2641,96 @@ int hsqp_evaluate_feedback_policy(hsqp_handle* h, const double* s, const double*
   { const int rc = feedback_ready(h, "hsqp_evaluate_feedback_policy"); if (rc != HSQP_OK) return rc; }
   if (!s || !x_meas) { h->err = "hsqp_evaluate_feedback_policy: null time offsets or measured states"; return HSQP_ERR_BAD_ARG; }
   return run_policy(h, h->B, true, s, nullptr, x_meas, x, u, tau);
+}
+
+// ---- Riccati value function (include/hsqp_value.h, csrc/hsqp_value.h)
+static int value_ready(hsqp_handle* h, const char* who) {
+  if (!h->have_value || !h->vf_record) {
+    h->err = std::string(who) + ": no value-function record (the last call that touched it was not a successful iteration with HSQP_ITER_VALUE_FUNCTION)";
+    return HSQP_ERR_BAD_ARG;
+  }
+  return HSQP_OK;
+}
+
+static int value_function_impl(hsqp_handle* h, int k0, int k1, double* S, double* s, double* xbar, bool device_dst) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = device_dst ? "hsqp_value_function_device" : "hsqp_value_function";
+  { const int rc = value_ready(h, who); if (rc != HSQP_OK) return rc; }
+  if (k0 < 0 || k0 > k1 || k1 > h->N) { h->err = std::string(who) + ": nodes k0 .. k1 outside [0, N], or k0 > k1"; return HSQP_ERR_BAD_ARG; }
+  if (!S && !s && !xbar) return HSQP_OK;
+  HCHECK(hipSetDevice(h->device));
+  const size_t B = h->B, count = (size_t)(k1 - k0 + 1), nS = B * count * NX * NX, nv = B * count * NX;
+  double* dS = S; double* ds = s; double* dxb = xbar;
+  if (!device_dst) {
+    DEV_ENSURE(h->d_val, ((S ? nS : 0) + (s ? nv : 0) + (xbar ? nv : 0)) * 8, "value function staging");
+    double* p = h->d_val.p;
+    dS = S ? p : nullptr; p += S ? nS : 0;
+    ds = s ? p : nullptr; p += s ? nv : 0;
+    dxb = xbar ? p : nullptr;
+  }
+  StickyError step{h};
+  HSQP_LAUNCH(k_value_record, dim3((unsigned)count, (unsigned)B), dim3(VAL_THREADS), sizeof(ValueWS), h->stream, h->vf_record, (const double*)h->d_xbar, h->N, k0, (int)count,
+              h->hdm.formulation == HSQP_FORM_CENTROIDAL ? 1 : 0, dS, ds, dxb);
+  step(hipGetLastError(), "k_value_record");
+  if (!device_dst) {
+    if (S) step(hipMemcpyAsync(S, dS, nS * 8, hipMemcpyDeviceToHost, h->stream), "download S");
+    if (s) step(hipMemcpyAsync(s, ds, nv * 8, hipMemcpyDeviceToHost, h->stream), "download s");
+    if (xbar) step(hipMemcpyAsync(xbar, dxb, nv * 8, hipMemcpyDeviceToHost, h->stream), "download xbar");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+
+int hsqp_value_function(hsqp_handle* h, int k0, int k1, double* S, double* s, double* xbar) { return value_function_impl(h, k0, k1, S, s, xbar, false); }
+int hsqp_value_function_device(hsqp_handle* h, int k0, int k1, double* d_S, double* d_s, double* d_xbar) { return value_function_impl(h, k0, k1, d_S, d_s, d_xbar, true); }
+
+static int evaluate_value_impl(hsqp_handle* h, int n, const double* sq, const double* xq, double* dV, double* dfdx, double* dfdxx, bool dev) {
+  if (!h) return HSQP_ERR_BAD_ARG;
+  const char* who = dev ? "hsqp_evaluate_value_function_device" : "hsqp_evaluate_value_function";
+  { const int rc = value_ready(h, who); if (rc != HSQP_OK) return rc; }
+  if (n < 1) { h->err = std::string(who) + ": n_queries < 1"; return HSQP_ERR_BAD_ARG; }
+  if (!sq || !xq) { h->err = std::string(who) + ": null s_query or x_query"; return HSQP_ERR_BAD_ARG; }
+  const size_t B = h->B, nq = B * (size_t)n;
+  if (!dev)
+    for (size_t i = 0; i < nq; ++i)
+      if (!std::isfinite(sq[i])) { h->err = std::string(who) + ": s_query must be finite"; return HSQP_ERR_BAD_ARG; }
+  if (!dV && !dfdx && !dfdxx) return HSQP_OK;
+  HCHECK(hipSetDevice(h->device));
+  const double* d_sq = sq; const double* d_xq = xq;
+  double* d_dV = dV; double* d_g = dfdx; double* d_H = dfdxx;
+  StickyError step{h};
+  if (!dev) {
+    DEV_ENSURE(h->d_val, (nq + nq * NX + (dV ? nq : 0) + (dfdx ? nq * NX : 0) + (dfdxx ? nq * NX * NX : 0)) * 8, "value function staging");
+    double* p = h->d_val.p;
+    double* in_s = p; p += nq;
+    double* in_x = p; p += nq * NX;
+    d_dV = dV ? p : nullptr; p += dV ? nq : 0;
+    d_g = dfdx ? p : nullptr; p += dfdx ? nq * NX : 0;
+    d_H = dfdxx ? p : nullptr;
+    step(hipMemcpyAsync(in_s, sq, nq * 8, hipMemcpyHostToDevice, h->stream), "upload s_query");
+    step(hipMemcpyAsync(in_x, xq, nq * NX * 8, hipMemcpyHostToDevice, h->stream), "upload x_query");
+    d_sq = in_s; d_xq = in_x;
+  }
+  if (step.rc == HSQP_OK) {
+    HSQP_LAUNCH(k_value_eval, dim3((unsigned)n, (unsigned)B), dim3(VAL_THREADS), sizeof(ValueWS), h->stream, h->vf_record, (const double*)h->d_xbar, (const double*)h->d_dt, h->N,
+                h->dt, h->uniform_grid ? 1 : 0, h->hdm.formulation == HSQP_FORM_CENTROIDAL ? 1 : 0, n, d_sq, d_xq, d_dV, d_g, d_H);
+    step(hipGetLastError(), "k_value_eval");
+  }
+  if (!dev) {
+    if (dV) step(hipMemcpyAsync(dV, d_dV, nq * 8, hipMemcpyDeviceToHost, h->stream), "download dV");
+    if (dfdx) step(hipMemcpyAsync(dfdx, d_g, nq * NX * 8, hipMemcpyDeviceToHost, h->stream), "download dfdx");
+    if (dfdxx) step(hipMemcpyAsync(dfdxx, d_H, nq * NX * NX * 8, hipMemcpyDeviceToHost, h->stream), "download dfdxx");
+  }
+  step(hipStreamSynchronize(h->stream), "sync");
+  return step.rc;
+}
+
+int hsqp_evaluate_value_function(hsqp_handle* h, int n_queries, const double* s_query, const double* x_query, double* dV, double* dfdx, double* dfdxx) {
+  return evaluate_value_impl(h, n_queries, s_query, x_query, dV, dfdx, dfdxx, false);
+}
+int hsqp_evaluate_value_function_device(hsqp_handle* h, int n_queries, const double* d_s_query, const double* d_x_query, double* d_dV, double* d_dfdx,
+                                        double* d_dfdxx) {
+  return evaluate_value_impl(h, n_queries, d_s_query, d_x_query, d_dV, d_dfdx, d_dfdxx, true);
 }
 
 // ---- batched policy rollout (include/hsqp_rollout.h, csrc/hsqp_rollout.h)
@@ -3840,6 +3975,7 @@ static int loop_cycle(hsqp_handle* h, double* d_xlog, double* d_ulog) {
   p.batch = L.B; p.n_nodes = grid ? st.n_nodes + L.grid_st.event_nodes : st.n_nodes; p.dt = st.dt; p.x_init = xm;
   // step 2's checks come first, as in hsqp_upload_reference: a rejected cycle leaves the resident solution as it was
   h->have_policy = false;
+  h->have_value = false;
   const int N_prev = h->N;
   if (warm == HSQP_WARM_SHIFT) { const int rc = warm_shift_ready(h, L.B, true, iso); if (rc != HSQP_OK) return rc; }
   StickyError step{h};

@@ -16,6 +16,7 @@
 
 #include "../../include/hsqp.h"
 #include "../../include/hsqp_feedback.h"
+#include "../../include/hsqp_value.h"
 #include "../../include/hsqp_rollout.h"
 #include "../../include/hsqp_loop.h"
 #include "../../include/hsqp_cent_loop.h"
@@ -155,6 +156,32 @@ class HipSqpSolver {
     state.assign(B * HSQP_NX, 0.0); input.assign(B * HSQP_NU, 0.0); jointTorques.assign(B * HSQP_NJ, 0.0);
     const int rc = hsqp_evaluate_feedback_policy(h_, secondsAfterStart.data(), measuredState.data(), state.data(), input.data(), jointTorques.data());
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_evaluate_feedback_policy failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+
+  /** sqp::Settings::createValueFunction: the runWithReference / runRecedingHorizon calls that follow keep the Riccati value function of their last
+   *  iteration (HSQP_ITER_VALUE_FUNCTION, include/hsqp_value.h) for valueFunction / evaluateValueFunction; off by default — the record costs device
+   *  memory, not time.  run() goes through hsqp_solve, which knows no such flag: it ignores this setting and clears a record kept earlier. */
+  void setKeepValueFunction(bool on) { keepValue_ = on; }
+  /** The record of nodes k0 .. k1 (k1 < 0: node N) of every instance: S [batch][n][HSQP_NX][HSQP_NX] (symmetric), s and xbar [batch][n][HSQP_NX], row-major;
+   *  the cost-to-go is s' dx + 1/2 dx' S dx in dx = x - xbar, xbar the trajectory the last QP was linearised at. */
+  void valueFunction(int k0, int k1, std::vector<double>& S, std::vector<double>& s, std::vector<double>& xbar) {
+    const size_t B = (size_t)solution_.batch;
+    if (k1 < 0) k1 = solution_.nodes;
+    const size_t n = k1 >= k0 ? (size_t)(k1 - k0 + 1) : 0;
+    S.assign(B * n * HSQP_NX * HSQP_NX, 0.0); s.assign(B * n * HSQP_NX, 0.0); xbar.assign(B * n * HSQP_NX, 0.0);
+    const int rc = hsqp_value_function(h_, k0, k1, S.data(), s.data(), xbar.data());
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_value_function failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
+  }
+  /** SolverBase::getValueFunction for nQueries (time, state) pairs per instance: secondsAfterStart [batch][nQueries], state [batch][nQueries][HSQP_NX];
+   *  dV [batch][nQueries], dfdx [batch][nQueries][HSQP_NX], dfdxx [batch][nQueries][HSQP_NX][HSQP_NX] (withHessian = false leaves it empty). */
+  void evaluateValueFunction(int nQueries, const std::vector<double>& secondsAfterStart, const std::vector<double>& state, std::vector<double>& dV,
+                             std::vector<double>& dfdx, std::vector<double>& dfdxx, bool withHessian = true) {
+    const size_t B = (size_t)solution_.batch, n = nQueries > 0 ? (size_t)nQueries : 0;
+    if (nQueries < 1 || secondsAfterStart.size() != B * n || state.size() != B * n * HSQP_NX)
+      throw std::runtime_error("[HipSqpSolver] evaluateValueFunction: nQueries >= 1 and one time and one state per instance and query expected");
+    dV.assign(B * n, 0.0); dfdx.assign(B * n * HSQP_NX, 0.0); dfdxx.assign(withHessian ? B * n * HSQP_NX * HSQP_NX : 0, 0.0);
+    const int rc = hsqp_evaluate_value_function(h_, nQueries, secondsAfterStart.data(), state.data(), dV.data(), dfdx.data(), withHessian ? dfdxx.data() : nullptr);
+    if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_evaluate_value_function failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
   }
 
   /** MRT_BASE::rolloutPolicy for every instance of the last run (include/hsqp_rollout.h): instance b from x0[b] (one HSQP_NX row per
@@ -704,7 +731,8 @@ class HipSqpSolver {
     int rc = hsqp_upload_reference(h_, &p, &ref);
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_upload_reference failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     rc = hsqp_iterate_device(h_, maxIterations < 1 ? 1 : maxIterations,
-                             HSQP_ITER_TAKE_STEP | (reportKkt_ ? HSQP_ITER_KKT : 0) | (takeStepWithLinesearch ? HSQP_ITER_LINESEARCH : 0) | HSQP_ITER_UNTIL_CONVERGED);
+                             HSQP_ITER_TAKE_STEP | (reportKkt_ ? HSQP_ITER_KKT : 0) | (takeStepWithLinesearch ? HSQP_ITER_LINESEARCH : 0) | HSQP_ITER_UNTIL_CONVERGED |
+                                 (keepValue_ ? HSQP_ITER_VALUE_FUNCTION : 0));
     if (rc != HSQP_OK) throw std::runtime_error("[HipSqpSolver] hsqp_iterate_device failed (" + std::to_string(rc) + "): " + hsqp_last_error(h_));
     shiftable_ = true;
     iterations_ = hsqp_last_iterations(h_);
@@ -737,6 +765,7 @@ class HipSqpSolver {
   Benchmarks bench_;
   int iterations_ = 0;
   bool reportKkt_ = false;
+  bool keepValue_ = false;   // setKeepValueFunction
   size_t loopBatch_ = 0;     // instances of the started loop (startLoop)
   size_t loopNodes_ = 0;     // its n_nodes
   size_t gridNodes_ = 0;     // n_nodes + event_nodes of its last setLoopEventGrid (0: none since the start)

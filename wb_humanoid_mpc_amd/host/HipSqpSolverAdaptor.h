@@ -51,6 +51,10 @@ struct HipSqpAdaptorConfig {
   // WeightCompInitializer (the device builds that one: state kept, weight-compensating input of the node's contact flags).  The trajectories
   // are still downloaded (getPrimalSolution).  The runImpl overload with an external PrimalSolution takes the host path for that call.
   bool deviceWarmStart = false;
+  // sqp::Settings::createValueFunction of upstream ocs2_sqp (the stand-in settings struct of the tests does not carry it, so it lives here): every
+  // iteration keeps the Riccati cost-to-go of its QP on the device (HSQP_ITER_VALUE_FUNCTION, include/hsqp_value.h) and getValueFunction answers from
+  // it.  Off: getValueFunction throws.  The record costs device memory ((maxNodes + 1) x 27 KB), no time inside the iteration.
+  bool createValueFunction = false;
   // rolloutPolicy's integrator (include/hsqp_rollout.h): the task.info rollout block by default; the controller field is ignored — the rollout
   // follows sqp::Settings::useFeedbackPolicy like the PrimalSolution's controller.  INTEGRATION.md: filling it from interface.rolloutSettings().
   hsqp_rollout_settings rollout = rolloutDefaults();
@@ -92,6 +96,7 @@ class HipSqpSolverAdaptor final : public SolverBase {
     ls.g_max = settings_.g_max; ls.g_min = settings_.g_min; ls.gamma_c = settings_.gamma_c; ls.armijo_factor = settings_.armijoFactor;
     ls.alpha_decay = settings_.alpha_decay; ls.alpha_min = settings_.alpha_min; ls.delta_tol = settings_.deltaTol; ls.cost_tol = settings_.costTol;
     impl_.setLinesearchSettings(ls);
+    impl_.setKeepValueFunction(cfg_.createValueFunction);
   }
 
   void reset() override { primal_.clear(); gainK_.clear(); gainUff_.clear(); log_.clear(); numIterations_ = 0; benchmarks_ = HipSqpBenchmarks(); }
@@ -136,15 +141,41 @@ class HipSqpSolverAdaptor final : public SolverBase {
     }
     out->controllerPtr_.reset(new LinearController(out->timeTrajectory_, std::move(bias), std::move(gain)));
   }
-  // ---- the rest of SolverBase's pure-virtual query interface.  Upstream SqpSolver answers these the same way: it throws "not
-  //      implemented" for the value function, the Hamiltonian, the Lagrangian and the multipliers (ocs2_sqp/SqpSolver.h); the
-  //      optimal control problem lives on the device here (hsqp_model_desc), so there is no host OptimalControlProblem to hand out.
+  // ---- the rest of SolverBase's pure-virtual query interface.  Upstream SqpSolver throws "not implemented" for the Hamiltonian, the
+  //      Lagrangian and the multipliers (ocs2_sqp/SqpSolver.h) and so does this class; the value function it answers with
+  //      sqp::Settings::createValueFunction, as getValueFunction below does with HipSqpAdaptorConfig::createValueFunction.  The optimal
+  //      control problem lives on the device here (hsqp_model_desc), so there is no host OptimalControlProblem to hand out.
   const OptimalControlProblem& getOptimalControlProblem() const override {
     throw std::runtime_error("[HipSqpSolverAdaptor] getOptimalControlProblem() not available: the problem definition is device code (hsqp_model_desc)");
   }
   const DualSolution* getDualSolution() const override { return nullptr; }   // upstream SqpSolver: nullptr as well (no dual solution)
-  ScalarFunctionQuadraticApproximation getValueFunction(scalar_t, const vector_t&) const override {
-    throw std::runtime_error("[HipSqpSolverAdaptor] getValueFunction() not implemented");
+  /** {f = 0, dfdx, dfdxx} of the last QP's cost-to-go at (time, state) (hsqp_evaluate_value_function, one query): dfdx = s + S dx, dfdxx = S with
+   *  S, s and the centre xbar interpolated on the state segment of evaluatePolicy, dx = state - xbar.  The constant of the cost-to-go is not
+   *  computed: f = 0.  Declared difference from upstream: ocs2 re-centres on the post-step nominal trajectory, this class on the trajectory
+   *  the QP was linearised at, where the quadratic lives (include/hsqp_value.h).  valueFunctionAt hands out the same numbers as plain arrays
+   *  together with dV = s' dx + 1/2 dx' S dx. */
+  ScalarFunctionQuadraticApproximation getValueFunction(scalar_t time, const vector_t& state) const override {
+    std::vector<double> dV, g, H;
+    valueFunctionAt(time, state, dV, g, H);
+    const int nx = cfg_.stateDim;
+    ScalarFunctionQuadraticApproximation q;
+    q.f = 0.0;
+    q.dfdx = vector_t(nx);
+    for (int i = 0; i < nx; ++i) q.dfdx[i] = g[i];
+    setDfdxx(q, H, nx, 0);
+    return q;
+  }
+  /** dV [1], dfdx [HSQP_NX], dfdxx [HSQP_NX][HSQP_NX] (row-major, padded to the device layout) of getValueFunction(time, state) */
+  void valueFunctionAt(scalar_t time, const vector_t& state, std::vector<double>& dV, std::vector<double>& dfdx, std::vector<double>& dfdxx) const {
+    if (!cfg_.createValueFunction)
+      throw std::runtime_error("[HipSqpSolverAdaptor] getValueFunction(): no value function is kept, set HipSqpAdaptorConfig::createValueFunction "
+                               "(sqp::Settings::createValueFunction of upstream)");
+    if (primal_.timeTrajectory_.empty()) throw std::runtime_error("[HipSqpSolverAdaptor] getValueFunction(): no problem solved yet");
+    if ((int)state.size() != cfg_.stateDim) throw std::runtime_error("[HipSqpSolverAdaptor] getValueFunction(): state has the wrong dimension");
+    std::vector<double> x(HSQP_NX, 0.0);
+    std::copy_n(state.data(), cfg_.stateDim, x.data());
+    // (a query of a const solver: it changes nothing the class hands out, but the device call stages its arrays in the handle, hence the cast)
+    const_cast<hsqp_host::HipSqpSolver&>(impl_).evaluateValueFunction(1, {time - primal_.timeTrajectory_.front()}, x, dV, dfdx, dfdxx);
   }
   ScalarFunctionQuadraticApproximation getHamiltonian(scalar_t, const vector_t&, const vector_t&) override {
     throw std::runtime_error("[HipSqpSolverAdaptor] getHamiltonian() not implemented");
@@ -194,6 +225,18 @@ class HipSqpSolverAdaptor final : public SolverBase {
   }
 
  private:
+  // dfdxx of an ocs2 ScalarFunctionQuadraticApproximation (a stand-in struct without that member compiles too: the second overload).
+  // NOT COMPILED BY THIS REPOSITORY'S TESTS: their stand-in struct (tests/stubs) has no dfdxx, so they instantiate the second overload only and
+  // check f and dfdx of getValueFunction; the Hessian is checked through valueFunctionAt's arrays.  The first overload meets a compiler with real ocs2.
+  template <class Q>
+  static auto setDfdxx(Q& q, const std::vector<double>& H, int nx, int) -> decltype((void)q.dfdxx) {
+    q.dfdxx = matrix_t(nx, nx);
+    for (int i = 0; i < nx; ++i)
+      for (int j = 0; j < nx; ++j) q.dfdxx(i, j) = H[(size_t)i * HSQP_NX + j];
+  }
+  template <class Q>
+  static void setDfdxx(Q&, const std::vector<double>&, int, long) {}
+
   // clamped linear interpolation of the previous solution (ocs2 LinearInterpolation on the PrimalSolution stamps)
   static void interpolate(const scalar_array_t& t, const vector_array_t& v, scalar_t time, double* out, int n) {
     if (time <= t.front()) { std::copy_n(v.front().data(), n, out); return; }

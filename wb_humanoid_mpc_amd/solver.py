@@ -91,6 +91,11 @@ def load_library():
     lib.hsqp_feedback_policy.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
     lib.hsqp_feedback_policy_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
     lib.hsqp_evaluate_feedback_policy.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
+    # include/hsqp_value.h
+    lib.hsqp_value_function.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]
+    lib.hsqp_value_function_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]
+    lib.hsqp_evaluate_value_function.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]
+    lib.hsqp_evaluate_value_function_device.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]
     # include/hsqp_rollout.h
     _ip = C.POINTER(C.c_int32)
     lib.hsqp_rollout_defaults.argtypes = [C.POINTER(_abi.RolloutSettings)]
@@ -459,11 +464,12 @@ class HipSqpSolver:
             raise HsqpError(n, self.lib.hsqp_last_error(self.h).decode())
         return a
 
-    def iterate(self, n_iterations=1, take_step=False, kkt=False, linesearch=False, until_converged=False):
+    def iterate(self, n_iterations=1, take_step=False, kkt=False, linesearch=False, until_converged=False, value_function=False):
         """until_converged: n_iterations is an upper bound; the call ends when every instance's step is below deltaTol (or no step length
-        was accepted): ocs2's SqpSolver::checkConvergence.  Returns the number of iterations run."""
+        was accepted): ocs2's SqpSolver::checkConvergence.  value_function: keep the Riccati value function of the last iteration
+        (HSQP_ITER_VALUE_FUNCTION; value_function / evaluate_value_function below).  Returns the number of iterations run."""
         self._check(self.lib.hsqp_iterate_device(self.h, n_iterations, (1 if take_step else 0) | (2 if kkt else 0) | (4 if linesearch else 0) |
-                                                 (8 if until_converged else 0)))
+                                                 (8 if until_converged else 0) | (_abi.ITER_VALUE_FUNCTION if value_function else 0)))
         return int(self.lib.hsqp_last_iterations(self.h))
 
     def iteration_log(self, iteration):
@@ -583,6 +589,43 @@ class HipSqpSolver:
         self._check(self.lib.hsqp_evaluate_feedback_policy(self.h, s.ctypes.data_as(_dp), x_meas.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
                                                            u.ctypes.data_as(_dp), tau.ctypes.data_as(_dp)))
         return x, u, tau
+
+    # ---- the Riccati value function (include/hsqp_value.h; ocs2 SqpSolver::getValueFunction, createValueFunction)
+    def value_function(self, k0=0, k1=None):
+        """The record of nodes k0 .. k1 (k1 None: node N) an iterate(..., value_function=True) left: (S[B, n, 58, 58] symmetric, s[B, n, 58],
+        xbar[B, n, 58]) — the cost-to-go s' dx + 1/2 dx' S dx in dx = x - xbar, xbar the trajectory the QP was linearised at."""
+        B, N = self._shape
+        if k1 is None:
+            k1 = N
+        n = max(int(k1) - int(k0) + 1, 0)
+        S, s, xbar = np.zeros((B, n, _abi.NX, _abi.NX)), np.zeros((B, n, _abi.NX)), np.zeros((B, n, _abi.NX))
+        self._check(self.lib.hsqp_value_function(self.h, int(k0), int(k1), S.ctypes.data_as(_dp), s.ctypes.data_as(_dp), xbar.ctypes.data_as(_dp)))
+        return S, s, xbar
+
+    def value_function_device(self, k0, k1, S_ptr=0, s_ptr=0, xbar_ptr=0):
+        """hsqp_value_function_device: the same into device memory (device addresses, 0 = not wanted)."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_value_function_device(self.h, int(k0), int(k1), cast(S_ptr), cast(s_ptr), cast(xbar_ptr)))
+
+    def evaluate_value_function(self, s, x, hessian=True):
+        """getValueFunction(t, x) at s[B, n] (or [B]: one query per instance) seconds after the first node and the states x[B, n, 58]:
+        (dV[B, n], dfdx[B, n, 58], dfdxx[B, n, 58, 58] or None without hessian); dV = s' dx + 1/2 dx' S dx is the value relative to the nominal."""
+        B, _ = self._shape
+        s = np.asarray(s, dtype=np.float64)
+        s = _c(s.reshape(B, -1) if s.ndim else np.full((B, 1), float(s)))
+        n = s.shape[1]
+        x = np.asarray(x, dtype=np.float64)
+        x = _c(np.broadcast_to(x.reshape(B, 1, _abi.NX) if x.ndim == 2 else x, (B, n, _abi.NX)))   # ([B, 58]: the same state for an instance's queries)
+        dV, g = np.zeros((B, n)), np.zeros((B, n, _abi.NX))
+        H = np.zeros((B, n, _abi.NX, _abi.NX)) if hessian else None
+        self._check(self.lib.hsqp_evaluate_value_function(self.h, n, s.ctypes.data_as(_dp), x.ctypes.data_as(_dp), dV.ctypes.data_as(_dp), g.ctypes.data_as(_dp),
+                                                          H.ctypes.data_as(_dp) if hessian else None))
+        return dV, g, H
+
+    def evaluate_value_function_device(self, n_queries, s_ptr, x_ptr, dV_ptr=0, dfdx_ptr=0, dfdxx_ptr=0):
+        """hsqp_evaluate_value_function_device: every array in device memory (device addresses, 0 = output not wanted)."""
+        cast = lambda a: C.cast(C.c_void_p(int(a)), _dp) if a else None  # noqa: E731
+        self._check(self.lib.hsqp_evaluate_value_function_device(self.h, int(n_queries), cast(s_ptr), cast(x_ptr), cast(dV_ptr), cast(dfdx_ptr), cast(dfdxx_ptr)))
 
     # ---- batched policy rollout (include/hsqp_rollout.h; ocs2 MRT_BASE::rolloutPolicy)
     _INTEGRATORS = {"ode45": _abi.ROLLOUT_ODE45, "rk4": _abi.ROLLOUT_RK4}
